@@ -25,6 +25,9 @@ says whether that profile was taken on the sources being run.  `cpu_baseline` is
 same range and filter, or the oracle port if the binary is not there.
 
     python bench.py --cmd mul      non-headline: the `mul` path (2^24 seeded scalars per step through ecl_hip_mul_batch)
+    python bench.py ... --dump-outputs DIR
+                                   after the timed steps: what the timed path returned in its last step (the found records)
+                                   as DIR/<name>.npy, float64, so that two builds can be compared output for output
 """
 import argparse
 import glob
@@ -68,6 +71,39 @@ def splitmix_hashes(n, seed):
 
 def planted_offsets(nkeys):
     return [(nkeys // PLANTED) * i + 12345 * (i + 1) % 4096 for i in range(PLANTED)]
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: cap of all files together
+
+
+def dump_outputs(path, count, rows, extra=None):
+    """--dump-outputs DIR: the records the timed path handed its caller in its last step, one DIR/<name>.npy per field, float64
+    (every value is a 32-bit word, an index, a flag or a count: exact).  `rows` maps name -> array with one row per record, already
+    in a canonical order; `count` is how many records there were; `extra`: small arrays written as they are.  More rows than fit
+    DUMP_BYTES: a fixed seeded sample of them (rows_sampled names which)."""
+    os.makedirs(path, exist_ok=True)
+    rows = {k: np.asarray(v, dtype=np.float64) for k, v in rows.items()}
+    assert all(len(v) == count for v in rows.values())
+    per_row = sum(int(np.prod(v.shape[1:])) for v in rows.values()) * 8
+    keep = min(count, (DUMP_BYTES - (1 << 20)) // max(per_row + 8, 1))
+    out = {"found_count": np.array([count], dtype=np.float64)}
+    out.update({k: np.asarray(v, dtype=np.float64) for k, v in (extra or {}).items()})
+    if keep < count:
+        pick = np.sort(np.random.default_rng(2025).choice(count, keep, replace=False))
+        rows = {k: v[pick] for k, v in rows.items()}
+        out["rows_sampled"] = pick.astype(np.float64)
+    out.update(rows)
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
+def dump_found_records(path, recs):
+    """the found list of KeySearch.add_keys (FoundRecord: label, hash160 words, private key), sorted by private key then kind"""
+    pk = np.array([[(r[0] >> (32 * (7 - i))) & 0xFFFFFFFF for i in range(8)] for r in recs], dtype=np.uint64).reshape(-1, 8)
+    h160 = np.array([r[1] for r in recs], dtype=np.uint64).reshape(-1, 5)
+    comp = np.array([r[2] for r in recs], dtype=np.uint64)
+    order = np.lexsort(np.hstack([pk, comp[:, None], h160])[:, ::-1].T)
+    dump_outputs(path, len(recs), {"found_private_key_u32": pk[order], "found_hash160_u32": h160[order], "found_compressed": comp[order]})
 
 
 def build_filter(dev, start, nkeys, filter_n=FILTER_N, ranges=1, cuda_index=0):
@@ -488,6 +524,16 @@ def bench_mul(args, sync, dev_index, emit):
     sync.barrier()
     dt = sync.allmax(time.perf_counter() - t0)
     ms, calls, nsc = ks.dev.mul_timing()
+    if args.dump_outputs:  # the last call's records and hit count, every worker's (the filter above is empty: no records, 0 hits)
+        from ecloop_amd.capi import FOUND_DTYPE
+        got = out.view(FOUND_DTYPE)[: min(cnt.value, len(out))]
+        parts = sync.gather((int(cnt.value), [(rank, int(r["key_offset"]), [int(w) for w in r["h160"]], int(r["compressed"])) for r in got]))
+        recs = sorted(x for _, part in parts for x in part)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, len(recs), {"found_worker": [r[0] for r in recs], "found_scalar_index": [r[1] for r in recs],
+                                                        "found_hash160_u32": np.array([r[2] for r in recs], dtype=np.uint64).reshape(-1, 5),
+                                                        "found_compressed": [r[3] for r in recs]},
+                         extra={"hits_reported": [c for c, _ in parts]})
     if rank != 0:
         return
     hashes = len(addr)
@@ -573,9 +619,12 @@ def bench_add(args, sync, dev_index, emit, t_process):
         shards = sync.gather({"gpu": dev_index, "worker": rank, "first_key": hex(start), "keys_per_step": cnt, "lanes": ks.dev.geometry()[1],
                               "ms_per_step": round(mine_dt / steps * 1e3, 3), "kernel_ms_per_step": round(kernel_ms / steps, 3),
                               "found_per_step": len(ks.found), "planted_checked": len(mine)})
+        recs = None
+        if args.dump_outputs and mode == order[0]:  # the found list of the last timed step, every worker's
+            recs = [x for part in sync.gather([(r.pk, [int(w) for w in r.h160], int(r.label == "addr33")) for r in ks.found]) for x in part]
         return {"dt": dt, "value": total / dt / 1e6, "ms_per_step": dt / steps * 1e3, "kernel_ms": kernel_ms, "launches": launches,
                 "kkeys": kkeys, "setup_ms": setup_ms, "setups": setups, "planted_checked": len(mine), "found": len(ks.found),
-                "found_lines": sorted(r.line() for r in ks.found), "shards": shards}
+                "found_lines": sorted(r.line() for r in ks.found), "shards": shards, "records": recs}
 
     out = {order[0]: run_leg(order[0], args.steps, args.warmup)}
     for m in order[1:]:
@@ -617,6 +666,8 @@ def bench_add(args, sync, dev_index, emit, t_process):
         return
 
     main_leg = out[order[0]]
+    if args.dump_outputs:
+        dump_found_records(args.dump_outputs, main_leg["records"])
     ms_launch = main_leg["kernel_ms"] / max(main_leg["launches"], 1)
     keys_per_launch = main_leg["kkeys"] / max(main_leg["launches"], 1)
     per_gpu = legs[order[0]][1]
@@ -1210,6 +1261,9 @@ def main():
     ap.add_argument("--cfg4-steps", type=int, default=3)
     ap.add_argument("--small-jobs-log2", type=int, default=34, help="keys of the `small_jobs` leg (the reference's 2^21-key hand-out through the host program)")
     ap.add_argument("--cfg4-cli-log2", type=int, default=0, help="lines fed to the host program; 0 = 2^30 where /dev/shm and RAM allow (70 GB), else 2^28 / 2^26")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float64, at most 64 MB); "
+                         "--cmd mul runs against an empty filter, so its dump is a hit count of 0 and no records and cannot tell two builds apart")
     args = ap.parse_args()
     t_process = time.perf_counter()
 

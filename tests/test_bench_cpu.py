@@ -73,3 +73,34 @@ def test_more_gpus_than_visible_is_refused():
     pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "64", "--no-cpu"] + SMALL, stdout=subprocess.PIPE,
                         stderr=subprocess.PIPE, timeout=300, cwd=ROOT, env=ENV)
     assert pr.returncode != 0 and b"GPU(s) visible" in pr.stderr and not pr.stdout.strip()
+
+
+def _dumped(path):
+    import numpy as np
+    out = {f[:-4]: np.load(os.path.join(path, f)) for f in sorted(os.listdir(path)) if f.endswith(".npy")}
+    assert out and all(a.dtype in (np.float32, np.float64) for a in out.values()) and sum(a.nbytes for a in out.values()) <= 64 << 20
+    return out
+
+
+@pytest.mark.timeout(600)
+def test_dump_outputs_is_the_found_list_of_the_last_step(tmp_path):
+    """--dump-outputs DIR: the found records of the last timed step as float64 .npy files - identical from run to run, identical
+    whether one worker scans the range or two workers scan its shards, and the planted keys are among them"""
+    import numpy as np
+    from bench import RANGE_A, planted_offsets
+    runs = {}
+    for name, extra in (("one", []), ("again", []), ("two", ["--gpus", "2"])):
+        pr = subprocess.run([sys.executable, BENCH] + SMALL + ["--no-cpu", "--dump-outputs", str(tmp_path / name)] + extra,
+                            stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=580, cwd=ROOT, env=ENV)
+        r = last_json(pr)
+        runs[name] = _dumped(tmp_path / name)
+        assert int(runs[name]["found_count"][0]) == r["config"]["found_per_step"] == len(runs[name]["found_private_key_u32"])
+    for name in ("again", "two"):
+        assert runs[name].keys() == runs["one"].keys() and all(np.array_equal(runs[name][k], runs["one"][k]) for k in runs["one"])
+    d = runs["one"]
+    assert d["found_hash160_u32"].shape == (len(d["found_compressed"]), 5) and set(d["found_compressed"]) <= {0.0, 1.0}
+    keys = [sum(int(w) << (32 * (7 - i)) for i, w in enumerate(row)) for row in d["found_private_key_u32"]]
+    assert keys == sorted(keys) and {RANGE_A + o for o in planted_offsets(1 << 15)} <= set(keys)
+    import orc  # every dumped hash160 is the oracle's for its key and kind
+    for k, h, c in zip(keys, d["found_hash160_u32"], d["found_compressed"]):
+        assert [int(w) for w in h] == orc.hash160(*orc.point_of(k), compressed=bool(c)), hex(k)

@@ -115,7 +115,8 @@ def test_bench_two_ranks_strong_and_weak_legs(control):
     (needs two real GPUs: RCCL refuses two ranks on one device)"""
     env, two = two_gpu_env()
     if control == "nccl" and not two:
-        pytest.skip("one GPU on this box: RCCL cannot host two ranks on it")
+        import torch
+        pytest.skip(f"needs 2 GPUs (RCCL cannot host two ranks on one GPU), found {torch.cuda.device_count()}")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29517" if control == "gloo" else "29519", os.path.join(ROOT, "bench.py"), "--control", control] + SMALL2
     pr = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1200, cwd=ROOT, env=env)
@@ -129,9 +130,13 @@ def test_bench_gpus_8_shared(launcher):
     onto device g mod count), in both launcher shapes: eight device threads in one process, and eight ranks under torch.distributed.run
     with the rendezvous over gloo.  Eight contexts, eight filters and eight sets of walk buffers live on the device(s) at once (the lane
     count is cut back to what the free HBM allows, ecloop_hip.hip: default_lanes); every shard finds the planted keys of ITS part of the
-    range (bench.py aborts otherwise), and the line is timed over the slowest worker."""
+    range (bench.py aborts otherwise), and the line is timed over the slowest worker.  The rank shape runs only with eight GPUs: folded
+    onto fewer, its eight rank processes (plus the launcher and this one) hold one GPU open at once, more processes than a shared GPU
+    admits; the thread shape folds onto any GPU count."""
     import torch
     ngpu = torch.cuda.device_count()
+    if launcher == "ranks" and ngpu < 8:
+        pytest.skip(f"needs 8 GPUs, found {ngpu}: 8 rank processes folded onto {ngpu} GPU(s) exceed the processes a shared GPU may have open")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     if ngpu < 8:
         env["ECL_BENCH_SHARE_GPU"] = "1"
@@ -194,3 +199,23 @@ def test_bench_cmd_mul_line():
     r = last_json(pr.stdout)
     assert r["unit"] == "Mscalars/s" and r["config"]["window_bits"] == 26 and r["n_gpus"] == 1
     assert abs(r["value"] - (1 << 21) / (r["ms_per_step"] * 1e3)) / r["value"] < 1e-3 and r["value"] > 100
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the found records of the last timed step, float64, the planted keys among them"""
+    import numpy as np
+    from bench import RANGE_A, planted_offsets
+    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--keys-log2", "26", "--steps", "2", "--warmup", "0", "--no-cpu",
+                         "--dump-outputs", str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900, cwd=ROOT)
+    assert pr.returncode == 0, pr.stderr.decode(errors="replace")[-2000:]
+    r = last_json(pr.stdout)
+    assert r["steps"] == 2 and r["ms_per_step"] > 0
+    d = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in sorted(os.listdir(tmp_path)) if f.endswith(".npy")}
+    assert all(a.dtype == np.float64 for a in d.values()) and sum(a.nbytes for a in d.values()) <= 64 << 20
+    n = int(d["found_count"][0])
+    assert n == r["config"]["found_per_step"] and d["found_private_key_u32"].shape == (n, 8) and d["found_hash160_u32"].shape == (n, 5)
+    keys = [sum(int(w) << (32 * (7 - i)) for i, w in enumerate(row)) for row in d["found_private_key_u32"]]
+    assert keys == sorted(keys) and {RANGE_A + o for o in planted_offsets(1 << 26)} <= set(keys) and set(d["found_compressed"]) == {1.0}
+    import orc  # every dumped hash160 is the oracle's for its key
+    for k, h in zip(keys, d["found_hash160_u32"]):
+        assert [int(w) for w in h] == orc.hash160(*orc.point_of(k)), hex(k)
