@@ -196,24 +196,12 @@ static int mul_setup(ecl_hip* h, u32 n, u32 W) {
   }
   return ECL_OK;
 }
-// (the tuning hooks of this file read the environment of whoever loaded the library: every value is clamped to what the piece loop
-//  can run with - a zero or tiny thread count divided by zero / never advanced the loop, advisor r04)
-static u32 env_u32(const char* name, u32 dflt, u32 lo, u32 hi) {
-  const char* e = getenv(name);
-  if (!e || !*e) return dflt;
-  const long v = atol(e);
-  return v < (long)lo ? lo : (v > (long)hi ? hi : (u32)v);
-}
 // threads and scalars per thread of one k_mul_check launch over m scalars: as many scalars per thread (one shared inversion, at most
 // MUL_R) as still keep 65536 x ECL_MUL_WAVES threads in flight - what the chip holds at once; a few blocks more would wait for a whole
 // round - in whole workgroups, so that every row of scalars and every parking plane starts on a 1 KiB boundary
-static u32 mul_nt_target() {
-  static const u32 v = env_u32("ECL_HIP_MUL_NT", 65536u * ECL_MUL_WAVES, 1024u, 1u << 22) & ~255u;  // tuning hook (A/B runs)
-  return v;
-}
+static const u32 MUL_NT = 65536u * ECL_MUL_WAVES;
 static void mul_geometry(u32 m, u32* R_out, u32* nt_out) {
-  const u32 chains = mul_nt_target();
-  u32 R = (m + chains - 1) / chains;
+  u32 R = (m + MUL_NT - 1) / MUL_NT;
   R = R < 1 ? 1 : (R > MUL_R ? MUL_R : R);
   *R_out = R, *nt_out = ((m + R - 1) / R + 255u) / 256u * 256u;
 }
@@ -257,29 +245,26 @@ template <class CopyIn, class Prepare> static int mul_pieces(ecl_hip* h, u32 n, 
   // scalars per resident thread (12 for calls of 2^26 scalars and more), i.e. 196 608 x 1, 2, 4, 8, 10 (12) scalars at three waves per SIMD -
   // each copy is about as long as the kernel before it.  More scalars per thread share an inversion among more of them but park more sums
   // (144 bytes each: at 16 per thread a piece parks 453 MB, past the Infinity Cache) and lengthen the pipeline's fill and drain:
-  // tools/ab_mul_topr.sh (profiles/r04_mul_sched.txt, three waves per SIMD): 2^24-scalar calls 1252 / 1277 / 1252 / 1199 M scalars/s at
+  // profiles/r04_mul_sched.txt (three waves per SIMD): 2^24-scalar calls 1252 / 1277 / 1252 / 1199 M scalars/s at
   // 8 / 10 / 12 / 16 per thread, 2^25: 1313 / 1320 / 1319 / 1291, 2^26: 1354 / 1330 / 1346 / 1324, 2^27: 1368 / 1367 / 1378 / 1340.
-  // Round 4's earlier measurements at two waves per SIMD (tools/mul_kernel_times.sh, profiles/r04_mul_split.txt): 8 per thread 0.888 ms per
+  // Round 4's earlier measurements at two waves per SIMD (profiles/r04_mul_split.txt): 8 per thread 0.888 ms per
   // piece = 1.18 G scalars/s (22-bit table), 16 per thread 1.763 ms = 1.19 G/s, 32 per thread lose; doubling first pieces 1222-1230 / 1261-1270
   // on 2^24 / 2^26-scalar calls against 1214 / 1253 for a 2^18-scalar piece followed at once by full ones; two staging buffers 1208 / 1249.
   // (in units of one scalar per chain = what the chip holds at once: 2^17 scalars at two waves per SIMD: 2^18, then 2^20 / 2^21)
   // Round 5: the pieces alternate between TWO compute streams (each with its own parking space).  A piece's 768 workgroups are all
   // resident at once and do the same work, but they do not end together; on one stream the next piece's first workgroup waits for the
-  // last of this one.  On two streams the next piece's workgroups move into the slots as they fall free (ECL_HIP_MUL_STREAMS=1: one stream).
-  static const u32 first_R = env_u32("ECL_HIP_MUL_FIRST_R", 1u, 1u, MUL_R);   // tuning hooks (A/B runs)
-  static const u32 grow_pct = env_u32("ECL_HIP_MUL_GROW", 200u, 100u, 1600u);
-  static const u32 top_R = env_u32("ECL_HIP_MUL_TOP_R", 0u, 0u, MUL_R);
-  static const u32 nstreams = env_u32("ECL_HIP_MUL_STREAMS", 2u, 1u, 2u);
-  const u64 unit = (u64)mul_nt_target();
-  const u64 top_want = unit * (top_R ? top_R : (n >= (1u << 26) ? 12u : 10u));
+  // last of this one.  On two streams the next piece's workgroups move into the slots as they fall free (profiles/r05_mul_streams.txt:
+  // +3.6 % on 2^24-scalar calls, +7 % on 2^26).
+  const u64 unit = MUL_NT;
+  const u64 top_want = unit * (n >= (1u << 26) ? 12u : 10u);
   const u32 top = h->kbuf_cap < top_want ? h->kbuf_cap : (u32)top_want;
-  u32 lim = top < unit * first_R ? top : (u32)(unit * first_R);
+  u32 lim = top < unit ? top : (u32)unit;
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));
   HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));  // the second stream starts behind the counters' reset (and behind the call before)
   HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
-  for (u32 at = 0, c = 0, m = 0; at < n; at += m, ++c, lim = (u64)lim * grow_pct / 100 <= top ? (u32)((u64)lim * grow_pct / 100) & ~1023u : top) {
+  for (u32 at = 0, c = 0, m = 0; at < n; at += m, ++c, lim = (u64)lim * 2 <= top ? (u32)((u64)lim * 2) & ~1023u : top) {
     const u32 b = c % MUL_NBUF;
-    const int lane = (int)(c % nstreams);
+    const int lane = (int)(c % 2);
     hipStream_t st = lane ? h->stream2 : h->stream;
     m = n - at < lim ? n - at : lim;
     // no crumb at the end: what would be left after this piece is taken along if it is less than half a piece (a 2^24-scalar call used to
@@ -386,7 +371,7 @@ extern "C" int ecl_hip_mul_batch(ecl_hip* h, const uint64_t (*scalars)[4], uint3
 // into its staging buffer ahead of its window sums (details at the two lambdas below).  Until round 6 a call was ONE piece of at most
 // 2^22 lines on one stream and the host program made ~2 M-line calls: 0.79-0.87 G lines/s over 2^30 pass phrases; as pieces with the
 // hashing between the window sums of one stream and the whole text sent first, 2^24-line calls took 20.2 ms against 14.0 for 2^24
-// scalars; now 14.5-15.1 ms (tools/raw_api_probe.py), 1.09-1.16 G lines/s through the host program (tools/rawprobe3_r06.sh).
+// scalars; now 14.5-15.1 ms, 1.09-1.16 G lines/s through the host program (profiles/r06_mul_raw.txt).
 extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t text_bytes, const uint64_t* lines, uint32_t n, ecl_found* out,
                                      uint32_t cap, uint32_t* nout) {
   if (!h || (!text && text_bytes) || (!lines && n) || (!out && cap) || !nout || n > MUL_RAW_MAX || text_bytes > 0xFFFFFFF0u || cap > ECL_CAP_MAX) return ECL_E_ARG;

@@ -59,39 +59,20 @@ FE_FN void fe_st_words2(uint4* p, size_t stride, fe a) {  // normalises
   p[stride] = make_uint4(w[4], w[5], w[6], w[7]);
 }
 // raw limbs (any magnitude) in planes uint4, uint4, u32.  These are the prefix-product chain's accesses: every element is
-// written once and read once, a whole group later - a stream with no reuse in any cache.  ECL_CHAIN_NT (A/B builds) marks
-// the loads (bit 0) and / or the stores (bit 1) non-temporal (`nt`: the L1 is bypassed, the L2 / Infinity Cache line is
-// first in line for eviction), so that the stream does not displace the bloom filter's lines.
-#ifndef ECL_CHAIN_NT
-#define ECL_CHAIN_NT 0
-#endif
-#if defined(__HIPCC__)
-typedef u32 ecl_v4u __attribute__((ext_vector_type(4)));
-#endif
+// written once and read once, a whole group later - a stream with no reuse in any cache.  It does not hurt the filter's
+// cache residency either: non-temporal loads / stores measured 0.2 % / 1.8 % slower (profiles/r03_nt_ab.txt), so they stay plain.
 FE_FN fe fe_ld_limbs(const uint4* p4, size_t stride4, const u32* p1) {
   fe r;
-#if defined(__HIPCC__) && (ECL_CHAIN_NT & 1)
-  const ecl_v4u a = __builtin_nontemporal_load((const ecl_v4u*)p4), b = __builtin_nontemporal_load((const ecl_v4u*)(p4 + stride4));
-  r.n[8] = __builtin_nontemporal_load(p1);
-#else
   const uint4 a = p4[0], b = p4[stride4];
   r.n[8] = p1[0];
-#endif
   r.n[0] = a.x, r.n[1] = a.y, r.n[2] = a.z, r.n[3] = a.w;
   r.n[4] = b.x, r.n[5] = b.y, r.n[6] = b.z, r.n[7] = b.w;
   return r;
 }
 FE_FN void fe_st_limbs(uint4* p4, size_t stride4, u32* p1, const fe& a) {
-#if defined(__HIPCC__) && (ECL_CHAIN_NT & 2)
-  const ecl_v4u lo = {a.n[0], a.n[1], a.n[2], a.n[3]}, hi = {a.n[4], a.n[5], a.n[6], a.n[7]};
-  __builtin_nontemporal_store(lo, (ecl_v4u*)p4);
-  __builtin_nontemporal_store(hi, (ecl_v4u*)(p4 + stride4));
-  __builtin_nontemporal_store(a.n[8], p1);
-#else
   p4[0] = make_uint4(a.n[0], a.n[1], a.n[2], a.n[3]);
   p4[stride4] = make_uint4(a.n[4], a.n[5], a.n[6], a.n[7]);
   p1[0] = a.n[8];
-#endif
 }
 // Table entries are read through the constant address space: the address is wave-uniform (kernel argument + loop
 // counter), so these become scalar loads (s_load_dwordx*) into SGPRs and everything computed from them alone
@@ -137,9 +118,6 @@ struct cand_queue {
   u32 count;   // wave-uniform, < 64 between calls
 };
 
-#ifndef ECL_TWO_LEVEL_QUEUE
-#define ECL_TWO_LEVEL_QUEUE 1
-#endif
 struct cand_rec {
   u64 off;
   u32 h[5], tag;
@@ -190,7 +168,7 @@ struct cand_queues {
 __device__ __forceinline__ void cand_finish(const add_args& a, cand_queue& qb) {  // up to 64 records of ring B
   bool valid;
   const cand_rec r = cand_take(qb, valid);
-  const int from = ECL_TWO_LEVEL_QUEUE ? ECL_STAGE1_PROBES + (bloom_mid_two(a.bloom) ? 2 : 1) : ECL_STAGE1_PROBES;
+  const int from = bloom_mid_two(a.bloom) ? 3 : 2;  // probe 0 and the middle stage's one or two are done
   if (valid && bloom_probes_from(a.bloom, r.h, from))
     found_push(a, r.off, r.h, r.tag & 0xff, (r.tag >> 8) & 1);
 }
@@ -201,16 +179,10 @@ __device__ __forceinline__ void cand_mid(const add_args& a, cand_queues& q) {  /
   if (cand_append(q.b, pass, r.off, r.h, r.tag)) cand_finish(a, q.b);
 }
 __device__ __forceinline__ void cand_push(const add_args& a, cand_queues* q, bool pass, u64 off, const u32 h[5], u32 tag) {
-#if ECL_TWO_LEVEL_QUEUE
   if (cand_append(q->a, pass, off, h, tag)) cand_mid(a, *q);
-#else
-  if (cand_append(q->b, pass, off, h, tag)) cand_finish(a, q->b);
-#endif
 }
 __device__ __forceinline__ void cand_flush(const add_args& a, cand_queues& q) {  // end of the kernel: the remainders
-#if ECL_TWO_LEVEL_QUEUE
   cand_mid(a, q);  // A holds < 64
-#endif
   cand_finish(a, q.b);  // B holds < 128: at most two rounds
   cand_finish(a, q.b);
 }
@@ -277,22 +249,14 @@ __device__ __forceinline__ void check_point(const add_args& a, cand_queues* q, b
   }
 }
 
-// waves per SIMD the register allocator must leave room for (256-thread blocks: blocks per CU = this value)
-// 1: load the next prefix product one iteration ahead (10 more live VGPRs across the hash), 0: load at use
-#ifndef ECL_PREFETCH
-#define ECL_PREFETCH 0  /* measured early in the round: 0 -> 9.70, 1 -> 9.35 Gkeys/s; with the final kernel both give the same rate */
-#endif
-#ifndef ECL_ADD_WAVES
-#define ECL_ADD_WAVES 4  /* measured early in the round: 2 -> 8.38, 3 -> 8.99, 4 -> 7.97 Gkeys/s (addr33); final kernel: 2 is 2 % slower, 5 is 0.9 % and 6 is 4.8 % slower,
-                           4 is 0.2-0.5 % faster than 3 except for -a cu -endo (0.4 % slower: it stays at 3); -a u -endo spills inside its per-point loop at 4
-                           (17 scratch instructions per table point), so it takes 3 as well (round 6) */
-#endif
+// waves per SIMD the register allocator must leave room for (256-thread blocks: blocks per CU = this value).  Final kernel:
+// 2 is 2 % slower, 5 is 0.9 % and 6 is 4.8 % slower, 4 is 0.2-0.5 % faster than 3 except for -a cu -endo (0.4 % slower: it
+// stays at 3); -a u -endo spills inside its per-point loop at 4 (17 scratch instructions per table point), so it takes 3 as well
+#define ECL_ADD_WAVES 4
 // threads per workgroup of the add kernel.  Waves never talk to each other (no barrier, wave-private LDS rings), so the
 // only thing the size decides is the granularity at which the dispatcher hands out work: 64 / 128 / 256 measured equal
 // within 0.1 % in round 2 (tried and rejected); the lane count of a call is a multiple of 256
-#ifndef ECL_ADD_BLOCK
 #define ECL_ADD_BLOCK 256
-#endif
 template <bool A33, bool A65, bool ENDO>
 __global__ void __launch_bounds__(ECL_ADD_BLOCK, (A65 && ENDO) ? 3 : ECL_ADD_WAVES) k_add(const add_args a) {
   __shared__ u32 q_mem[ECL_ADD_BLOCK / 64][2][8 * ECL_Q_SLOTS];  // two candidate rings per wave
@@ -331,19 +295,12 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, (A65 && ENDO) ? 3 : ECL_ADD_WAV
     }
     // ---- phase 2: one inversion for the whole chain
     fe inv = fe_inv(acc);
-    // ---- phase 3: walk the chain backwards, emit C +- G_i
-#if ECL_PREFETCH
-    fe pre = fe_ld_limbs(scr4 + (size_t)(B - 1) * s4, plane, scr2 + (size_t)(B - 1) * plane);
-#endif
+    // ---- phase 3: walk the chain backwards, emit C +- G_i.  Each prefix product is loaded at use: loading it one
+    // iteration ahead measured 2.9 % slower (profiles/r03_pmc_filter_compare.txt section 4)
 #pragma unroll 1
     for (u32 k = B; k >= 1; --k) {
       const u32 i = k - 1;
-#if ECL_PREFETCH
-      fe nxt = pre;
-      if (k >= 2) nxt = fe_ld_limbs(scr4 + (size_t)(k - 2) * s4, plane, scr2 + (size_t)(k - 2) * plane);  // prefetch
-#else
       const fe pre = fe_ld_limbs(scr4 + (size_t)i * s4, plane, scr2 + (size_t)i * plane);
-#endif
       const fe gx = fe_ld_tab(tab + (size_t)i * ECL_TAB_STRIDE), gy = fe_ld_tab(tab + (size_t)i * ECL_TAB_STRIDE + FE_LIMBS);
       const fe dx = fe_sub(gx, X);
       const fe invk = fe_mul(inv, pre);  // 1 / (Gx_i - X)
@@ -381,9 +338,6 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, (A65 && ENDO) ? 3 : ECL_ADD_WAV
         }
         if (valid) check_point<A33, A65, ENDO>(a, &q, off < a.nkeys, px, py, off);
       }
-#if ECL_PREFETCH
-      pre = nxt;
-#endif
     }
     // ---- next centre: C + J with 1/(Jx - X) = inv (or the tangent if C == J)
     fe lam;

@@ -55,23 +55,14 @@ FE_FN u64 bloom_index(const u64 a[5], int probe) {
   const int j = probe % 5;
   return a[j] << S | a[(j + 1) % 5] >> S;
 }
-// ECL_PROBE_NT (A/B builds): the probe's 8-byte load marked non-temporal (bypasses the per-CU L1, where a random probe
-// into a filter of tens of MB never hits anyway)
-#ifndef ECL_PROBE_NT
-#define ECL_PROBE_NT 0
-#endif
-FE_FN u64 bloom_word(const bloom_t& b, u64 w) {
-#if defined(__HIPCC__) && ECL_PROBE_NT
-  return __builtin_nontemporal_load(b.bits + w);
-#else
-  return b.bits[w];
-#endif
-}
+// The probe is a plain load: marked non-temporal, a 54 MB filter lost its Infinity-Cache residency and ran 8 % slower
+// (profiles/r03_nt_ab.txt).
+FE_FN u64 bloom_word(const bloom_t& b, u64 w) { return b.bits[w]; }
 FE_FN bool bloom_bit(const bloom_t& b, u64 idx) { return (bloom_word(b, bloom_mod(b, idx >> 6)) >> (idx & 63)) & 1; }
 
 // lib/utils.c:308-326 in stages.  Stage 1: probe 0 alone (at the `.blf` design density 0.375 it rejects 62 % of the
-// hashes; ECL_STAGE1_PROBES = 2 would issue probes 0 and 1 together and reject 86 %).  Then the remaining probes, one
-// at a time with the reference's early-out (bloom_stage2); bloom_has() = both.  The add kernel parks the survivors of
+// hashes; probes 0 and 1 together would reject 86 %).  Then the remaining probes, one at a time with the reference's
+// early-out (bloom_stage2); bloom_has() = both.  The add kernel parks the survivors of
 // stage 1 in per-wave rings and finishes them 64 at a time in two steps - bloom_mid (one or two probes, no loop),
 // then bloom_probes_from (the early-out loop) - because inside the hot loop a few surviving lanes would keep the whole
 // wave iterating (add_kernel.h: cand_queues).  Measured on MI355X, addr33 over 2^32 keys, 1 vs 2 probes in stage 1:
@@ -84,20 +75,11 @@ FE_FN void bloom_words_of(u64 a[5], const u32 h[5]) {
   a[3] = (u64)h[1] << 32 | h[2];
   a[4] = (u64)h[3] << 32 | h[4];
 }
-#ifndef ECL_STAGE1_PROBES
-#define ECL_STAGE1_PROBES 1
-#endif
 // (Issuing this probe as four instructions of 16 active lanes for multi-GB filters was built and rejected in round 4: -1.3 %, HISTORY.md.)
 FE_FN bool bloom_stage1(const bloom_t& b, const u32 h[5]) {
   u64 a[5];
   bloom_words_of(a, h);
-  bool p0 = bloom_bit(b, bloom_index(a, 0));
-#if ECL_STAGE1_PROBES == 2
-  bool p1 = bloom_bit(b, bloom_index(a, 1));
-  return p0 && p1;
-#else
-  return p0;
-#endif
+  return bloom_bit(b, bloom_index(a, 0));
 }
 // probes [from, 20) one at a time with the reference's early-out
 FE_FN bool bloom_probes_from(const bloom_t& b, const u32 h[5], int from) {
@@ -115,24 +97,20 @@ FE_FN bool bloom_probes_from(const bloom_t& b, const u32 h[5], int from) {
   }
   return true;
 }
-FE_FN bool bloom_stage2(const bloom_t& b, const u32 h[5]) { return bloom_probes_from(b, h, ECL_STAGE1_PROBES); }
-// the middle stage of the add kernel's two-level candidate queue: probe ECL_STAGE1_PROBES, and with `two` also the
-// next one, issued together (independent loads, no loop)
+FE_FN bool bloom_stage2(const bloom_t& b, const u32 h[5]) { return bloom_probes_from(b, h, 1); }
+// the middle stage of the add kernel's two-level candidate queue: probe 1, and with `two` also probe 2, issued together
+// (independent loads, no loop)
 FE_FN bool bloom_mid(const bloom_t& b, const u32 h[5], bool two) {
   u64 a[5];
   bloom_words_of(a, h);
-  bool p = bloom_bit(b, bloom_index(a, ECL_STAGE1_PROBES));
-  if (two) p = bloom_bit(b, bloom_index(a, ECL_STAGE1_PROBES + 1)) && p;
+  bool p = bloom_bit(b, bloom_index(a, 1));
+  if (two) p = bloom_bit(b, bloom_index(a, 2)) && p;
   return p;
 }
 // Filters that stay in the 256 MB Infinity Cache take two probes in the middle stage (fewer instructions: 5 % of the
 // candidates reach the loop instead of 14 %); bigger ones take one (every probe is a random HBM sector + TLB miss, and
 // one-at-a-time touches 1.59 sectors per hash instead of 1.79).
-#ifdef ECL_MID_TWO_FORCE /* A/B builds: 0 / 1 fixes the choice whatever the filter size */
-FE_FN bool bloom_mid_two(const bloom_t&) { return ECL_MID_TWO_FORCE != 0; }
-#else
 FE_FN bool bloom_mid_two(const bloom_t& b) { return b.nwords < (1ull << 24); }
-#endif
 FE_FN bool bloom_has(const bloom_t& b, const u32 h[5]) { return bloom_stage1(b, h) && bloom_stage2(b, h); }
 #if defined(__HIPCC__)
 // lib/utils.c:290-306 (blf_add) for one hash: 20 atomic ORs

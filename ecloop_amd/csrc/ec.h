@@ -86,24 +86,9 @@ struct xyzz {
 // neg != 0: P - Q, i.e. (qx, -qy) is added: the sign goes on s2 = qy ZZZ (one select per limb, inside the sum that is normalised anyway).
 // The ten field operations of an addition come in five independent pairs; each pair runs as one interleaved instruction stream
 // (fe256.h: fe_mul2 / fe_sqr2 - four accumulator chains instead of two, no wait states between dependent multiply-adds), which is worth
-// 5 % of a multiplication at the two waves per SIMD the `mul` kernel runs at (csrc/tools/femul_bench.hip; ECL_MUL_PAIRS=0: one by one).
-#ifndef ECL_MUL_PAIRS
-#define ECL_MUL_PAIRS 1
-#endif
-FE_FN void fe_mul_pair(fe& r1, fe& r2, const fe& a1, const fe& b1, const fe& a2, const fe& b2) {
-#if ECL_MUL_PAIRS
-  fe_mul2(r1, r2, a1, b1, a2, b2);
-#else
-  r1 = fe_mul(a1, b1), r2 = fe_mul(a2, b2);
-#endif
-}
-FE_FN void fe_sqr_pair(fe& r1, fe& r2, const fe& a1, const fe& a2) {
-#if ECL_MUL_PAIRS
-  fe_sqr2(r1, r2, a1, a2);
-#else
-  r1 = fe_sqr(a1), r2 = fe_sqr(a2);
-#endif
-}
+// 5 % of a multiplication at the two waves per SIMD the `mul` kernel runs at (csrc/tools/femul_bench.hip, profiles/r04_mul_pairs.txt).
+FE_FN void fe_mul_pair(fe& r1, fe& r2, const fe& a1, const fe& b1, const fe& a2, const fe& b2) { fe_mul2(r1, r2, a1, b1, a2, b2); }
+FE_FN void fe_sqr_pair(fe& r1, fe& r2, const fe& a1, const fe& a2) { fe_sqr2(r1, r2, a1, a2); }
 FE_FN xyzz xyzz_madd_lazy(const xyzz& p, const fe& qx, const fe& qy, u32 neg = 0) {
   fe u2, s2p;
   fe_mul_pair(u2, s2p, qx, p.ZZ, qy, p.ZZZ);

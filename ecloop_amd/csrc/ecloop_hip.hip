@@ -213,7 +213,7 @@ int ecl_hip_set_bloom(ecl_hip* h, const uint64_t* bits, uint64_t nwords) {
 
 // Page-locked host memory comes from the runtime (hipHostMalloc, next to the GPU's NUMA node), never from registering the caller's
 // own memory in place: hipHostRegister / hipHostUnregister cycles on memory that the host allocator recycles end in GPU memory access
-// faults inside the ROCm runtime (rounds 2 and 5; tools/repro_pin_fault.py, profiles/r05_pin_fault.txt), which is why the entry points
+// faults inside the ROCm runtime (rounds 2 and 5; profiles/r05_pin_fault.txt), which is why the entry points
 // that used to do that are gone.  Pageable buffers are copied by the runtime (filter) or staged through the library's own pinned
 // buffers (scalar arrays of ecl_hip_mul_batch).
 #define ECL_PIN_MIN_BYTES ((size_t)1 << 20)  /* ecl_hip_mul_batch: batches below this are staged whatever their memory is */

@@ -59,7 +59,7 @@ FE_FN u32 fe_opaque(u32 c) { return c; }
 // bits the AMDGPU backend first treats the multiply as a 24-bit one (which lets it drop the masks) and then
 // selects v_mad_u64_u32 on the unmasked registers: the top limb of a field element squared as (c & 0xFFFFFF)^2
 // came out as (low32(c))^2 whenever one multiplication fed another directly.  Reproduced and localised with an
-// instruction-level emulation of the generated code; tests: diag ops 6-8 in tests/test_gpu_primitives.py.
+// instruction-level emulation of the generated code (tools/gcn_valu_emu.py); tests: diag ops 6-8 in tests/test_gpu_primitives.py.
 // FE_HIDE24 makes the masked value opaque so the product is an ordinary 32 x 32 multiply of the masked register.
 #if defined(__HIP_DEVICE_COMPILE__)
 #define FE_HIDE24(x) asm("" : "+v"(x))
@@ -440,11 +440,7 @@ struct ds_mat {
 // (q, r) with g, doubled instead of halved.  Ten steps at a time both entries of a row share one register (u + v 2^16: every
 // operation of a step is linear, and |u| + |v| <= 2^10 leaves the fields apart), the three 10-step matrices are multiplied out in
 // 32 bits: 17 instructions per step + 42 per round instead of 24 per step.
-#ifndef ECL_DS_PACKED
-#define ECL_DS_PACKED 1 /* A/B: 0 = the four matrix entries in registers of their own, 30 steps in one go */
-#endif
 FE_FN i32 ds_divsteps30(i32 zeta, u32 f, u32 g, ds_mat& t) {
-#if ECL_DS_PACKED
   i32 mu = 1, mv = 0, mq = 0, mr = 1;  // matrix of the steps done so far in this round
 #pragma unroll
   for (int part = 0; part < 3; ++part) {
@@ -470,22 +466,6 @@ FE_FN i32 ds_divsteps30(i32 zeta, u32 f, u32 g, ds_mat& t) {
   }
   t.u = mu, t.v = mv, t.q = mq, t.r = mr;
   return zeta;
-#else
-  u32 u = 1, v = 0, q = 0, r = 1;
-#pragma unroll
-  for (int i = 0; i < 30; ++i) {
-    u32 c1 = (u32)(zeta >> 31);    // all ones: zeta < 0
-    const u32 c2 = 0u - (g & 1u);  // all ones: g odd
-    const u32 x = (f ^ c1) - c1, y = (u ^ c1) - c1, z = (v ^ c1) - c1;  // -f, -u, -v where zeta < 0
-    g += x & c2, q += y & c2, r += z & c2;
-    c1 &= c2;                      // swap
-    zeta = (i32)((u32)zeta ^ c1) - 1;
-    f += g & c1, u += q & c1, v += r & c1;
-    g >>= 1, u <<= 1, v <<= 1;
-  }
-  t.u = (i32)u, t.v = (i32)v, t.q = (i32)q, t.r = (i32)r;
-  return zeta;
-#endif
 }
 // (f, g) <- t (f, g) / 2^30 (exact)
 FE_FN void ds_update_fg(ds30& f, ds30& g, const ds_mat& t) {
@@ -567,16 +547,9 @@ __host__ __device__ __noinline__ inline fe fe_inv_divsteps(fe a) {
   FE_HIDE24(r.n[8]);
   return r;
 }
-#ifndef ECL_FE_INV_DIVSTEPS
-#define ECL_FE_INV_DIVSTEPS 1 /* A/B: 0 = the addition chain everywhere */
-#endif
-FE_FN fe fe_inv(const fe& a) {
-#if ECL_FE_INV_DIVSTEPS
-  return fe_inv_divsteps(a);
-#else
-  return fe_inv_fermat(a);
-#endif
-}
+// the inversion everywhere: divsteps run 1.9-2.1x the rate of the addition chain (fe_inv_fermat) on gfx950, and the mul
+// kernel is 6-7 % faster with them (profiles/r04_inv_ab.txt)
+FE_FN fe fe_inv(const fe& a) { return fe_inv_divsteps(a); }
 
 // secp256k1 constants as canonical little-endian u32 words
 #define FE_BETA1_W                                                                                              \

@@ -17,10 +17,7 @@ H_FN u32 bswap32(u32 x) { return __builtin_bswap32(x); }
 // bitfield select: (m & a) | (~m & b)  -> v_bfi_b32
 H_FN u32 bsel(u32 m, u32 a, u32 b) { return (a & m) | (b & ~m); }
 
-// three-input xor: one v_bitop3_b32 on the device (the compiler prefers two v_xor_b32; ECL_XOR3_BITOP3=0 keeps that)
-#ifndef ECL_XOR3_BITOP3
-#define ECL_XOR3_BITOP3 1
-#endif
+// three-input xor: one v_bitop3_b32 on the device (the compiler would emit two v_xor_b32)
 // Boolean functions of three words as ONE v_bitop3_b32 (truth table = f(0xF0, 0xCC, 0xAA)).  Written with the
 // builtin because the compiler otherwise splits Ch / Maj / select into disjoint AND terms that it folds into the
 // additions ((e&f) + (~e&g)), which costs more instructions than it saves.
@@ -28,7 +25,7 @@ H_FN u32 bsel(u32 m, u32 a, u32 b) { return (a & m) | (b & ~m); }
 #define BITSEL_C(m, a, b) (((a) & (m)) | ((b) & ~(m)))
 #define MAJ3_C(a, b, c) (((a) & (b)) | ((c) & ((a) | (b))))
 #define ORN_XOR_C(x, y, z) (((x) | ~(y)) ^ (z))
-#if defined(__HIP_DEVICE_COMPILE__) && ECL_XOR3_BITOP3
+#if defined(__HIP_DEVICE_COMPILE__)
 // The builtin is opaque to constant folding: with all-constant inputs (IV state in the first rounds, the constant
 // words of the padded message) it would be evaluated at run time - hoisted out of the loops, but then its result
 // occupies a VGPR for the whole kernel.  Constant inputs take the plain C form, which folds to a literal.

@@ -10,9 +10,7 @@
 // <= 19 mixed additions of table points per scalar (64-byte gathers, the 19.9 MB table lives in L2 / Infinity Cache).
 // The scalar 0 (mod n) yields no point (the reference emits garbage).
 #define GT_W 14u
-#ifndef MUL_NBUF
 #define MUL_NBUF 4  /* staging buffers of ecl_hip_mul_batch: the copy engine runs up to MUL_NBUF - 1 pieces ahead of the kernel */
-#endif
 #define MUL_CHUNK (1u << 22)  /* scalars per staged chunk of ecl_hip_mul_batch (128 MB): 2^18 threads x MUL_R */
 #define MUL_RAW_MAX (1u << 26) /* lines per ecl_hip_mul_batch_raw call (a 512 MB line table on the device) */
 #define GT_WINDOWS 19u
@@ -187,12 +185,10 @@ __global__ void k_gather_slots(const u32* __restrict__ table, const u64* __restr
 // the reference's 2048-key job): 11 multiplications per non-zero digit + 17 + 7 per scalar instead of 209 + 270 + 3.
 __device__ __forceinline__ xyzz wtab_sum_fast(const u32* __restrict__ kw, const wtab t, u32& bad);
 #define MUL_R 32u  /* at most (one bit of `infmask` each); short pieces take fewer per thread so that the chip still fills (ecl_hip_mul_batch) */
-#ifndef ECL_MUL_WAVES
 #define ECL_MUL_WAVES 3  /* waves per SIMD the register allocator leaves room for (256-thread blocks: blocks per CU); the host side launches
                             65536 x ECL_MUL_WAVES threads per piece.  With the low-register window sum the kernel fits 168 VGPRs (one spill): three
                             waves hide the wait states between dependent multiply-adds better than two (profiles/r04_mul_fastsum.txt: 2^26-scalar
                             calls 1391 against 1370 M scalars/s, 2^24 equal); the sum with the scalar in registers needed 67 spills there */
-#endif
 template <bool A33, bool A65>
 __global__ void __launch_bounds__(256, ECL_MUL_WAVES) k_mul_check(const u32* __restrict__ k, u32 n, u32 base, const wtab gtab, add_args a,
                                                    u32* __restrict__ tmp, u32 nt, u32 R) {
@@ -274,21 +270,15 @@ __device__ __forceinline__ u32 wtab_digit_mem(const u32* __restrict__ kw, const 
   __builtin_memcpy(&v, kw + word, 8);  // an 8-byte load from a 4-byte aligned address (odd `word`): one global_load_dwordx2 on gfx950
   return (u32)(v >> sh) & t.per;  // raw digit
 }
-#ifndef ECL_MUL_HOT_GATHERS
-#define ECL_MUL_HOT_GATHERS 0  /* MEASUREMENT BUILD ONLY (wrong points): every gather lands in the first 256 slots of its row, i.e. in cache - the same
-                                  instructions and loads without the table's HBM traffic (tools/ab_r05b.sh, tools/ab_r05c.sh) */
-#endif
-#if ECL_MUL_HOT_GATHERS && !defined(ECL_MEASUREMENT_BUILD_WRONG_RESULTS)
-#error "ECL_MUL_HOT_GATHERS computes wrong points: measurement builds only, and they say so with -DECL_MEASUREMENT_BUILD_WRONG_RESULTS"
-#endif
 // How the table points reach the additions, and what was measured about it in round 5 (profiles/r05_mul_lds_gather.txt, commit be22f1e):
 // the point of window w + 1 is requested in the middle of window w's addition and held in 16 VGPRs.  Three deeper forms were built - the
 // point staged in LDS by global_load_lds_dwordx4 (no register held), the wave's scalars staged in LDS a round ahead (digits by ds_read
 // instead of a global load four instructions before its use), the first two points of the next scalar requested during the last addition
 // of this one - and all ran within 0.5 % of this form (1272-1279 M scalars/s on 2^24-scalar calls): at three waves per SIMD another wave
-// issues while one waits.  The build with cache-resident gathers is 11-13 % faster, but through the CLOCK (2.26 against 2.06 GHz; wait
-// share and clocks per instruction unchanged): the kernel runs against the board's power limit, and 0.9 TB/s of random 64-byte HBM
-// reads take watts from the shader clock.  Fewer HBM bytes per scalar would help; hiding their latency does not.
+// issues while one waits.  A measurement build whose gathers all landed in cache (same instructions, wrong points) was 11-13 % faster,
+// but through the CLOCK (2.26 against 2.06 GHz; wait share and clocks per instruction unchanged): the kernel runs against the board's
+// power limit, and 0.9 TB/s of random 64-byte HBM reads take watts from the shader clock.  Fewer HBM bytes per scalar would help;
+// hiding their latency does not.
 __device__ __forceinline__ xyzz wtab_sum_fast(const u32* __restrict__ kw, const wtab t, u32& bad) {
   // Windows that hold a zero digit in EVERY lane of the wave are not walked at all: the loop ends at the highest window in which some
   // lane has something to add (round 5).  That is what small scalars need - puzzle-range or sequential keys: all of their high windows,
@@ -311,7 +301,6 @@ __device__ __forceinline__ xyzz wtab_sum_fast(const u32* __restrict__ kw, const 
   u32 dn = nw > 2u ? wtab_recode(t, 2, wtab_digit_mem(kw, t, 2), carry, sn) : 1u;
   bad = (d0 == 0u) | (d1 == 0u);
   d0 = d0 ? d0 : 1u, d1 = d1 ? d1 : 1u;
-  if (ECL_MUL_HOT_GATHERS) d0 = (d0 & 255u) + 1u, d1 = (d1 & 255u) + 1u;
   xyzz acc;
   {
     const uint4* e0 = (const uint4*)(t.p + ((size_t)d0 - 1) * 16);
@@ -325,7 +314,6 @@ __device__ __forceinline__ xyzz wtab_sum_fast(const u32* __restrict__ kw, const 
   if (nw > 2u) {
     bad |= dn == 0u;
     dn = dn ? dn : 1u;
-    if (ECL_MUL_HOT_GATHERS) dn = (dn & 255u) + 1u;
     const uint4* e = (const uint4*)(t.p + ((size_t)2 * t.stride + dn - 1) * 16);
     n0 = e[0], n1 = e[1], n2 = e[2], n3 = e[3];
   }
@@ -341,7 +329,6 @@ __device__ __forceinline__ xyzz wtab_sum_fast(const u32* __restrict__ kw, const 
     if (more) {
       bad |= dn == 0u;
       dn = dn ? dn : 1u;
-      if (ECL_MUL_HOT_GATHERS) dn = (dn & 255u) + 1u;
       const uint4* e = (const uint4*)(t.p + ((size_t)(w + 1u) * t.stride + dn - 1) * 16);
       n0 = e[0], n1 = e[1], n2 = e[2], n3 = e[3];
     }

@@ -176,7 +176,7 @@ int ecl_hip_bloom_insert_count(ecl_hip *h, const uint32_t (*h160)[5], uint64_t n
    GPU's copy engine directly (57 GB/s), pageable ones go through a staging copy (18 GB/s: 0.57 instead of 1.3 G scalars/s for `mul`).
    The runtime places the pages next to the GPU, which matters on a two-socket host: from the far socket the copy runs at about half
    the rate (30 against 57 GB/s measured).  (There is no call that page-locks the caller's own memory in place: register / unregister
-   cycles on memory the host allocator recycles fault inside the ROCm runtime - tools/repro_pin_fault.py, profiles/r05_pin_fault.txt.) */
+   cycles on memory the host allocator recycles fault inside the ROCm runtime - profiles/r05_pin_fault.txt.) */
 void *ecl_hip_alloc_host(size_t bytes);
 void ecl_hip_free_host(void *p);
 

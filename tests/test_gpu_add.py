@@ -583,7 +583,7 @@ def test_mul_both_address_forms_on_the_long_table_against_the_oracle():
 
 def test_small_pageable_and_page_locked_scalar_arrays():
     """ecl_hip_mul_batch from small pageable arrays that the host allocator recycles between calls (the pattern that met GPU memory
-    faults in round 2 when such arrays were page-locked in place - the library no longer offers that, tools/repro_pin_fault.py), from a
+    faults in round 2 when such arrays were page-locked in place - the library no longer offers that, profiles/r05_pin_fault.txt), from a
     large pageable array (staged) and from ecl_hip_alloc_host memory (read by DMA): same records whichever way the scalars travel."""
     import ctypes as C
     from ecloop_amd import Device, capi
