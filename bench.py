@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — `add` (addr33) key-search throughput on MI355X: BASELINE.json's metric on its configs[1].
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full]
         N>1 under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`: one rank per GPU;
         N>1 WITHOUT a launcher: N device threads in this one process, one GPU each (same shards, same line).
         Fewer visible GPUs than N is an error in both shapes.
@@ -10,19 +10,26 @@ One step = one pass of the hot path over ONE contiguous range of 2^32 private ke
 `.blf`-format bloom filter resident in HBM: batch affine additions, SHA-256 -> RIPEMD-160 of every compressed public
 key, bloom probe, hits gathered on the host.  With N GPUs the range is cut into N contiguous shards, one per rank
 (north_star: "a 2^32 contiguous range at 1, 2, 4 and 8 MI355X") - strong scaling, no collective on the data path, only
-the timing rendezvous (barrier + MAX over workers; gloo by default, `--control nccl` for RCCL).  `weak_scaling` in the same line is a second, separately timed leg where every rank scans its own
-2^32 keys (`--scaling weak` makes that leg the headline instead).  Inputs are synthetic and already in HBM when the
-timed region starts: the filter holds 10^7 seeded pseudo-random hash160 values plus 16 planted keys per 2^32-key range
-(so the found list is not empty and is checked: a missing planted key or a found list that differs from the reference
-binary's on the CPU sample aborts the run).
+the timing rendezvous (barrier + MAX over workers; gloo by default, `--control nccl` for RCCL).  `--scaling weak` makes
+every rank scan its own 2^32 keys instead.  Inputs are synthetic and already in HBM when the timed region starts: the
+filter holds 10^7 seeded pseudo-random hash160 values plus 16 planted keys per 2^32-key range (so the found list is not
+empty and is checked: a missing planted key aborts the run).
 
 Prints ONE JSON line (rank 0).  `roofline`: the kernel is integer-VALU issue bound; `achieved` = VALU lane-operations
 per key (rocprofv3 SQ_INSTS_VALU of THIS build, loaded from the tracked profile named in the line) x keys per launch
 / the kernel's HIP-event time measured in this process.  Nothing in it is a constant typed into this file: every field
 is measured here or loaded from profiles/<tag>_roofline.json (tools/collect_profiles.sh), and `profile.matches_build`
-says whether that profile was taken on the sources being run.  `cpu_baseline` is the unmodified reference binary
-(oracle/_ref, built from /root/reference by oracle/Makefile) timed on this host's cores over a bounded sample of the
-same range and filter, or the oracle port if the binary is not there.
+says whether that profile was taken on the sources being run.
+
+A plain run does what the headline needs and nothing more: set-up, warm-up, the timed steps, --dump-outputs, the line.
+`--full` adds, after the headline's steps and in the same line, everything else the benchmark measures and checks:
+    N>1   `weak_scaling` (`strong_scaling` under --scaling weak): the other scaling mode as a second, separately timed leg
+    N=1   `shard_steps`: the per-GPU shards of the range at N = 2, 4, 8 as timed steps on this GPU
+          `cpu_baseline`: the unmodified reference binary (oracle/_ref, built from the reference's sources by oracle/Makefile)
+          timed on this host's cores over a bounded sample of the same range and filter, or the oracle port if the binary
+          is not there; a GPU found list that differs from its list on that sample aborts the run
+          `secondary`: BASELINE.json's configs[2], [3], [4], each checked against the oracle on a sample
+    (--no-second-leg leaves out the second leg, --no-cpu `cpu_baseline`, --no-secondary `shard_steps` and `secondary`)
 
     python bench.py --cmd mul      non-headline: the `mul` path (2^24 seeded scalars per step through ecl_hip_mul_batch)
     python bench.py ... --dump-outputs DIR
@@ -568,10 +575,12 @@ def bench_add(args, sync, dev_index, emit, t_process):
     # per-worker scan of each leg: strong = shard `rank` of the one range, weak = the worker's own range
     legs = {"strong": (RANGE_A + shard(nkeys, rank, world)[0], shard(nkeys, rank, world)[1]),
             "weak": (RANGE_A + rank * nkeys, nkeys)}
-    order = [args.scaling] + ([m for m in ("strong", "weak") if m != args.scaling] if world > 1 and not args.no_second_leg else [])
+    order = [args.scaling] + ([m for m in ("strong", "weak") if m != args.scaling] if args.full and world > 1 and not args.no_second_leg else [])
 
     # --- inputs -> HBM (untimed)
     headline = args.addr == "c" and not args.endo and args.filter_n == FILTER_N
+    with_cpu = args.full and world == 1 and not args.no_cpu and headline
+    with_secondary = args.full and world == 1 and headline and not args.no_secondary and args.keys_log2 == 32
     t0 = time.perf_counter()
     ks = KeySearch(Filter(np.zeros(1, dtype=np.uint64)), device=dev_index, a33="c" in args.addr, a65="u" in args.addr,
                    endo=args.endo, verify=True,
@@ -579,7 +588,7 @@ def bench_add(args, sync, dev_index, emit, t_process):
     setup = dict(SETUP, context_open_and_selftest_s=round(time.perf_counter() - t0, 2))  # HIP init, streams, the device code's self-test
     t0 = time.perf_counter()
     size, planted_offs, _ = build_filter(ks.dev, RANGE_A, nkeys, args.filter_n, ranges=world, cuda_index=dev_index)
-    words = ks.dev.get_bloom(size) if (rank == 0 and world == 1 and not args.no_cpu and headline) else None
+    words = ks.dev.get_bloom(size) if (rank == 0 and with_cpu) else None
     setup["filter_build_s"] = round(time.perf_counter() - t0, 2)
     t0 = time.perf_counter()
     for m in order:  # walk buffers allocated with the inputs, outside the timed region
@@ -633,7 +642,7 @@ def bench_add(args, sync, dev_index, emit, t_process):
     # re-positions the walk - set-up kernels, host work and hit handling included, as a rank of an N-GPU run pays them), so that the
     # projected strong-scaling efficiency is a measured number of this run, not prose.  A projection: N identical GPUs, no host contention.
     shard_steps = None
-    if world == 1 and headline and args.keys_log2 == 32 and not args.no_secondary and order[0] == "strong":
+    if with_secondary and order[0] == "strong":
         shard_steps = []
         for n in (2, 4, 8):
             first, cnt = shard(nkeys, n - 1, n)
@@ -703,7 +712,7 @@ def bench_add(args, sync, dev_index, emit, t_process):
         res["config"]["hashes_per_key"] = hashes_per_key
         res["roofline"] = {"bound": "valu-int32", "note": "non-headline variant: no PMC profile of this kernel is loaded", "ms_per_launch": round(ms_launch, 3),
                            "keys_per_launch": int(keys_per_launch), "hash160_per_s_G": round(main_leg["value"] * hashes_per_key / 1e3, 2)}
-    if world == 1 and not args.no_cpu and headline:
+    if with_cpu:
         cb, (log2n, cpu_lines) = cpu_baseline(words)
         res["cpu_baseline"] = cb
         if log2n <= args.keys_log2:
@@ -712,14 +721,14 @@ def bench_add(args, sync, dev_index, emit, t_process):
             if gpu_lines != cpu_lines:
                 emit(res)
                 raise SystemExit(f"[bench] FOUND LIST MISMATCH on the CPU sample: gpu {len(gpu_lines)} lines, cpu {len(cpu_lines)} lines")
-    if world == 1 and headline and not args.no_secondary and args.keys_log2 == 32:
+    if with_secondary:
         res["secondary"] = secondary_legs(args, dev_index)  # configs[2], [3], [4] in the same run; a failed check aborts
     emit(res)
 
 
 
 # ----------------------------------------------------------------------------------------------- secondary legs (N = 1)
-# BASELINE.json's other configs, measured in the same run as the headline and reported under `secondary` (the headline
+# BASELINE.json's other configs, measured by a --full run after the headline and reported under `secondary` (the headline
 # fields are untouched): cfg2 = configs[2] on one GPU (add -a cu -endo, ~6 GB .blf), cfg3 = configs[3] (rnd -d 128:32
 # windows through the C host program), cfg4 = configs[4] (mul: scalars through ecl_hip_mul_batch and hex lines through
 # the host program's stdin).  Each leg checks what it found: planted keys must be there, and the found list over a
@@ -1243,8 +1252,10 @@ def main():
     ap.add_argument("--launch-log2", type=int, default=32, help="largest number of keys given to one device call")
     ap.add_argument("--half-group", type=int, default=0)
     ap.add_argument("--lanes", type=int, default=0)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-second-leg", action="store_true", help="N>1: skip the other scaling mode's leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the other scaling mode's leg (N>1), or shard_steps, cpu_baseline and the secondary legs (N=1)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
+    ap.add_argument("--no-second-leg", action="store_true", help="--full, N>1: skip the other scaling mode's leg")
     ap.add_argument("--addr", default="c", choices=["c", "u", "cu"], help="non-headline variants: -a u / -a cu")
     ap.add_argument("--endo", action="store_true", help="non-headline variant: -endo (6 images per key)")
     ap.add_argument("--filter-n", type=int, default=FILTER_N, help="bloom entries (default 10^7 = 54 MB; 1.1e9 = 5.9 GB)")
@@ -1252,7 +1263,7 @@ def main():
     ap.add_argument("--mul-log2", type=int, default=24)
     ap.add_argument("--mul-window", type=int, default=26, help="mul: window width of the table (0 = the library's automatic choice)")
     ap.add_argument("--pageable", action="store_true", help="mul: scalars in pageable host memory (staged through pinned buffers by the library)")
-    ap.add_argument("--no-secondary", action="store_true", help="N=1 headline run: skip the `secondary` legs (configs[2], [3], [4])")
+    ap.add_argument("--no-secondary", action="store_true", help="--full, N=1 headline run: skip shard_steps and the `secondary` legs (configs[2], [3], [4])")
     ap.add_argument("--cfg2-keys-log2", type=int, default=30)
     ap.add_argument("--cfg2-steps", type=int, default=2)
     ap.add_argument("--cfg2-filter-n", type=int, default=1_100_000_000, help="entries of the cfg2 filter (1.1e9 = 5.9 GB, configs[2]'s '~6 GB bloom')")

@@ -38,7 +38,7 @@ def check_two_gpu_line(r, launcher):
 
 @pytest.mark.timeout(600)
 def test_gpus_2_without_a_launcher_runs_two_device_threads():
-    pr = subprocess.run([sys.executable, BENCH, "--gpus", "2"] + SMALL, stdout=subprocess.PIPE,
+    pr = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--full"] + SMALL, stdout=subprocess.PIPE,
                         stderr=subprocess.PIPE, timeout=580, cwd=ROOT, env=ENV)
     check_two_gpu_line(last_json(pr), "in-process device threads")
 
@@ -51,7 +51,7 @@ def test_gpus_2_under_torch_distributed_run():
     port = s.getsockname()[1]
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), BENCH, "--gpus", "2"] + SMALL
+           "--master-port", str(port), BENCH, "--gpus", "2", "--full"] + SMALL
     pr = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=580, cwd=ROOT, env=ENV)
     check_two_gpu_line(last_json(pr), "torch.distributed.run")
 
@@ -66,6 +66,18 @@ def test_single_worker_line_and_contradicting_flags():
     pr = subprocess.run([sys.executable, BENCH, "--gpus", "4"] + SMALL, stdout=subprocess.PIPE,
                         stderr=subprocess.PIPE, timeout=120, cwd=ROOT, env=env)
     assert pr.returncode != 0 and b"contradicts" in pr.stderr
+
+
+@pytest.mark.timeout(600)
+def test_plain_run_is_the_headline_alone():
+    """without --full the line carries the headline and nothing that needs runs of its own: no cpu_baseline at N=1 (--no-cpu not
+    given), no second scaling leg at N=2"""
+    for extra in ([], ["--gpus", "2"]):
+        pr = subprocess.run([sys.executable, BENCH] + SMALL + extra, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=580, cwd=ROOT, env=ENV)
+        r = last_json(pr)
+        assert r["n_gpus"] == (2 if extra else 1) and r["steps"] == 2 and r["warmup"] == 1 and r["config"]["planted_checked"] == 16
+        for k in ("cpu_baseline", "weak_scaling", "shard_steps", "secondary"):
+            assert k not in r, k
 
 
 def test_more_gpus_than_visible_is_refused():

@@ -39,9 +39,9 @@ def test_bench_line_single_gpu_small():
 
 
 def test_bench_secondary_legs_at_reduced_size():
-    """the `secondary` object of the default N = 1 run (BASELINE configs[2], [3], [4] beside the headline), at sizes that finish in a
+    """the `secondary` object of the `--full` N = 1 run (BASELINE configs[2], [3], [4] beside the headline), at sizes that finish in a
     minute: every leg present, checked against the oracle on its sample (a mismatch makes bench.py exit non-zero), rates consistent"""
-    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--no-cpu", "--cfg2-keys-log2", "27",
+    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "0", "--no-cpu", "--cfg2-keys-log2", "27",
                          "--cfg2-steps", "1", "--cfg2-filter-n", "60000000", "--cfg3-windows", "1", "--cfg4-log2", "22", "--cfg4-steps", "2",
                          "--cfg4-cli-log2", "22", "--small-jobs-log2", "30"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500, cwd=ROOT)
     assert pr.returncode == 0, pr.stderr.decode(errors="replace")[-3000:]
@@ -97,11 +97,11 @@ def two_gpu_env():
     return env, two
 
 
-SMALL2 = ["--gpus", "2", "--keys-log2", "27", "--steps", "2", "--warmup", "1"]
+SMALL2 = ["--gpus", "2", "--keys-log2", "27", "--steps", "2", "--warmup", "1", "--full"]
 
 
 def test_bench_gpus_2_without_a_launcher():
-    """`python bench.py --gpus 2`, nothing else: two device threads in one process (two GPUs if the box has them)"""
+    """`python bench.py --gpus 2 --full`, no launcher: two device threads in one process (two GPUs if the box has them)"""
     env, _ = two_gpu_env()
     pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SMALL2, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                         timeout=1200, cwd=ROOT, env=env)
@@ -140,7 +140,7 @@ def test_bench_gpus_8_shared(launcher):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     if ngpu < 8:
         env["ECL_BENCH_SHARE_GPU"] = "1"
-    tail = ["--gpus", "8", "--keys-log2", "29", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-secondary"]
+    tail = ["--gpus", "8", "--keys-log2", "29", "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-secondary"]
     if launcher == "threads":
         cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + tail
     else:

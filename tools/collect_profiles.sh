@@ -135,9 +135,9 @@ for k in mul cu_endo; do
 done
 want calib && cp "$O/calib.txt" "profiles/${TAG}_fetch_calibration.txt"
 want ubench && cat "$O/ubench8.txt" "$O/ubench4.txt" > "profiles/ubench_${TAG}.txt"
-# the final bench line, priced with the profiles just taken
+# the final bench line with everything --full measures beside the headline, priced with the profiles just taken
 if want bench; then
-  python bench.py > "$O/bench.json" 2> "$O/bench.err"
+  python bench.py --full > "$O/bench.json" 2> "$O/bench.err"
   cp "$O/bench.json" "profiles/${TAG}_bench.json"
   cat "$O/bench.json"
 fi
