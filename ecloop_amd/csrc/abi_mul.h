@@ -208,14 +208,19 @@ static void mul_geometry(u32 m, u32* R_out, u32* nt_out) {
 // one piece on compute stream `lane` (0: the context's stream, 1: the second one), parking space `lane`
 static void mul_launch_piece(ecl_hip* h, int lane, const u32* d_k, u32 m, u32 at, const wtab& gtab, const add_args& a) {
   u32 R, nt;
-  const bool a33 = h->flags & ECL_ADDR33, a65 = h->flags & ECL_ADDR65;
   hipStream_t st = lane ? h->stream2 : h->stream;
   u32* tmp = h->d_multmp[lane];
   mul_geometry(m, &R, &nt);
   dim3 grid(nt / 256), blk(256);
-  if (a33 && a65) hipLaunchKernelGGL((k_mul_check<true, true>), grid, blk, 0, st, d_k, m, at, gtab, a, tmp, nt, R);
-  else if (a33) hipLaunchKernelGGL((k_mul_check<true, false>), grid, blk, 0, st, d_k, m, at, gtab, a, tmp, nt, R);
-  else hipLaunchKernelGGL((k_mul_check<false, true>), grid, blk, 0, st, d_k, m, at, gtab, a, tmp, nt, R);
+  switch (h->flags & (ECL_ADDR33 | ECL_ADDR65 | ECL_P2SH)) {  // every non-empty set of address types
+  case ECL_ADDR33: hipLaunchKernelGGL((k_mul_check<true, false>), grid, blk, 0, st, d_k, m, at, gtab, a, tmp, nt, R); break;
+  case ECL_ADDR65: hipLaunchKernelGGL((k_mul_check<false, true>), grid, blk, 0, st, d_k, m, at, gtab, a, tmp, nt, R); break;
+  case ECL_ADDR33 | ECL_ADDR65: hipLaunchKernelGGL((k_mul_check<true, true>), grid, blk, 0, st, d_k, m, at, gtab, a, tmp, nt, R); break;
+  case ECL_P2SH: hipLaunchKernelGGL((k_mul_check_p2sh<false, false>), grid, blk, 0, st, d_k, m, at, gtab, a, tmp, nt, R); break;
+  case ECL_ADDR33 | ECL_P2SH: hipLaunchKernelGGL((k_mul_check_p2sh<true, false>), grid, blk, 0, st, d_k, m, at, gtab, a, tmp, nt, R); break;
+  case ECL_ADDR65 | ECL_P2SH: hipLaunchKernelGGL((k_mul_check_p2sh<false, true>), grid, blk, 0, st, d_k, m, at, gtab, a, tmp, nt, R); break;
+  default: hipLaunchKernelGGL((k_mul_check_p2sh<true, true>), grid, blk, 0, st, d_k, m, at, gtab, a, tmp, nt, R); break;
+  }
 }
 // window width of the next call: the caller's, or the short table until this context has seen enough scalars to pay for the long one
 static u32 mul_window_for(const ecl_hip* h, u32 n) {
@@ -509,6 +514,20 @@ extern "C" int ecl_hip_verify(ecl_hip* h, const uint64_t (*k)[4], uint32_t n, ui
   HIPCHK(h, hipMemcpyAsync(h33, d33, (size_t)n * 20, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemcpyAsync(h65, d65, (size_t)n * 20, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return ECL_OK;
+}
+
+extern "C" int ecl_hip_p2sh_hash(ecl_hip* h, const uint32_t (*h33)[5], uint32_t (*out)[5], uint32_t n) {
+  if (!h || !h33 || !out || n == 0 || n > (1u << 31)) return ECL_E_ARG;
+  HIPCHK(h, hipSetDevice(h->dev));
+  dbuf<u32> d;
+  HIPCHK(h, hipMalloc(&d.p, (size_t)n * 40));
+  u32* dout = d.p + (size_t)n * 5;
+  HIPCHK(h, hipMemcpyAsync(d.p, h33, (size_t)n * 20, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_p2sh_hash, dim3((n + 63) / 64), dim3(64), 0, h->stream, d.p, dout, n);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(out, dout, (size_t)n * 20, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return ECL_OK;
 }

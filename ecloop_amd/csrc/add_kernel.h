@@ -26,7 +26,7 @@
 struct ecl_found_dev {
   u64 key_offset;
   u32 h160[5];
-  u32 tag;  // byte 0 = endo, byte 1 = compressed
+  u32 tag;  // byte 0 = endo, byte 1 = address type (ecl_found.compressed: 1 addr33, 0 addr65, 2 p2sh)
 };
 
 struct add_args {
@@ -165,31 +165,37 @@ __device__ __forceinline__ cand_rec cand_take(cand_queue& q, bool& valid) {
 struct cand_queues {
   cand_queue a, b;
 };
+// P2SH: the kernel reports the address type 2 as well, so the type byte of a parked record keeps two bits instead of one
+template <bool P2SH>
 __device__ __forceinline__ void cand_finish(const add_args& a, cand_queue& qb) {  // up to 64 records of ring B
   bool valid;
   const cand_rec r = cand_take(qb, valid);
   const int from = bloom_mid_two(a.bloom) ? 3 : 2;  // probe 0 and the middle stage's one or two are done
   if (valid && bloom_probes_from(a.bloom, r.h, from))
-    found_push(a, r.off, r.h, r.tag & 0xff, (r.tag >> 8) & 1);
+    found_push(a, r.off, r.h, r.tag & 0xff, (r.tag >> 8) & (P2SH ? 3 : 1));
 }
+template <bool P2SH>
 __device__ __forceinline__ void cand_mid(const add_args& a, cand_queues& q) {  // up to 64 records of ring A -> ring B
   bool valid;
   const cand_rec r = cand_take(q.a, valid);
   const bool pass = valid && bloom_mid(a.bloom, r.h, bloom_mid_two(a.bloom));
-  if (cand_append(q.b, pass, r.off, r.h, r.tag)) cand_finish(a, q.b);
+  if (cand_append(q.b, pass, r.off, r.h, r.tag)) cand_finish<P2SH>(a, q.b);
 }
+template <bool P2SH>
 __device__ __forceinline__ void cand_push(const add_args& a, cand_queues* q, bool pass, u64 off, const u32 h[5], u32 tag) {
-  if (cand_append(q->a, pass, off, h, tag)) cand_mid(a, *q);
+  if (cand_append(q->a, pass, off, h, tag)) cand_mid<P2SH>(a, *q);
 }
+template <bool P2SH>
 __device__ __forceinline__ void cand_flush(const add_args& a, cand_queues& q) {  // end of the kernel: the remainders
-  cand_mid(a, q);  // A holds < 64
-  cand_finish(a, q.b);  // B holds < 128: at most two rounds
-  cand_finish(a, q.b);
+  cand_mid<P2SH>(a, q);  // A holds < 64
+  cand_finish<P2SH>(a, q.b);  // B holds < 128: at most two rounds
+  cand_finish<P2SH>(a, q.b);
 }
 // Filter test of one hash; q == nullptr: no queue (`mul` kernel), everything in place.  With a queue the call must
 // be reached by ALL lanes of the wave together: lanes whose key is outside the range come along with live = false.
 // (Deferring the stage-1 test by one hash - loads in flight under the next hash160 - was measured: no gain, the
 // other waves of the SIMD already cover the probe latency.)
+template <bool P2SH>
 __device__ __forceinline__ void filter_check(const add_args& a, cand_queues* q, bool live, u64 off, const u32 h[5], u32 endo,
                                              u32 compressed) {
   const bool pass = live && bloom_stage1(a.bloom, h);
@@ -197,13 +203,15 @@ __device__ __forceinline__ void filter_check(const add_args& a, cand_queues* q, 
     if (pass && bloom_stage2(a.bloom, h)) found_push(a, off, h, endo, compressed);
     return;
   }
-  cand_push(a, q, pass, off, h, endo | (compressed << 8));
+  cand_push<P2SH>(a, q, pass, off, h, endo | (compressed << 8));
 }
 
 // hash every selected encoding / endomorphism image of the affine point (x, y) and probe the filter
 // (check_found_add, main.c:287-347; endo images (x,-y) (bx,y) (bx,-y) (b2x,y) (b2x,-y), main.c:314-327).
+// P2SH (no reference counterpart): the script hash of the compressed key's hash160, one more SHA-256 and RIPEMD-160 block fed
+// by the addr33 hash, which is computed for it even when addr33 itself is not searched.
 // x: magnitude <= 4, y: magnitude <= 3.
-template <bool A33, bool A65, bool ENDO>
+template <bool A33, bool A65, bool P2SH, bool ENDO>
 __device__ __forceinline__ void check_point(const add_args& a, cand_queues* q, bool live, fe x, fe y, u64 off) {
   u32 xw[3][8], yw[2][8], par = 0;
   if (ENDO) {
@@ -235,16 +243,21 @@ __device__ __forceinline__ void check_point(const add_args& a, cand_queues* q, b
     u32 xs[8], h[5];
 #pragma unroll
     for (int i = 0; i < 8; ++i) xs[i] = ENDO ? (e < 2 ? xw[0][i] : (e < 4 ? xw[1][i] : xw[2][i])) : xw[0][i];
-    if (A33) {
+    if (A33 || P2SH) {
       hash160_33(h, xs, (par ^ (u32)e) & 1u);  // parity(-y) = !parity(y): p is odd, y != 0
-      filter_check(a, q, live, off, h, e, 1);
+      if (A33) filter_check<P2SH>(a, q, live, off, h, e, 1);
+      if (P2SH) {
+        u32 hs[5];
+        hash160_p2sh(hs, h);
+        filter_check<P2SH>(a, q, live, off, hs, e, 2);
+      }
     }
     if (A65) {
       u32 ys[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) ys[i] = (ENDO && (e & 1)) ? yw[1][i] : yw[0][i];
       hash160_65(h, xs, ys);
-      filter_check(a, q, live, off, h, e, 0);
+      filter_check<P2SH>(a, q, live, off, h, e, 0);
     }
   }
 }
@@ -257,103 +270,25 @@ __device__ __forceinline__ void check_point(const add_args& a, cand_queues* q, b
 // only thing the size decides is the granularity at which the dispatcher hands out work: 64 / 128 / 256 measured equal
 // within 0.1 % in round 2 (tried and rejected); the lane count of a call is a multiple of 256
 #define ECL_ADD_BLOCK 256
-template <bool A33, bool A65, bool ENDO>
-__global__ void __launch_bounds__(ECL_ADD_BLOCK, (A65 && ENDO) ? 3 : ECL_ADD_WAVES) k_add(const add_args a) {
-  __shared__ u32 q_mem[ECL_ADD_BLOCK / 64][2][8 * ECL_Q_SLOTS];  // two candidate rings per wave
-  cand_queues q;
-  q.a.mem = q_mem[threadIdx.x >> 6][0], q.a.head = 0, q.a.count = 0;
-  q.b.mem = q_mem[threadIdx.x >> 6][1], q.b.head = 0, q.b.count = 0;
-  const u32 g = blockIdx.x * (u32)ECL_ADD_BLOCK + threadIdx.x;
-  const u32 T = a.T, B = a.B;
-  if (g >= T) return;
-  const size_t plane = T;
-  // centre (X, Y): canonical in HBM, magnitude 1 in registers
-  fe X = fe_ld_words2(a.cxy + g, plane), Y = fe_ld_words2(a.cxy + 2 * (size_t)T + g, plane);
-  const fe Jx = fe_ldw(a.jump), Jy = fe_ldw(a.jump + 8);
-  const ctab_ptr tab = (ctab_ptr)(uintptr_t)a.tab;
-  uint4* scr4 = a.scratch + g;
-  u32* scr2 = a.scratch2 + g;
-  const size_t s4 = 2 * (size_t)T;  // one chain element = two uint4 planes + one u32 plane
-
-#pragma unroll 1
-  for (u32 b = 0; b < a.nb; ++b) {
-    const u64 base = ((u64)b * T + g) * (2ull * B);
-    // groups only grow: a wave leaves when none of its lanes has keys left (wave-uniform control flow keeps the
-    // candidate queue state uniform; the lane count is sized to the range, so idle lanes are rare)
-    if (__builtin_amdgcn_ballot_w64(base < a.nkeys) == 0) break;
-
-    // ---- phase 1: prefix products of e_0 = Jx - X, e_k = Gx_{k-1} - X   (differences have magnitude 3)
-    fe acc = fe_sub(Jx, X);
-    fe_normalize_weak(acc);            // magnitude 1: the chain multiplies it by a magnitude-3 difference
-    const bool dbl = fe_is_zero(acc);  // C == J: next centre is 2C (C == -J would be the scalar 0: excluded)
-    if (dbl) acc = fe_one();
-#pragma unroll 1
-    for (u32 k = 1; k <= B; ++k) {
-      fe_st_limbs(scr4 + (size_t)(k - 1) * s4, plane, scr2 + (size_t)(k - 1) * plane, acc);
-      fe dx = fe_sub(fe_ld_tab(tab + (size_t)(k - 1) * ECL_TAB_STRIDE), X);
-      acc = fe_mul(acc, dx);
-    }
-    // ---- phase 2: one inversion for the whole chain
-    fe inv = fe_inv(acc);
-    // ---- phase 3: walk the chain backwards, emit C +- G_i.  Each prefix product is loaded at use: loading it one
-    // iteration ahead measured 2.9 % slower (profiles/r03_pmc_filter_compare.txt section 4)
-#pragma unroll 1
-    for (u32 k = B; k >= 1; --k) {
-      const u32 i = k - 1;
-      const fe pre = fe_ld_limbs(scr4 + (size_t)i * s4, plane, scr2 + (size_t)i * plane);
-      const fe gx = fe_ld_tab(tab + (size_t)i * ECL_TAB_STRIDE), gy = fe_ld_tab(tab + (size_t)i * ECL_TAB_STRIDE + FE_LIMBS);
-      const fe dx = fe_sub(gx, X);
-      const fe invk = fe_mul(inv, pre);  // 1 / (Gx_i - X)
-      inv = fe_mul(inv, dx);
-      const fe nxg = fe_neg(fe_add(X, gx), 2);  // -(X + Gx), magnitude 3
-      const int nwhich = (k == 1) ? 3 : 2;
-#pragma unroll 1
-      for (int which = 0; which < nwhich; ++which) {
-        fe px, py;
-        u64 off;
-        bool valid = true;  // wave-uniform
-        if (which < 2) {
-          // lambda = (+-Gy - Y) / (Gx - X); x3 = lambda^2 - X - Gx; y3 = lambda (X - x3) - Y   (main.c:379-386)
-          // +-Gy - Y, magnitude 3.  The table side (Gy + 2p or 3p - Gy) is wave-uniform like `which`: selected on
-          // the scalar unit, so the vector side is one subtraction per limb (written as a select of two vector
-          // results the compiler emits both and nine v_cndmask)
-          const fe c = which == 0 ? fe_add(gy, fe_neg(fe_zero(), 1)) : fe_neg(gy, 2);
-          fe s;
-#pragma unroll
-          for (int l = 0; l < FE_LIMBS; ++l) s.n[l] = c.n[l] - Y.n[l];
-          fe lam = fe_mul(s, invk);
-          px = fe_add(fe_sqr(lam), nxg);                                   // magnitude 4
-          py = fe_sub(fe_mul(lam, fe_add(X, fe_neg(px, 4))), Y);           // X - px: magnitude 6; py: magnitude 3
-          off = base + (which == 0 ? B + 1 + i : B - 1 - i);  // scalar select, one 64-bit add
-          valid = which == 1 || i + 1 < B;
-        } else {
-          px = X, py = Y, off = base + B;
-          // the centre itself, once per B iterations: keep the copies of X and Y inside this branch (left alone, the
-          // compiler copies them into px / py at the head of EVERY iteration and overwrites them: 18 moves per key)
-#pragma unroll
-          for (int l = 0; l < FE_LIMBS; ++l) {
-            FE_HIDE24(px.n[l]);
-            FE_HIDE24(py.n[l]);
-          }
-        }
-        if (valid) check_point<A33, A65, ENDO>(a, &q, off < a.nkeys, px, py, off);
-      }
-    }
-    // ---- next centre: C + J with 1/(Jx - X) = inv (or the tangent if C == J)
-    fe lam;
-    if (!dbl) {
-      lam = fe_mul(fe_sub(Jy, Y), inv);
-    } else {
-      fe x2 = fe_sqr(X);
-      lam = fe_mul(fe_add(fe_add(x2, x2), x2), fe_inv(fe_add(Y, Y)));
-    }
-    fe Xn = fe_add(fe_sqr(lam), fe_neg(fe_add(X, Jx), 2));           // magnitude 4
-    fe Yn = fe_sub(fe_mul(lam, fe_add(X, fe_neg(Xn, 4))), Y);        // magnitude 3
-    fe_normalize_weak(Xn);
-    fe_normalize_weak(Yn);
-    X = Xn, Y = Yn;
-  }
-  cand_flush(a, q);
-  fe_st_words2(a.cxy + g, plane, X);
-  fe_st_words2(a.cxy + 2 * (size_t)T + g, plane, Y);
-}
+// The kernel body is written once (add_walk.inc) and instantiated under two names: k_add for addr33 / addr65 and k_add_p2sh for the
+// sets that include P2SH.  Two names rather than a fourth template parameter, so that the six instantiations without P2SH keep their
+// symbols (tools/isa_mix.py and the tracked profiles/ records are keyed on them); and the body sits in each kernel itself rather than
+// in a __device__ function that both call, because the compiler optimises such a function on its own before it inlines it: built
+// that way, all six came out with a different register allocation than before (and k_mul_check with 16 more bytes of scratch).
+#define ECL_WALK_KERNEL k_add
+#define ECL_WALK_P2SH false
+#define ECL_WALK_WAVES ((A65 && ENDO) ? 3 : ECL_ADD_WAVES)
+#include "add_walk.inc"
+#undef ECL_WALK_KERNEL
+#undef ECL_WALK_P2SH
+#undef ECL_WALK_WAVES
+// P2SH instantiations (A33 / A65 = the other types searched with it), at the waves per SIMD of the k_add instantiation with the same
+// A65 / ENDO.  All eight keep their per-key loops (prefix products, table, `which`) free of scratch instructions, like the six above:
+// what they spill sits in the once-per-group launch loop (tools/isa_mix.py on the built library)
+#define ECL_WALK_KERNEL k_add_p2sh
+#define ECL_WALK_P2SH true
+#define ECL_WALK_WAVES ((A65 && ENDO) ? 3 : ECL_ADD_WAVES)
+#include "add_walk.inc"
+#undef ECL_WALK_KERNEL
+#undef ECL_WALK_P2SH
+#undef ECL_WALK_WAVES

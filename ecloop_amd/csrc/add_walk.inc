@@ -1,0 +1,104 @@
+// add_walk.inc - the body of the add kernel, instantiated twice by add_kernel.h: as k_add (address types addr33 / addr65) and as
+// k_add_p2sh (the same sets plus P2SH, and P2SH alone).  Included with ECL_WALK_KERNEL (the kernel's name), ECL_WALK_P2SH and
+// ECL_WALK_WAVES (waves per SIMD of an instantiation, an expression of A33 / A65 / ENDO) defined; no include guard on purpose.
+template <bool A33, bool A65, bool ENDO>
+__global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL(const add_args a) {
+  constexpr bool P2SH = ECL_WALK_P2SH;
+  __shared__ u32 q_mem[ECL_ADD_BLOCK / 64][2][8 * ECL_Q_SLOTS];  // two candidate rings per wave
+  cand_queues q;
+  q.a.mem = q_mem[threadIdx.x >> 6][0], q.a.head = 0, q.a.count = 0;
+  q.b.mem = q_mem[threadIdx.x >> 6][1], q.b.head = 0, q.b.count = 0;
+  const u32 g = blockIdx.x * (u32)ECL_ADD_BLOCK + threadIdx.x;
+  const u32 T = a.T, B = a.B;
+  if (g >= T) return;
+  const size_t plane = T;
+  // centre (X, Y): canonical in HBM, magnitude 1 in registers
+  fe X = fe_ld_words2(a.cxy + g, plane), Y = fe_ld_words2(a.cxy + 2 * (size_t)T + g, plane);
+  const fe Jx = fe_ldw(a.jump), Jy = fe_ldw(a.jump + 8);
+  const ctab_ptr tab = (ctab_ptr)(uintptr_t)a.tab;
+  uint4* scr4 = a.scratch + g;
+  u32* scr2 = a.scratch2 + g;
+  const size_t s4 = 2 * (size_t)T;  // one chain element = two uint4 planes + one u32 plane
+
+#pragma unroll 1
+  for (u32 b = 0; b < a.nb; ++b) {
+    const u64 base = ((u64)b * T + g) * (2ull * B);
+    // groups only grow: a wave leaves when none of its lanes has keys left (wave-uniform control flow keeps the
+    // candidate queue state uniform; the lane count is sized to the range, so idle lanes are rare)
+    if (__builtin_amdgcn_ballot_w64(base < a.nkeys) == 0) break;
+
+    // ---- phase 1: prefix products of e_0 = Jx - X, e_k = Gx_{k-1} - X   (differences have magnitude 3)
+    fe acc = fe_sub(Jx, X);
+    fe_normalize_weak(acc);            // magnitude 1: the chain multiplies it by a magnitude-3 difference
+    const bool dbl = fe_is_zero(acc);  // C == J: next centre is 2C (C == -J would be the scalar 0: excluded)
+    if (dbl) acc = fe_one();
+#pragma unroll 1
+    for (u32 k = 1; k <= B; ++k) {
+      fe_st_limbs(scr4 + (size_t)(k - 1) * s4, plane, scr2 + (size_t)(k - 1) * plane, acc);
+      fe dx = fe_sub(fe_ld_tab(tab + (size_t)(k - 1) * ECL_TAB_STRIDE), X);
+      acc = fe_mul(acc, dx);
+    }
+    // ---- phase 2: one inversion for the whole chain
+    fe inv = fe_inv(acc);
+    // ---- phase 3: walk the chain backwards, emit C +- G_i.  Each prefix product is loaded at use: loading it one
+    // iteration ahead measured 2.9 % slower (profiles/r03_pmc_filter_compare.txt section 4)
+#pragma unroll 1
+    for (u32 k = B; k >= 1; --k) {
+      const u32 i = k - 1;
+      const fe pre = fe_ld_limbs(scr4 + (size_t)i * s4, plane, scr2 + (size_t)i * plane);
+      const fe gx = fe_ld_tab(tab + (size_t)i * ECL_TAB_STRIDE), gy = fe_ld_tab(tab + (size_t)i * ECL_TAB_STRIDE + FE_LIMBS);
+      const fe dx = fe_sub(gx, X);
+      const fe invk = fe_mul(inv, pre);  // 1 / (Gx_i - X)
+      inv = fe_mul(inv, dx);
+      const fe nxg = fe_neg(fe_add(X, gx), 2);  // -(X + Gx), magnitude 3
+      const int nwhich = (k == 1) ? 3 : 2;
+#pragma unroll 1
+      for (int which = 0; which < nwhich; ++which) {
+        fe px, py;
+        u64 off;
+        bool valid = true;  // wave-uniform
+        if (which < 2) {
+          // lambda = (+-Gy - Y) / (Gx - X); x3 = lambda^2 - X - Gx; y3 = lambda (X - x3) - Y   (main.c:379-386)
+          // +-Gy - Y, magnitude 3.  The table side (Gy + 2p or 3p - Gy) is wave-uniform like `which`: selected on
+          // the scalar unit, so the vector side is one subtraction per limb (written as a select of two vector
+          // results the compiler emits both and nine v_cndmask)
+          const fe c = which == 0 ? fe_add(gy, fe_neg(fe_zero(), 1)) : fe_neg(gy, 2);
+          fe s;
+#pragma unroll
+          for (int l = 0; l < FE_LIMBS; ++l) s.n[l] = c.n[l] - Y.n[l];
+          fe lam = fe_mul(s, invk);
+          px = fe_add(fe_sqr(lam), nxg);                                   // magnitude 4
+          py = fe_sub(fe_mul(lam, fe_add(X, fe_neg(px, 4))), Y);           // X - px: magnitude 6; py: magnitude 3
+          off = base + (which == 0 ? B + 1 + i : B - 1 - i);  // scalar select, one 64-bit add
+          valid = which == 1 || i + 1 < B;
+        } else {
+          px = X, py = Y, off = base + B;
+          // the centre itself, once per B iterations: keep the copies of X and Y inside this branch (left alone, the
+          // compiler copies them into px / py at the head of EVERY iteration and overwrites them: 18 moves per key)
+#pragma unroll
+          for (int l = 0; l < FE_LIMBS; ++l) {
+            FE_HIDE24(px.n[l]);
+            FE_HIDE24(py.n[l]);
+          }
+        }
+        if (valid) check_point<A33, A65, P2SH, ENDO>(a, &q, off < a.nkeys, px, py, off);
+      }
+    }
+    // ---- next centre: C + J with 1/(Jx - X) = inv (or the tangent if C == J)
+    fe lam;
+    if (!dbl) {
+      lam = fe_mul(fe_sub(Jy, Y), inv);
+    } else {
+      fe x2 = fe_sqr(X);
+      lam = fe_mul(fe_add(fe_add(x2, x2), x2), fe_inv(fe_add(Y, Y)));
+    }
+    fe Xn = fe_add(fe_sqr(lam), fe_neg(fe_add(X, Jx), 2));           // magnitude 4
+    fe Yn = fe_sub(fe_mul(lam, fe_add(X, fe_neg(Xn, 4))), Y);        // magnitude 3
+    fe_normalize_weak(Xn);
+    fe_normalize_weak(Yn);
+    X = Xn, Y = Yn;
+  }
+  cand_flush<P2SH>(a, q);
+  fe_st_words2(a.cxy + g, plane, X);
+  fe_st_words2(a.cxy + 2 * (size_t)T + g, plane, Y);
+}

@@ -128,7 +128,8 @@ const char* ecl_hip_strerror(int code) {
 const char* ecl_hip_last_error(const ecl_hip* h) { return h ? h->err.c_str() : ""; }
 
 int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
-  if (!out || ord_offs > 255 || !(flags & (ECL_ADDR33 | ECL_ADDR65)) || (flags & ~7u)) return ECL_E_ARG;
+  const u32 types = ECL_ADDR33 | ECL_ADDR65 | ECL_P2SH;
+  if (!out || ord_offs > 255 || !(flags & types) || (flags & ~(types | ECL_ENDO))) return ECL_E_ARG;
   int n = ecl_hip_device_count();
   if (device < 0 || device >= n) return ECL_E_NODEV;
   ecl_hip* h = new ecl_hip();
@@ -149,7 +150,7 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   static std::mutex mu;
   static std::set<u32> passed;
   const char* skip = getenv("ECL_HIP_SKIP_SELFTEST");
-  const u32 key = (u32)device * 8u + flags;
+  const u32 key = (u32)device * 32u + flags;  // flags < 32
   {
     std::lock_guard<std::mutex> lk(mu);
     if ((skip && skip[0] == '1') || passed.count(key)) return ECL_OK;
@@ -380,11 +381,18 @@ int ecl_hip_get_setup_timing(ecl_hip* h, double* setup_ms, uint64_t* setups) {
 // ------------------------------------------------------------------------------------------------ add path (host)
 
 typedef void (*add_kernel_t)(const add_args);
+// every non-empty set of address types (ecl_hip_open refuses the empty one) x endo
 static add_kernel_t pick_add_kernel(u32 flags) {
-  bool a33 = flags & ECL_ADDR33, a65 = flags & ECL_ADDR65, endo = flags & ECL_ENDO;
-  if (a33 && !a65) return endo ? k_add<true, false, true> : k_add<true, false, false>;
-  if (!a33 && a65) return endo ? k_add<false, true, true> : k_add<false, true, false>;
-  return endo ? k_add<true, true, true> : k_add<true, true, false>;
+  const bool endo = flags & ECL_ENDO;
+  switch (flags & (ECL_ADDR33 | ECL_ADDR65 | ECL_P2SH)) {
+  case ECL_ADDR33: return endo ? k_add<true, false, true> : k_add<true, false, false>;
+  case ECL_ADDR65: return endo ? k_add<false, true, true> : k_add<false, true, false>;
+  case ECL_ADDR33 | ECL_ADDR65: return endo ? k_add<true, true, true> : k_add<true, true, false>;
+  case ECL_P2SH: return endo ? k_add_p2sh<false, false, true> : k_add_p2sh<false, false, false>;
+  case ECL_ADDR33 | ECL_P2SH: return endo ? k_add_p2sh<true, false, true> : k_add_p2sh<true, false, false>;
+  case ECL_ADDR65 | ECL_P2SH: return endo ? k_add_p2sh<false, true, true> : k_add_p2sh<false, true, false>;
+  default: return endo ? k_add_p2sh<true, true, true> : k_add_p2sh<true, true, false>;
+  }
 }
 
 // found records of one call: [0, raw_cap) written by the search kernel; in list mode the confirmed ones are
@@ -410,7 +418,7 @@ static void found_to_host(ecl_found* out, const ecl_found_dev* tmp, u32 n, bool 
   for (u32 i = 0; i < n; ++i) {
     out[i].key_offset = tmp[i].key_offset;
     memcpy(out[i].h160, tmp[i].h160, 20);
-    out[i].endo = keep_endo ? (uint8_t)(tmp[i].tag & 0xff) : 0, out[i].compressed = (uint8_t)((tmp[i].tag >> 8) & 1);
+    out[i].endo = keep_endo ? (uint8_t)(tmp[i].tag & 0xff) : 0, out[i].compressed = (uint8_t)((tmp[i].tag >> 8) & 0xff);
     out[i].pad[0] = out[i].pad[1] = 0;
   }
 }

@@ -96,6 +96,44 @@ H_FN void sha256_init(u32 st[8]) {
   st[0] = 0x6a09e667, st[1] = 0xbb67ae85, st[2] = 0x3c6ef372, st[3] = 0xa54ff53a;
   st[4] = 0x510e527f, st[5] = 0x9b05688c, st[6] = 0x1f83d9ab, st[7] = 0x5be0cd19;
 }
+// SHA-256 state after the one block of a 22-byte message (the P2SH-P2WPKH redeem script 00 14 <20 bytes>), from the IV: m = message
+// words 0..5 (the 0x80 pad byte included).  Words 6..14 (zero) and 15 (176 bits) are written into the rounds as literals, and so is
+// the IV: rounds 6..15 add the round constant alone and the schedule's first expansions lose their zero terms at compile time.
+H_FN void sha256_iv_22(u32 st[8], const u32 m[6]) {
+  u32 a = 0x6a09e667, b = 0xbb67ae85, c = 0x3c6ef372, d = 0xa54ff53a, e = 0x510e527f, f = 0x9b05688c, g = 0x1f83d9ab, h = 0x5be0cd19;
+  SHA_RND(a, b, c, d, e, f, g, h, SHA256_K[0], m[0]);
+  SHA_RND(h, a, b, c, d, e, f, g, SHA256_K[1], m[1]);
+  SHA_RND(g, h, a, b, c, d, e, f, SHA256_K[2], m[2]);
+  SHA_RND(f, g, h, a, b, c, d, e, SHA256_K[3], m[3]);
+  SHA_RND(e, f, g, h, a, b, c, d, SHA256_K[4], m[4]);
+  SHA_RND(d, e, f, g, h, a, b, c, SHA256_K[5], m[5]);
+  SHA_RND(c, d, e, f, g, h, a, b, SHA256_K[6], 0u);
+  SHA_RND(b, c, d, e, f, g, h, a, SHA256_K[7], 0u);
+  SHA_RND(a, b, c, d, e, f, g, h, SHA256_K[8], 0u);
+  SHA_RND(h, a, b, c, d, e, f, g, SHA256_K[9], 0u);
+  SHA_RND(g, h, a, b, c, d, e, f, SHA256_K[10], 0u);
+  SHA_RND(f, g, h, a, b, c, d, e, SHA256_K[11], 0u);
+  SHA_RND(e, f, g, h, a, b, c, d, SHA256_K[12], 0u);
+  SHA_RND(d, e, f, g, h, a, b, c, SHA256_K[13], 0u);
+  SHA_RND(c, d, e, f, g, h, a, b, SHA256_K[14], 0u);
+  SHA_RND(b, c, d, e, f, g, h, a, SHA256_K[15], 176u);
+  u32 w[16] = {m[0], m[1], m[2], m[3], m[4], m[5], 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 176u};
+#pragma unroll
+  for (int i = 16; i < 64; i += 8) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) SHA_EXP(w, i + j);
+    SHA_RND(a, b, c, d, e, f, g, h, SHA256_K[i + 0], w[(i + 0) & 15]);
+    SHA_RND(h, a, b, c, d, e, f, g, SHA256_K[i + 1], w[(i + 1) & 15]);
+    SHA_RND(g, h, a, b, c, d, e, f, SHA256_K[i + 2], w[(i + 2) & 15]);
+    SHA_RND(f, g, h, a, b, c, d, e, SHA256_K[i + 3], w[(i + 3) & 15]);
+    SHA_RND(e, f, g, h, a, b, c, d, SHA256_K[i + 4], w[(i + 4) & 15]);
+    SHA_RND(d, e, f, g, h, a, b, c, SHA256_K[i + 5], w[(i + 5) & 15]);
+    SHA_RND(c, d, e, f, g, h, a, b, SHA256_K[i + 6], w[(i + 6) & 15]);
+    SHA_RND(b, c, d, e, f, g, h, a, SHA256_K[i + 7], w[(i + 7) & 15]);
+  }
+  st[0] = 0x6a09e667 + a, st[1] = 0xbb67ae85 + b, st[2] = 0x3c6ef372 + c, st[3] = 0xa54ff53a + d;
+  st[4] = 0x510e527f + e, st[5] = 0x9b05688c + f, st[6] = 0x1f83d9ab + g, st[7] = 0x5be0cd19 + h;
+}
 
 // ---------------------------------------------------------------- RIPEMD-160, one block from the IV
 #define RMD_F1(x, y, z) XOR3(x, y, z)
@@ -202,6 +240,18 @@ H_FN void hash160_33(u32 h[5], const u32 x[8], u32 y_parity) {
   w[15] = 33 * 8;
   sha256_init(st);
   sha256_compress(st, w);
+  rmd160_of_sha(h, st);
+}
+// hash160 of the P2SH-P2WPKH redeem script 0x00 0x14 || h33 (BIP49 "3..." addresses; the reference has no such encoding):
+// h33 = hash160_33 of the key, h = the script hash, both in h160_t words.  The 22 script bytes shifted into big-endian message
+// words: w0 = 0x0014 | h33[0] high half, w1..w4 = h33[i-1] low half | h33[i] high half, w5 = h33[4] low half | the 0x80 pad byte.
+H_FN void hash160_p2sh(u32 h[5], const u32 h33[5]) {
+  u32 m[6], st[8];
+  m[0] = (0x0014u << 16) | (h33[0] >> 16);
+#pragma unroll
+  for (int i = 1; i < 5; ++i) m[i] = (h33[i - 1] << 16) | (h33[i] >> 16);
+  m[5] = (h33[4] << 16) | 0x8000u;
+  sha256_iv_22(st, m);
   rmd160_of_sha(h, st);
 }
 // hash160 of the uncompressed key 04 || X || Y  (lib/addr.c:47-67, 116-131)

@@ -1,0 +1,69 @@
+// mul_check.inc - the body of the `mul` kernel, instantiated twice by mul_kernels.h: as k_mul_check (address types addr33 / addr65)
+// and as k_mul_check_p2sh (the same sets plus P2SH, and P2SH alone), like add_walk.inc.  Included with ECL_MUL_KERNEL and ECL_MUL_P2SH
+// defined; no include guard on purpose.
+template <bool A33, bool A65>
+__global__ void __launch_bounds__(256, ECL_MUL_WAVES) ECL_MUL_KERNEL(const u32* __restrict__ k, u32 n, u32 base, const wtab gtab, add_args a,
+                                                      u32* __restrict__ tmp, u32 nt, u32 R) {
+  constexpr bool P2SH = ECL_MUL_P2SH;
+  __shared__ u32 q_mem[4][2][8 * ECL_Q_SLOTS];  // two candidate rings per wave (add_kernel.h)
+  const u32 t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= nt) return;  // nt is a multiple of 256: whole workgroups leave
+  fe prod = fe_one();
+  u32 infmask = 0;
+  // parked per scalar: X * ZZZ, Y * ZZ, T = ZZ * ZZZ and the running product of the T's; x = X ZZZ / T, y = Y ZZ / T
+#pragma unroll 1
+  for (u32 r = 0; r < R; ++r) {
+    const u32 i = r * nt + t;
+    if (i >= n) break;
+    u32 bad;
+    xyzz acc = wtab_sum_fast(k + (size_t)i * 8, gtab, bad);
+    acc.inf = 0;
+    // a zero digit (stand-in point), or P = +-Q on the way (h = 0: only scalars that are 0 (mod n) or built around n) which leaves ZZ = 0 -
+    // and a zero in the product chain would take the thread's other scalars with it: the complete sum, out of line
+    if (__builtin_expect(bad || fe_is_zero(acc.ZZ), 0)) {
+      u32 kk[9];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) kk[j] = k[(size_t)i * 8 + j];
+      kk[8] = 0;
+      acc = xyzz_from_jac(wtab_sum_complete(kk, gtab));
+    }
+    infmask |= (acc.inf ? 1u : 0u) << r;
+    fe tt, xs, ys, nprod;
+    fe_mul_pair(tt, xs, acc.ZZ, acc.ZZZ, acc.X, acc.ZZZ);
+    if (acc.inf) tt = fe_one();
+    fe_mul_pair(ys, nprod, acc.Y, acc.ZZ, prod, tt);
+    u32* p = tmp + (size_t)r * 36 * nt + t;
+#pragma unroll
+    for (int l = 0; l < FE_LIMBS; ++l) {
+      p[(size_t)l * nt] = xs.n[l], p[(size_t)(9 + l) * nt] = ys.n[l];
+      p[(size_t)(18 + l) * nt] = tt.n[l], p[(size_t)(27 + l) * nt] = prod.n[l];
+    }
+    prod = nprod;
+  }
+  fe inv = fe_inv(prod);
+  // the filter test through the add kernel's two candidate rings per wave (add_kernel.h: survivors of probe 0 are parked in LDS and
+  // finished 64 at a time): every lane of the wave walks all R rounds - a lane without a scalar (i >= n) or with the point at infinity
+  // comes along with live = false and leaves the inversion chain alone - so that the rings' wave-uniform state stays uniform
+  // (+1.7 % at the .blf design density against finishing every hash's test in place, profiles/r04_mul_rings.txt)
+  cand_queues q;
+  q.a.mem = q_mem[threadIdx.x >> 6][0], q.a.head = 0, q.a.count = 0;
+  q.b.mem = q_mem[threadIdx.x >> 6][1], q.b.head = 0, q.b.count = 0;
+#pragma unroll 1
+  for (u32 r = R; r-- > 0;) {
+    const u32 i = r * nt + t;
+    const bool have = i < n;
+    const u32* p = tmp + (size_t)r * 36 * nt + t;
+    fe X, Y, T, pre;
+#pragma unroll
+    for (int l = 0; l < FE_LIMBS; ++l) {
+      X.n[l] = have ? p[(size_t)l * nt] : 0u, Y.n[l] = have ? p[(size_t)(9 + l) * nt] : 0u;
+      T.n[l] = have ? p[(size_t)(18 + l) * nt] : (l == 0 ? 1u : 0u), pre.n[l] = have ? p[(size_t)(27 + l) * nt] : 0u;
+    }
+    fe ti, ninv, x, y;
+    fe_mul_pair(ti, ninv, inv, pre, inv, T);  // T = 1 for a lane without a scalar in this round
+    inv = ninv;
+    fe_mul_pair(x, y, X, ti, Y, ti);
+    check_point<A33, A65, P2SH, false>(a, &q, have && !((infmask >> r) & 1u), x, y, (u64)base + i);
+  }
+  cand_flush<P2SH>(a, q);
+}

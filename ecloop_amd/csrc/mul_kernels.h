@@ -189,71 +189,17 @@ __device__ __forceinline__ xyzz wtab_sum_fast(const u32* __restrict__ kw, const 
                             65536 x ECL_MUL_WAVES threads per piece.  With the low-register window sum the kernel fits 168 VGPRs (one spill): three
                             waves hide the wait states between dependent multiply-adds better than two (profiles/r04_mul_fastsum.txt: 2^26-scalar
                             calls 1391 against 1370 M scalars/s, 2^24 equal); the sum with the scalar in registers needed 67 spills there */
-template <bool A33, bool A65>
-__global__ void __launch_bounds__(256, ECL_MUL_WAVES) k_mul_check(const u32* __restrict__ k, u32 n, u32 base, const wtab gtab, add_args a,
-                                                   u32* __restrict__ tmp, u32 nt, u32 R) {
-  __shared__ u32 q_mem[4][2][8 * ECL_Q_SLOTS];  // two candidate rings per wave (add_kernel.h)
-  const u32 t = blockIdx.x * 256u + threadIdx.x;
-  if (t >= nt) return;  // nt is a multiple of 256: whole workgroups leave
-  fe prod = fe_one();
-  u32 infmask = 0;
-  // parked per scalar: X * ZZZ, Y * ZZ, T = ZZ * ZZZ and the running product of the T's; x = X ZZZ / T, y = Y ZZ / T
-#pragma unroll 1
-  for (u32 r = 0; r < R; ++r) {
-    const u32 i = r * nt + t;
-    if (i >= n) break;
-    u32 bad;
-    xyzz acc = wtab_sum_fast(k + (size_t)i * 8, gtab, bad);
-    acc.inf = 0;
-    // a zero digit (stand-in point), or P = +-Q on the way (h = 0: only scalars that are 0 (mod n) or built around n) which leaves ZZ = 0 -
-    // and a zero in the product chain would take the thread's other scalars with it: the complete sum, out of line
-    if (__builtin_expect(bad || fe_is_zero(acc.ZZ), 0)) {
-      u32 kk[9];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) kk[j] = k[(size_t)i * 8 + j];
-      kk[8] = 0;
-      acc = xyzz_from_jac(wtab_sum_complete(kk, gtab));
-    }
-    infmask |= (acc.inf ? 1u : 0u) << r;
-    fe tt, xs, ys, nprod;
-    fe_mul_pair(tt, xs, acc.ZZ, acc.ZZZ, acc.X, acc.ZZZ);
-    if (acc.inf) tt = fe_one();
-    fe_mul_pair(ys, nprod, acc.Y, acc.ZZ, prod, tt);
-    u32* p = tmp + (size_t)r * 36 * nt + t;
-#pragma unroll
-    for (int l = 0; l < FE_LIMBS; ++l) {
-      p[(size_t)l * nt] = xs.n[l], p[(size_t)(9 + l) * nt] = ys.n[l];
-      p[(size_t)(18 + l) * nt] = tt.n[l], p[(size_t)(27 + l) * nt] = prod.n[l];
-    }
-    prod = nprod;
-  }
-  fe inv = fe_inv(prod);
-  // the filter test through the add kernel's two candidate rings per wave (add_kernel.h: survivors of probe 0 are parked in LDS and
-  // finished 64 at a time): every lane of the wave walks all R rounds - a lane without a scalar (i >= n) or with the point at infinity
-  // comes along with live = false and leaves the inversion chain alone - so that the rings' wave-uniform state stays uniform
-  // (+1.7 % at the .blf design density against finishing every hash's test in place, profiles/r04_mul_rings.txt)
-  cand_queues q;
-  q.a.mem = q_mem[threadIdx.x >> 6][0], q.a.head = 0, q.a.count = 0;
-  q.b.mem = q_mem[threadIdx.x >> 6][1], q.b.head = 0, q.b.count = 0;
-#pragma unroll 1
-  for (u32 r = R; r-- > 0;) {
-    const u32 i = r * nt + t;
-    const bool have = i < n;
-    const u32* p = tmp + (size_t)r * 36 * nt + t;
-    fe X, Y, T, pre;
-#pragma unroll
-    for (int l = 0; l < FE_LIMBS; ++l) {
-      X.n[l] = have ? p[(size_t)l * nt] : 0u, Y.n[l] = have ? p[(size_t)(9 + l) * nt] : 0u;
-      T.n[l] = have ? p[(size_t)(18 + l) * nt] : (l == 0 ? 1u : 0u), pre.n[l] = have ? p[(size_t)(27 + l) * nt] : 0u;
-    }
-    fe ti, ninv, x, y;
-    fe_mul_pair(ti, ninv, inv, pre, inv, T);  // T = 1 for a lane without a scalar in this round
-    inv = ninv;
-    fe_mul_pair(x, y, X, ti, Y, ti);
-    check_point<A33, A65, false>(a, &q, have && !((infmask >> r) & 1u), x, y, (u64)base + i);
-  }
-  cand_flush(a, q);
-}
+// The body is written once (mul_check.inc) and instantiated as k_mul_check and k_mul_check_p2sh, for the reasons given at k_add
+#define ECL_MUL_KERNEL k_mul_check
+#define ECL_MUL_P2SH false
+#include "mul_check.inc"
+#undef ECL_MUL_KERNEL
+#undef ECL_MUL_P2SH
+#define ECL_MUL_KERNEL k_mul_check_p2sh
+#define ECL_MUL_P2SH true
+#include "mul_check.inc"
+#undef ECL_MUL_KERNEL
+#undef ECL_MUL_P2SH
 // ---- k_mul_check's window sum (round 4): written for a small register budget (three waves per SIMD) --------
 // * the scalar stays in memory: a digit is one 8-byte load at the digit's word (L2 / L1 hits after the first window: a wave's scalars
 //   are 2 KiB of contiguous memory) + a shift, not a 16-way select over eight registers, and is fetched one window ahead;
@@ -432,4 +378,15 @@ __global__ void __launch_bounds__(64) k_verify(const u32* __restrict__ k, u32 n,
 #pragma unroll
   for (int w = 0; w < 5; ++w) h65[(size_t)i * 5 + w] = h[w];
   ok[i] = (u8)fin;
+}
+// the P2SH half of pk_verify_hash (ecl_hip_p2sh_hash): the script hash of each given addr33 hash, one lane per hash
+__global__ void __launch_bounds__(64) k_p2sh_hash(const u32* __restrict__ h33, u32* __restrict__ out, u32 n) {
+  const u32 i = blockIdx.x * 64u + threadIdx.x;
+  if (i >= n) return;
+  u32 hi[5], ho[5];
+#pragma unroll
+  for (int w = 0; w < 5; ++w) hi[w] = h33[(size_t)i * 5 + w];
+  hash160_p2sh(ho, hi);
+#pragma unroll
+  for (int w = 0; w < 5; ++w) out[(size_t)i * 5 + w] = ho[w];
 }

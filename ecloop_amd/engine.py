@@ -11,7 +11,7 @@ import struct
 
 import numpy as np
 
-from .capi import Device, EclError
+from .capi import Device, EclError, label_of
 
 N = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141
 P = 2**256 - 2**32 - 977
@@ -234,13 +234,15 @@ class KeySearch:
     """ctx_t + cmd_add / cmd_mul for one GPU."""
 
     def __init__(self, flt, device=0, a33=True, a65=False, endo=False, ord_offs=0, verify=True, launch_keys=1 << 32,
-                 half_group=0, max_lanes=0, device_cls=None):
-        if not (a33 or a65):
+                 half_group=0, max_lanes=0, device_cls=None, p2sh=False):
+        if not (a33 or a65 or p2sh):
             a33 = True  # main.c:825-827
         self.flt, self.a33, self.a65, self.endo, self.offs, self.verify = flt, a33, a65, endo, ord_offs, verify
+        self.p2sh = p2sh  # P2SH-P2WPKH (no reference counterpart): records labelled "p2sh"
         self.stride = 1 << ord_offs
         # device_cls: the GPU context (capi.Device); the CPU tests of the host logic pass a stand-in with the same surface
-        self.dev = (device_cls or Device)(device, a33=a33, a65=a65, endo=endo, ord_offs=ord_offs)
+        kw = {"p2sh": True} if p2sh else {}  # (a stand-in without the P2SH type keeps working for the other types)
+        self.dev = (device_cls or Device)(device, a33=a33, a65=a65, endo=endo, ord_offs=ord_offs, **kw)
         if half_group or max_lanes:
             self.dev.set_geometry(half_group, max_lanes)
         self.dev.set_bloom(flt.words)
@@ -260,8 +262,9 @@ class KeySearch:
         if not recs:
             return
         h33, h65, ok = self.dev.verify([r.pk for r in recs])
+        hsh = self.dev.p2sh_hash(h33) if any(r.label == "p2sh" for r in recs) else None
         for i, r in enumerate(recs):
-            h = h33[i] if r.label == "addr33" else h65[i]
+            h = hsh[i] if r.label == "p2sh" else h33[i] if r.label == "addr33" else h65[i]
             if not ok[i] or [int(v) for v in h] != [int(v) for v in r.h160]:
                 raise EclError("[!] error: hash mismatch (%s) pk: %064x" % (r.label, r.pk))
 
@@ -271,7 +274,7 @@ class KeySearch:
             if not self.flt.confirm(r["h160"]):
                 continue
             pk = calc_priv(start, self.stride, int(r["key_offset"]), int(r["endo"]))
-            recs.append(FoundRecord("addr33" if r["compressed"] else "addr65", [int(v) for v in r["h160"]], pk))
+            recs.append(FoundRecord(label_of(r["compressed"]), [int(v) for v in r["h160"]], pk))
         if self.verify:
             self._verify(recs)
         self.found.extend(recs)
@@ -322,7 +325,7 @@ class KeySearch:
             raw, total = self.dev.mul_batch(ks, cap=c)
             for r in raw:
                 if self.flt.confirm(r["h160"]):
-                    self.found.append(FoundRecord("addr33" if r["compressed"] else "addr65", [int(v) for v in r["h160"]],
+                    self.found.append(FoundRecord(label_of(r["compressed"]), [int(v) for v in r["h160"]],
                                                   ks[int(r["key_offset"])]))
                     self.k_found += 1
             self.k_checked += len(ks)

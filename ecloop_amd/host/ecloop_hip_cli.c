@@ -114,7 +114,7 @@ static double bring_up(run_t *run, int shown, int real) {
     largest_call = scan_chunk(run, &keys, &fixed_shards);
     if (!(keys.w[1] | keys.w[2] | keys.w[3]) && keys.w[0] < largest_call) largest_call = keys.w[0];
   }
-  const u32 flags = (run->a33 ? ECL_ADDR33 : 0) | (run->a65 ? ECL_ADDR65 : 0) | (run->endo ? ECL_ENDO : 0);
+  const u32 flags = (run->a33 ? ECL_ADDR33 : 0) | (run->a65 ? ECL_ADDR65 : 0) | (run->p2sh ? ECL_P2SH : 0) | (run->endo ? ECL_ENDO : 0);
   pthread_t th[MAX_GPUS];
   bringup_t job[MAX_GPUS];
   for (int g = 0; g < run->ngpus; ++g) {
@@ -176,7 +176,8 @@ int main(int argc, const char **argv) {
   if (!plan_only) filter_open(&run.flt, o->filter);
   if (o->quiet && !o->outfile && !plan_only) { fprintf(stderr, "quiet mode chosen without output file\n"); exit(1); }
   run.a33 = o->addr ? strchr(o->addr, 'c') != NULL : true, run.a65 = o->addr && strchr(o->addr, 'u');
-  if (!run.a33 && !run.a65) run.a33 = true; /* main.c:825-827 */
+  run.p2sh = o->addr && strchr(o->addr, 's'); /* no reference counterpart: P2SH-P2WPKH */
+  if (!run.a33 && !run.a65 && !run.p2sh) run.a33 = true; /* main.c:825-827 */
   run.endo = o->endo && run.cmd != CMD_MUL, run.bin = o->bin && run.cmd == CMD_MUL;
   report_init(&run.rep, o->outfile, o->quiet);
   range_from_option(o->range, &run.range_s, &run.range_e);
@@ -213,7 +214,7 @@ int main(int argc, const char **argv) {
   if (shown > MAX_GPUS) shown = MAX_GPUS;
   const double setup_s = bring_up(&run, shown, real);
 
-  printf("gpus: %d ~ addr33: %d ~ addr65: %d ~ endo: %d | filter: ", shown, run.a33, run.a65, run.endo);
+  printf("gpus: %d ~ addr33: %d ~ addr65: %d ~ endo: %d%s | filter: ", shown, run.a33, run.a65, run.endo, run.p2sh ? " ~ p2sh: 1" : "");
   if (run.flt.list) printf("list (%'llu)\n", (unsigned long long)run.flt.nlist);
   else printf("bloom\n");
   if (run.cmd == CMD_ADD) print_scalar_row("range_s", &run.range_s), print_scalar_row("range_e", &run.range_e);
