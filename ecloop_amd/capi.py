@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("ECLOOP_HIP_LIB") or os.path.join(PKG, "libecloop_hip.
 
 ADDR33, ADDR65, ENDO, P2SH = 1, 2, 4, 16
 E_OVERFLOW = -4
+E_COVERAGE = -8  # the device did not hash every key of the call (include/ecloop_hip.h, section 1)
 
 U64x4 = C.c_uint64 * 4
 
@@ -35,14 +36,19 @@ EXPORTS = [
     "ecl_hip_mul_batch", "ecl_hip_bloom_insert", "ecl_hip_get_bloom", "ecl_hip_set_geometry", "ecl_hip_get_geometry", "ecl_hip_get_timing", "ecl_hip_reset_timing", "ecl_hip_selftest", "ecl_hip_strerror",
     "ecl_hip_last_error", "ecl_hip_diag_fe", "ecl_hip_diag_mulg", "ecl_hip_diag_hash160", "ecl_hip_diag_bloom", "ecl_hip_diag_bloom_mod", "ecl_hip_set_lookahead", "ecl_hip_set_scan_end", "ecl_hip_get_lookahead_stats",
     "ecl_hip_get_setup_timing", "ecl_hip_get_mul_timing", "ecl_hip_bloom_insert_count", "ecl_hip_alloc_host", "ecl_hip_free_host", "ecl_hip_verify", "ecl_hip_sort_list", "ecl_hip_reserve_mul", "ecl_hip_mul_batch_raw", "ecl_hip_set_mul_window", "ecl_hip_get_mul_window", "ecl_hip_fetch_found", "ecl_hip_plan_geometry",
-    "ecl_hip_p2sh_hash",
+    "ecl_hip_p2sh_hash", "ecl_hip_get_coverage", "ecl_hip_diag_drop_round",
 ]
 
 _lib = None
 
 
 class EclError(RuntimeError):
-    pass
+    """a failed library call; `code` is its return code (ECL_E_*: E_COVERAGE for a call whose keys were not all hashed), None when the
+    failure is not a return code"""
+
+    def __init__(self, msg, code=None):
+        super().__init__(msg)
+        self.code = code
 
 
 def load():
@@ -74,6 +80,8 @@ def load():
     lib.ecl_hip_reset_timing.argtypes = [P]
     lib.ecl_hip_get_setup_timing.argtypes = [P, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     lib.ecl_hip_get_mul_timing.argtypes = [P, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.ecl_hip_get_coverage.argtypes = [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.ecl_hip_diag_drop_round.argtypes = [P]
     lib.ecl_hip_set_lookahead.argtypes = [P, C.c_uint64]
     lib.ecl_hip_set_scan_end.argtypes = [P, C.c_void_p]
     lib.ecl_hip_get_lookahead_stats.argtypes = [P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -129,11 +137,11 @@ class Device:
             if self.h:
                 self.lib.ecl_hip_close(self.h)
                 self.h = None
-            raise EclError(f"ecl_hip_open(device={device}): {self.lib.ecl_hip_strerror(rc).decode()} {msg}")
+            raise EclError(f"ecl_hip_open(device={device}): {self.lib.ecl_hip_strerror(rc).decode()} {msg}", rc)
 
     def _chk(self, rc, allow=()):
         if rc != 0 and rc not in allow:
-            raise EclError(f"{self.lib.ecl_hip_strerror(rc).decode()}: {self.lib.ecl_hip_last_error(self.h).decode()}")
+            raise EclError(f"{self.lib.ecl_hip_strerror(rc).decode()}: {self.lib.ecl_hip_last_error(self.h).decode()}", rc)
         return rc
 
     def close(self):
@@ -284,6 +292,17 @@ class Device:
         ms, launches, keys = C.c_double(), C.c_uint64(), C.c_uint64()
         self._chk(self.lib.ecl_hip_get_timing(self.h, C.byref(ms), C.byref(launches), C.byref(keys)))
         return ms.value, launches.value, keys.value
+
+    def coverage(self):
+        """-> (requested, covered, device): keys / scalars of the calls since open, those whose device count was checked whole, and the
+        keys this context's kernels counted (look-ahead sweeps whole); requested == covered on a sound device"""
+        v = [C.c_uint64() for _ in range(3)]
+        self._chk(self.lib.ecl_hip_get_coverage(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def diag_drop_round(self):
+        """test hook: the next search launch runs one round short, so that the call fails with EclError(code=E_COVERAGE)"""
+        self._chk(self.lib.ecl_hip_diag_drop_round(self.h))
 
     def reset_timing(self):
         self._chk(self.lib.ecl_hip_reset_timing(self.h))

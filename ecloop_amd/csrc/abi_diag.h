@@ -161,6 +161,15 @@ extern "C" int ecl_hip_diag_bloom_mod(ecl_hip* h, uint64_t nwords, const uint64_
   return ECL_OK;
 }
 
+// test hook of the key-coverage check: the next search launch (add_range, a look-ahead sweep, or the first piece of a mul call) runs one
+// round short - the add kernel one group per lane fewer, the mul kernel one scalar per thread fewer - so that keys of the call are not
+// hashed and the call has to fail with ECL_E_COVERAGE.  Only a loop bound shrinks: the launch touches a part of what it touches anyway.
+extern "C" int ecl_hip_diag_drop_round(ecl_hip* h) {
+  if (!h) return ECL_E_ARG;
+  h->diag_drop = true;
+  return ECL_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ self-test
 
 extern "C" int ecl_hip_selftest(ecl_hip* h) {
@@ -189,6 +198,7 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   }
   // (2) the walk kernel against the double-and-add kernel: 4096 consecutive keys through an all-ones filter
   const u32 N = 4096, saveB = h->B, saveT = h->Tmax;
+  const uint64_t save_cov[3] = {h->cov_requested, h->cov_covered, h->cov_device};  // the caller's totals: "since open" leaves this call out
   const bool saveAuto = h->B_auto;
   u64* save_bloom = h->d_bloom;
   const u64 save_words = h->bloom_words, save_list_n = h->list_n;
@@ -224,6 +234,7 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   if (h->d_tab) (void)hipFree(h->d_tab);
   h->d_tab = nullptr, h->tab_B = 0, h->walk_valid = false;
   h->kernel_ms = 0, h->launches = 0, h->keys = 0, h->setup_ms = 0, h->setups = 0;
+  h->cov_requested = save_cov[0], h->cov_covered = save_cov[1], h->cov_device = save_cov[2];
   if (rc != ECL_OK) return rc;
   u32 seen = 0;
   bool good = n == cap;

@@ -10,7 +10,8 @@
 //
 // What is guaranteed.  A call is answered from a sweep only if all of its keys lie inside the sweep; it receives exactly the records
 // whose key offset falls into its own range, re-based to its own start - the same set a launch of its own would report (same kernel,
-// same filter, same flags; the order of records within a call was never specified: the device appends them with atomicAdd).  A sweep
+// same filter, same flags; the order of records within a call was never specified: the device appends them with atomicAdd), and only
+// from a sweep whose kernels counted every one of its keys (ECL_E_COVERAGE otherwise, to the job that ran it).  A sweep
 // whose records do not fit (more than 2^20 hits: a dense filter) is dropped and the pattern is left alone until it changes; a caller
 // whose density of hits is known from its earlier calls gets sweeps sized to about 2^16 records.  Anything else - a job that does not
 // continue the pattern, a caller-set geometry, a filter changed by ecl_hip_bloom_insert - takes the plain launch, as before.
@@ -216,8 +217,10 @@ static bool la_may_sweep(const ecl_hip* h, const la_group& g) {
   return it == g.sweeper.end() || it->second == h;
 }
 
-// claims [at, at + L) for this context, runs it, publishes it.  Called and left with the group's lock held.
-static bool la_claim_and_sweep(ecl_hip* h, la_group& g, std::unique_lock<std::mutex>& lk, const u256& at, u64 L) {
+// claims [at, at + L) for this context, runs it, publishes it; returns the sweep's result.  Called and left with the group's lock held.
+// A sweep that failed is never published, whatever the reason; one whose device count fell short of its keys (ECL_E_COVERAGE) is reported
+// to the caller of the job that ran it - answering that job with a plain launch instead would hide a device that skips keys.
+static int la_claim_and_sweep(ecl_hip* h, la_group& g, std::unique_lock<std::mutex>& lk, const u256& at, u64 L) {
   g.sweeper[h->dev] = h;
   auto r = std::make_shared<la_region>();
   r->start = at, r->nkeys = L, r->dev = h->dev;
@@ -230,7 +233,7 @@ static bool la_claim_and_sweep(ecl_hip* h, la_group& g, std::unique_lock<std::mu
     r->ready = true;
     g.hits += (double)r->recs.size(), g.keys += (double)L;
     while (g.regions.size() > (size_t)(2 * g.members + 2) && g.regions.front()->ready) g.regions.pop_front();  // stretches nobody came back for
-  } else {  // too dense, a scan through the scalar 0, out of memory ...: this pattern goes on with plain launches
+  } else {  // too dense, a scan through the scalar 0, out of memory, keys not hashed ...: this pattern goes on with plain launches
     for (auto it = g.regions.begin(); it != g.regions.end(); ++it)
       if (it->get() == r.get()) {
         g.regions.erase(it);
@@ -240,7 +243,7 @@ static bool la_claim_and_sweep(ecl_hip* h, la_group& g, std::unique_lock<std::mu
     (void)hipGetLastError();
   }
   g.cv.notify_all();
-  return rc == ECL_OK;
+  return rc;
 }
 
 static int la_fetch(ecl_hip* h, uint32_t first, ecl_found* out, uint32_t n, uint32_t* got) {
@@ -302,7 +305,7 @@ static int la_add_range(ecl_hip* h, const u256& k0, u64 n, ecl_found* out, u32 c
       const u64 L = (!mine_busy && !crowded && !g.blocked && g.pat && n == g.job_n && la_may_sweep(h, g)) ? la_plan(h, g, g.next, n) : 0;
       if (L) {
         const u256 at = g.next;
-        (void)la_claim_and_sweep(h, g, lk, at, L);
+        if (la_claim_and_sweep(h, g, lk, at, L) == ECL_E_COVERAGE) return ECL_E_COVERAGE;
       } else {
         g.cv.wait(lk);
       }
@@ -332,7 +335,9 @@ static int la_add_range(ecl_hip* h, const u256& k0, u64 n, ecl_found* out, u32 c
       g.next = la_advance(h, k0, n);
       return ECL_OK;
     }
-    if (!la_claim_and_sweep(h, g, lk, k0, L)) {
+    const int src = la_claim_and_sweep(h, g, lk, k0, L);
+    if (src == ECL_E_COVERAGE) return ECL_E_COVERAGE;  // (the job is not done: the pattern expects it again, g.next = k0)
+    if (src != ECL_OK) {
       g.next = la_advance(h, k0, n);
       return ECL_OK;
     }

@@ -205,12 +205,14 @@ static void mul_geometry(u32 m, u32* R_out, u32* nt_out) {
   R = R < 1 ? 1 : (R > MUL_R ? MUL_R : R);
   *R_out = R, *nt_out = ((m + R - 1) / R + 255u) / 256u * 256u;
 }
-// one piece on compute stream `lane` (0: the context's stream, 1: the second one), parking space `lane`
-static void mul_launch_piece(ecl_hip* h, int lane, const u32* d_k, u32 m, u32 at, const wtab& gtab, const add_args& a) {
+// one piece on compute stream `lane` (0: the context's stream, 1: the second one), parking space `lane`; short_round: one scalar per
+// thread fewer (the test hook ecl_hip_diag_drop_round - (R - 1) * nt < m, so the last round always holds scalars)
+static void mul_launch_piece(ecl_hip* h, int lane, const u32* d_k, u32 m, u32 at, const wtab& gtab, const add_args& a, bool short_round) {
   u32 R, nt;
   hipStream_t st = lane ? h->stream2 : h->stream;
   u32* tmp = h->d_multmp[lane];
   mul_geometry(m, &R, &nt);
+  if (short_round) R -= 1;
   dim3 grid(nt / 256), blk(256);
   switch (h->flags & (ECL_ADDR33 | ECL_ADDR65 | ECL_P2SH)) {  // every non-empty set of address types
   case ECL_ADDR33: hipLaunchKernelGGL((k_mul_check<true, false>), grid, blk, 0, st, d_k, m, at, gtab, a, tmp, nt, R); break;
@@ -264,6 +266,8 @@ template <class CopyIn, class Prepare> static int mul_pieces(ecl_hip* h, u32 n, 
   const u64 top_want = unit * (n >= (1u << 26) ? 12u : 10u);
   const u32 top = h->kbuf_cap < top_want ? h->kbuf_cap : (u32)top_want;
   u32 lim = top < unit ? top : (u32)unit;
+  const bool drop = h->diag_drop;
+  h->diag_drop = false;
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));
   HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));  // the second stream starts behind the counters' reset (and behind the call before)
   HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
@@ -281,7 +285,7 @@ template <class CopyIn, class Prepare> static int mul_pieces(ecl_hip* h, u32 n, 
     hipEvent_t ready = h->ev_copied[b];
     if (int rc = prepare(b, at, m, &ready)) return rc;
     HIPCHK(h, hipStreamWaitEvent(st, ready, 0));
-    mul_launch_piece(h, lane, h->d_kbuf[b], m, at, gtab, a);
+    mul_launch_piece(h, lane, h->d_kbuf[b], m, at, gtab, a, drop && c == 0);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->ev_free[b], st));
   }
@@ -344,8 +348,8 @@ extern "C" int ecl_hip_mul_batch(ecl_hip* h, const uint64_t (*scalars)[4], uint3
   add_args a;
   memset(&a, 0, sizeof a);
   a.bloom = bloom_make(h->d_bloom, h->bloom_words);
-  a.found = h->d_found, a.counter = h->d_counter, a.cap = rcap;
-  HIPCHK(h, hipMemsetAsync(h->d_counter, 0, 2 * sizeof(u32), h->stream));
+  a.found = h->d_found, a.counter = h->d_counter, a.cap = rcap, a.keys = (unsigned long long*)(h->d_counter + 4);
+  HIPCHK(h, hipMemsetAsync(h->d_counter, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
   // Scalars are used as given (4 little-endian u64 = 8 u32 words): the window sum (wtab_sum_fast, any width) is k*G for any
   // 256-bit k, which is (k mod n)*G; k = 0 (mod n) gives the point at infinity and is skipped.
   const bool staged = !direct;
@@ -367,8 +371,9 @@ extern "C" int ecl_hip_mul_batch(ecl_hip* h, const uint64_t (*scalars)[4], uint3
     float ms = 0;
     HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));  // copies + kernels of this call, as the stream saw them
     h->mul_ms += ms, h->mul_calls += 1, h->mul_scalars += n;
+    rc = check_coverage(h, "mul_batch", n, rc, nout);  // the counts of all pieces, summed on the device
   }
-  return rc;
+  return count_call(h, n, rc);
 }
 
 // `mul -raw`: lines of text in, SHA-256 on the device, then the `mul` body on the digests (n <= 2^26 lines a call): the pieces of
@@ -427,7 +432,7 @@ extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t t
   add_args a;
   memset(&a, 0, sizeof a);
   a.bloom = bloom_make(h->d_bloom, h->bloom_words);
-  a.found = h->d_found, a.counter = h->d_counter, a.cap = rcap;
+  a.found = h->d_found, a.counter = h->d_counter, a.cap = rcap, a.keys = (unsigned long long*)(h->d_counter + 4);
   u64* d_lines = h->d_rawlines;
   u32* d_flags = h->d_counter + 2;  // [0] a line outside the text, [1] a line beyond the part of the text that was on the device when it was hashed
   u32* d_text = h->d_rawtext;
@@ -437,9 +442,11 @@ extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t t
   // a 20 ms call).  The kernel checks it line by line; a table in another order raises flag [1], and the call is run again with the
   // whole text sent first.  Page-locked text and table (ecl_hip_alloc_host) go by DMA from where they are.
   u32 flags[2] = {0, 0}, cnt = 0;
+  bool missed = false;  // a pass whose device count differs from n: the call fails even if a second pass was whole
+  u64 missed_got = 0;
   for (int pass = 0; pass < 2; ++pass) {
     const bool in_order = pass == 0;
-    HIPCHK(h, hipMemsetAsync(h->d_counter, 0, 4 * sizeof(u32), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->d_counter, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
     HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));  // the hashing writes the flags: behind their reset
     HIPCHK(h, hipStreamWaitEvent(h->prep_stream, h->ev_fork, 0));
     u32 have = 0;  // bytes of the text on the copy stream so far
@@ -473,6 +480,9 @@ extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t t
     rc = collect_found(h, cap, rcap, out, &cnt, false);  // (the one wait of the call; the flags come back with the counters)
     if (rc != ECL_OK && rc != ECL_E_OVERFLOW) return rc;
     flags[0] = h->pin_counter[2], flags[1] = h->pin_counter[3];
+    const u64 got = counted_keys(h);
+    h->cov_device += got;
+    if (got != n && !missed) missed = true, missed_got = got;
     if (flags[0] || !flags[1]) break;
   }
   if (flags[0]) {
@@ -485,8 +495,9 @@ extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t t
     float ms = 0;
     HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
     h->mul_ms += ms, h->mul_calls += 1, h->mul_scalars += n;
+    if (missed) rc = coverage_failed(h, "mul_batch_raw", n, missed_got, nout);
   }
-  return rc;
+  return count_call(h, n, rc);
 }
 
 extern "C" int ecl_hip_verify(ecl_hip* h, const uint64_t (*k)[4], uint32_t n, uint32_t (*h33)[5], uint32_t (*h65)[5], uint8_t* ok) {

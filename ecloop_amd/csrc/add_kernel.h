@@ -43,6 +43,7 @@ struct add_args {
   u32 T;      // lanes
   u32 nb;     // groups per lane in this launch
   u64 nkeys;  // keys with offset >= nkeys are not tested
+  unsigned long long* keys;  // the call's key count (cand_queues::keys): each wave adds what reached check_point, once, at its end
 };
 
 // canonical words in two uint4 planes <-> fe
@@ -162,9 +163,18 @@ __device__ __forceinline__ cand_rec cand_take(cand_queue& q, bool& valid) {
 // the middle stage (probes 1-2: 14 % of A; one probe for multi-GB filters: 37 %).  A is drained 64 at a time without
 // a loop; only B runs the remaining probes with the early-out loop, where the wave iterates until its slowest lane
 // is done.  Per hash and wave: 68 VALU instructions for the whole filter test instead of 96 with one ring.
+// keys: the keys of the call that this wave has brought to check_point (live lanes), wave-uniform, so it lives in SGPRs: per key a bit
+// count of the compare mask the range test already produced and a 64-bit add, on the scalar unit.  keys_flush hands it to the call's
+// counter at the end of the wave; the host compares the sum with the keys it asked for (ECL_E_COVERAGE)
 struct cand_queues {
   cand_queue a, b;
+  u64 keys;
 };
+__device__ __forceinline__ void keys_count(cand_queues& q, bool live) { q.keys += (u64)__builtin_popcountll(__builtin_amdgcn_ballot_w64(live)); }
+// one vector atomic per wave and launch (lane 0; every lane of the wave reaches the end of both kernels)
+__device__ __forceinline__ void keys_flush(const add_args& a, const cand_queues& q) {
+  if ((threadIdx.x & 63u) == 0) atomicAdd(a.keys, (unsigned long long)q.keys);
+}
 // P2SH: the kernel reports the address type 2 as well, so the type byte of a parked record keeps two bits instead of one
 template <bool P2SH>
 __device__ __forceinline__ void cand_finish(const add_args& a, cand_queue& qb) {  // up to 64 records of ring B

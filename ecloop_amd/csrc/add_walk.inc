@@ -8,9 +8,10 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
   cand_queues q;
   q.a.mem = q_mem[threadIdx.x >> 6][0], q.a.head = 0, q.a.count = 0;
   q.b.mem = q_mem[threadIdx.x >> 6][1], q.b.head = 0, q.b.count = 0;
+  q.keys = 0;
   const u32 g = blockIdx.x * (u32)ECL_ADD_BLOCK + threadIdx.x;
   const u32 T = a.T, B = a.B;
-  if (g >= T) return;
+  if (g >= T) return;  // (never taken: T is a multiple of the block size)
   const size_t plane = T;
   // centre (X, Y): canonical in HBM, magnitude 1 in registers
   fe X = fe_ld_words2(a.cxy + g, plane), Y = fe_ld_words2(a.cxy + 2 * (size_t)T + g, plane);
@@ -81,7 +82,11 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
             FE_HIDE24(py.n[l]);
           }
         }
-        if (valid) check_point<A33, A65, P2SH, ENDO>(a, &q, off < a.nkeys, px, py, off);
+        if (valid) {
+          const bool live = off < a.nkeys;
+          keys_count(q, live);
+          check_point<A33, A65, P2SH, ENDO>(a, &q, live, px, py, off);
+        }
       }
     }
     // ---- next centre: C + J with 1/(Jx - X) = inv (or the tangent if C == J)
@@ -99,6 +104,7 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
     X = Xn, Y = Yn;
   }
   cand_flush<P2SH>(a, q);
+  keys_flush(a, q);
   fe_st_words2(a.cxy + g, plane, X);
   fe_st_words2(a.cxy + 2 * (size_t)T + g, plane, Y);
 }

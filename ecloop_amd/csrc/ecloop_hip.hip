@@ -28,6 +28,8 @@
 
 // ------------------------------------------------------------------------------------------------ context
 
+#define ECL_COUNTER_WORDS 6u  /* d_counter: see ecl_hip_open */
+
 struct ecl_hip {
   int dev = 0;
   u32 flags = 0, offs = 0;
@@ -62,6 +64,10 @@ struct ecl_hip {
   u32* d_list = nullptr; u64 list_n = 0;       // optional sorted hash list (exact confirm on the device)
   ecl_found_dev* d_found = nullptr; u32 found_cap = 0;
   u32* d_counter = nullptr; u32* pin_counter = nullptr;  // (the counters' page-locked host copy: read back by the copy engine, no compute slot needed)
+  // key coverage (ecl_hip_get_coverage): keys / scalars of the calls that launched or were served from a sweep, those of them whose device
+  // count matched, and the keys the kernels of this context's launches counted; never reset
+  uint64_t cov_requested = 0, cov_covered = 0, cov_device = 0;
+  bool diag_drop = false;  // ecl_hip_diag_drop_round: the next search launch runs one round short
   // records of the last add_range / mul_batch call that are still on the device (ecl_hip_fetch_found): where they start in d_found,
   // how many the device holds, the call's total, and whether the endo byte is meaningful
   u32 last_at = 0, last_held = 0, last_total = 0; bool last_endo = false;
@@ -122,6 +128,7 @@ const char* ecl_hip_strerror(int code) {
   case ECL_E_NOBLOOM: return "no bloom filter set";
   case ECL_E_RANGE: return "range touches scalar 0 (mod n)";
   case ECL_E_SELFTEST: return "device self-test failed";
+  case ECL_E_COVERAGE: return "the device did not hash every key of the call";
   default: return "unknown error";
   }
 }
@@ -143,8 +150,9 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   HIPCHK(h, hipEventCreate(&h->ev_s1));
   HIPCHK(h, hipMalloc(&h->d_aux, 34 * 16 * sizeof(u32)));
   HIPCHK(h, hipMalloc(&h->d_auxk, 34 * 8 * sizeof(u32)));
-  HIPCHK(h, hipMalloc(&h->d_counter, 4 * sizeof(u32)));  // [0] records appended, [1] records confirmed by the list, [2] [3] input flags of mul_batch_raw
-  HIPCHK(h, hipHostMalloc((void**)&h->pin_counter, 4 * sizeof(u32), hipHostMallocDefault));
+  // [0] records appended, [1] records confirmed by the list, [2] [3] input flags of mul_batch_raw, [4] [5] the u64 count of keys hashed
+  HIPCHK(h, hipMalloc(&h->d_counter, ECL_COUNTER_WORDS * sizeof(u32)));
+  HIPCHK(h, hipHostMalloc((void**)&h->pin_counter, ECL_COUNTER_WORDS * sizeof(u32), hipHostMallocDefault));
   // the self-test checks the CODE (known answers, walk kernel against the double-and-add kernel): once per process
   // for every (device, kernel selection) is enough - eight handles for eight shards of one scan do not repeat it
   static std::mutex mu;
@@ -363,6 +371,13 @@ int ecl_hip_get_timing(ecl_hip* h, double* kernel_ms, uint64_t* launches, uint64
   if (keys) *keys = h->keys;
   return ECL_OK;
 }
+int ecl_hip_get_coverage(ecl_hip* h, uint64_t* requested, uint64_t* covered, uint64_t* device_keys) {
+  if (!h) return ECL_E_ARG;
+  if (requested) *requested = h->cov_requested;
+  if (covered) *covered = h->cov_covered;
+  if (device_keys) *device_keys = h->cov_device;
+  return ECL_OK;
+}
 int ecl_hip_reset_timing(ecl_hip* h) {
   if (!h) return ECL_E_ARG;
   h->kernel_ms = 0, h->launches = 0, h->keys = 0, h->setup_ms = 0, h->setups = 0;
@@ -433,9 +448,10 @@ static int collect_found(ecl_hip* h, u32 cap, u32 rcap, ecl_found* out, u32* nou
   }
   // One read-back and one wait per call, into page-locked memory: a copy into pageable memory goes through a staging kernel, and with
   // a second context's k_mul_check launches filling the chip every small kernel waits milliseconds for a slot (each such wait at the
-  // end of a `mul` call is time this context has nothing in flight).  All four words: mul_batch_raw reads its flags from the same copy.
+  // end of a `mul` call is time this context has nothing in flight).  All the words: mul_batch_raw reads its flags from the same copy, and
+  // every caller the count of keys hashed (counted_keys).
   u32* cnts = h->pin_counter;
-  HIPCHK(h, hipMemcpyAsync(cnts, h->d_counter, 4 * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(cnts, h->d_counter, ECL_COUNTER_WORDS * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   const u32 cnt = lst ? cnts[1] : cnts[0];
   const u32 take = cnt < cap ? cnt : cap;
@@ -453,6 +469,32 @@ static int collect_found(ecl_hip* h, u32 cap, u32 rcap, ecl_found* out, u32* nou
     return ECL_E_OVERFLOW;
   }
   return cnt > cap ? ECL_E_OVERFLOW : ECL_OK;
+}
+
+// Key coverage.  Every launch of a search kernel counts, on the device, the keys that reach the hash-and-probe step inside its range
+// (add_kernel.h: keys_count / keys_flush) into the u64 at d_counter + 4, which the one read-back of collect_found brings home.  A call whose
+// count differs from the keys it asked for returns ECL_E_COVERAGE: no records, nothing to fetch, and the resident walk is dropped.
+static u64 counted_keys(const ecl_hip* h) { return (u64)h->pin_counter[4] | (u64)h->pin_counter[5] << 32; }
+static int coverage_failed(ecl_hip* h, const char* what, u64 want, u64 got, u32* nout) {
+  char msg[160];
+  snprintf(msg, sizeof msg, "%s: the device hashed %llu keys of the %llu asked for", what, (unsigned long long)got, (unsigned long long)want);
+  h->err = msg;
+  h->walk_valid = false, h->last_held = h->last_total = 0, h->last_from_host = false;
+  *nout = 0;
+  return ECL_E_COVERAGE;
+}
+// after collect_found: the launch's device count against `want` (rc: collect_found's result, ECL_OK or ECL_E_OVERFLOW)
+static int check_coverage(ecl_hip* h, const char* what, u64 want, int rc, u32* nout) {
+  const u64 got = counted_keys(h);
+  h->cov_device += got;
+  return got == want ? rc : coverage_failed(h, what, want, got, nout);
+}
+// the totals of ecl_hip_get_coverage for one add / mul call, by its result: a call that returns ECL_OK / ECL_E_OVERFLOW was launched or served
+// and counted whole; one that returns ECL_E_COVERAGE was launched and not
+static int count_call(ecl_hip* h, u64 n, int rc) {
+  if (rc == ECL_OK || rc == ECL_E_OVERFLOW || rc == ECL_E_COVERAGE) h->cov_requested += n;
+  if (rc == ECL_OK || rc == ECL_E_OVERFLOW) h->cov_covered += n;
+  return rc;
 }
 
 static int la_fetch(ecl_hip* h, uint32_t first, ecl_found* out, uint32_t n, uint32_t* got);
@@ -730,9 +772,10 @@ static int add_core(ecl_hip* h, const u256& k0, uint64_t nkeys, ecl_found* out, 
   memcpy(a.jump, h->jump_host, sizeof a.jump);
   a.cxy = h->d_cxy, a.scratch = h->d_scr, a.scratch2 = h->d_scr2;
   a.bloom = bloom_make(h->d_bloom, h->bloom_words);
-  a.found = h->d_found, a.counter = h->d_counter, a.cap = rcap;
+  a.found = h->d_found, a.counter = h->d_counter, a.cap = rcap, a.keys = (unsigned long long*)(h->d_counter + 4);
   a.B = B, a.T = T, a.nb = nb, a.nkeys = nkeys;
-  HIPCHK(h, hipMemsetAsync(h->d_counter, 0, 2 * sizeof(u32), h->stream));
+  if (h->diag_drop) h->diag_drop = false, a.nb = nb - 1;  // (test hook: lane 0's last group is in the range, so keys go missing)
+  HIPCHK(h, hipMemsetAsync(h->d_counter, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));
   hipLaunchKernelGGL(pick_add_kernel(h->flags), dim3(T / ECL_ADD_BLOCK), dim3(ECL_ADD_BLOCK), 0, h->stream, a);
   HIPCHK(h, hipGetLastError());
@@ -747,6 +790,7 @@ static int add_core(ecl_hip* h, const u256& k0, uint64_t nkeys, ecl_found* out, 
     HIPCHK(h, hipEventElapsedTime(&ms, h->ev_s0, h->ev_s1));
     h->setup_ms += ms, h->setups += 1;
   }
+  if (check_coverage(h, "add_range", nkeys, rc, nout) == ECL_E_COVERAGE) return ECL_E_COVERAGE;
 
   // the centres now sit at the start of group nb*T + g: valid continuation only if the launch was exact
   const u64 walked = (u64)nb * T * group;
@@ -792,7 +836,7 @@ extern "C" int ecl_hip_add_range(ecl_hip* h, const uint64_t start[4], uint64_t n
   if (!h->d_bloom) return ECL_E_NOBLOOM;
   if (nkeys == 0) return ECL_OK;
   HIPCHK(h, hipSetDevice(h->dev));
-  return la_dispatch(h, sc_reduce(u256_from(start)), nkeys, out, cap, nout);
+  return count_call(h, nkeys, la_dispatch(h, sc_reduce(u256_from(start)), nkeys, out, cap, nout));
 }
 
 #include "abi_mul.h"

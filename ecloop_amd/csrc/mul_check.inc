@@ -48,6 +48,7 @@ __global__ void __launch_bounds__(256, ECL_MUL_WAVES) ECL_MUL_KERNEL(const u32* 
   cand_queues q;
   q.a.mem = q_mem[threadIdx.x >> 6][0], q.a.head = 0, q.a.count = 0;
   q.b.mem = q_mem[threadIdx.x >> 6][1], q.b.head = 0, q.b.count = 0;
+  q.keys = 0;
 #pragma unroll 1
   for (u32 r = R; r-- > 0;) {
     const u32 i = r * nt + t;
@@ -63,7 +64,9 @@ __global__ void __launch_bounds__(256, ECL_MUL_WAVES) ECL_MUL_KERNEL(const u32* 
     fe_mul_pair(ti, ninv, inv, pre, inv, T);  // T = 1 for a lane without a scalar in this round
     inv = ninv;
     fe_mul_pair(x, y, X, ti, Y, ti);
+    keys_count(q, have);  // a scalar whose point is at infinity counts: it has nothing to hash
     check_point<A33, A65, P2SH, false>(a, &q, have && !((infmask >> r) & 1u), x, y, (u64)base + i);
   }
   cand_flush<P2SH>(a, q);
+  keys_flush(a, q);
 }

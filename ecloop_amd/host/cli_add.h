@@ -205,6 +205,10 @@ static void print_device_stats(run_t *run) {
     printf("gpu %d: %llu launches, %.3f ms in the search kernel, %llu set-ups, %.3f ms in set-up kernels (%.2f %%)\n", g,
            (unsigned long long)launches, kernel_ms, (unsigned long long)setups, setup_ms,
            kernel_ms > 0 ? 100.0 * setup_ms / (kernel_ms + setup_ms) : 0.0);
+    u64 requested = 0, covered = 0, device = 0;
+    ecl_hip_get_coverage(run->dev[g], &requested, &covered, &device);
+    printf("gpu %d coverage: requested %llu, covered %llu, device %llu\n", g, (unsigned long long)requested, (unsigned long long)covered,
+           (unsigned long long)device);
   }
 }
 

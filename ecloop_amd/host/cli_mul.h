@@ -1042,6 +1042,10 @@ static void cmd_mul(run_t *run) {
       ecl_hip_get_mul_timing(run->dev[g], &ms, &calls, &n);
       fprintf(stderr, "mul context %d: %llu arrays, %llu scalars, %.1f ms in device calls (%.1f ms by the library's events over %llu calls), %.1f ms waiting for parsed input\n", g,
               (unsigned long long)dargs[g].calls, (unsigned long long)dargs[g].scalars, dargs[g].busy_us / 1e3, ms, (unsigned long long)calls, dargs[g].wait_us / 1e3);
+      uint64_t requested = 0, covered = 0, device = 0;
+      ecl_hip_get_coverage(run->dev[g], &requested, &covered, &device);
+      fprintf(stderr, "mul context %d coverage: requested %llu, covered %llu, device %llu\n", g, (unsigned long long)requested,
+              (unsigned long long)covered, (unsigned long long)device);
     }
   if (getenv("ECLOOP_HIP_STATS")) /* where the front end's wall time went (the main thread drives one chunk at a time) */
     fprintf(stderr, "mul front end: %llu batches of fixed records straight from the file (%llu lines), %llu chunks (%llu of fixed 65-byte records), %d pool threads; ms waiting for text %.1f, "

@@ -103,9 +103,18 @@ typedef struct run_t {
   u32 ord_offs, ord_size;
 } run_t;
 
+/* A failed library call ends the run.  Device threads can fail at the same time (`mul`'s two contexts of a GPU): the first one reports and
+   ends the process, the others wait here - two threads in exit() at once, or the HIP runtime's teardown under another thread's calls,
+   crash the process instead of ending it with status 1.  _exit runs no atexit handlers: the streams and the terminal (cli_keys.h) are
+   seen to here. */
+static void keys_restore(void);
 static void die_ecl(run_t *run, int g, int rc, const char *what) {
+  static pthread_mutex_t once = PTHREAD_MUTEX_INITIALIZER;
+  pthread_mutex_lock(&once);
   fprintf(stderr, "\n[!] %s: %s (%s)\n", what, ecl_hip_strerror(rc), run->dev[g] ? ecl_hip_last_error(run->dev[g]) : "");
-  exit(1);
+  fflush(NULL);
+  keys_restore();
+  _exit(1);
 }
 /* pk_verify_hash (main.c:248-263) for all hits of one device call at once: both hash160 values of every reported key are
    derived again on the device by the window-table sum (ecl_hip_verify: not the walk kernel; own inversion per key) and

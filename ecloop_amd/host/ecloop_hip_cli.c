@@ -213,6 +213,14 @@ int main(int argc, const char **argv) {
   int shown = (int)(asked < 1 ? 1 : asked > (u64)usable ? (u64)usable : asked);
   if (shown > MAX_GPUS) shown = MAX_GPUS;
   const double setup_s = bring_up(&run, shown, real);
+  /* test hook: ECLOOP_HIP_TEST_DROP_ROUND=1 makes the first search launch of every context run one round short (ecl_hip_diag_drop_round),
+     so that the key-coverage check of the library has to stop the run (exit status 1, ECL_E_COVERAGE on stderr) whichever context the
+     first work goes to (`mul`: either of a GPU's two) */
+  const char *drop = getenv("ECLOOP_HIP_TEST_DROP_ROUND");
+  for (int g = 0; drop && drop[0] == '1' && g < run.ngpus; ++g) {
+    const int rc = ecl_hip_diag_drop_round(run.dev[g]);
+    if (rc != ECL_OK) die_ecl(&run, g, rc, "drop_round");
+  }
 
   printf("gpus: %d ~ addr33: %d ~ addr65: %d ~ endo: %d%s | filter: ", shown, run.a33, run.a65, run.endo, run.p2sh ? " ~ p2sh: 1" : "");
   if (run.flt.list) printf("list (%'llu)\n", (unsigned long long)run.flt.nlist);

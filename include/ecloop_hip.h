@@ -33,7 +33,7 @@
  * section 3 (sweeps and their records belong to the group of contexts that share a filter; one mutex per group; records are immutable
  * once published).  ecl_hip_strerror returns static text; ecl_hip_last_error returns the handle's own buffer (same thread rule).
  *
- * Exports: exactly the ecl_hip_* functions declared below (the library is linked with a version script; `nm -D` shows nothing else).
+ * Exports: exactly the 41 ecl_hip_* functions declared below (the library is linked with a version script; `nm -D` shows nothing else).
  */
 #ifndef ECLOOP_HIP_H
 #define ECLOOP_HIP_H
@@ -66,6 +66,7 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
 #define ECL_E_NOBLOOM (-5)  /* add/mul called before ecl_hip_set_bloom */
 #define ECL_E_RANGE (-6)    /* range touches the scalar 0 (mod n) neighbourhood the method cannot represent */
 #define ECL_E_SELFTEST (-7) /* the device code failed its known-answer / cross-path self-test (miscompile, bad GPU) */
+#define ECL_E_COVERAGE (-8) /* the device did not hash every key of the call (section 1): no records, the call has to be repeated */
 
 /* One bloom-filter hit.  key_offset counts keys from the `start` scalar of the call in units of the stride:
    privkey = start + key_offset * 2^ord_offs (mod n), then the endo map of calc_priv (main.c:267-276):
@@ -84,7 +85,14 @@ typedef struct ecl_found {
    device_count / open / set_bloom / add_range / mul_batch / close replace the reference's calls listed above; fetch_found serves a call
    whose hits did not fit the caller's buffer; strerror / last_error give the text of a failure.  Everything after this section is
    optional: a caller that uses nothing else gets the full search path, at the library's rate (the look-ahead of section 3 is on by
-   default). */
+   default).
+   Key coverage.  The kernels count, on the device, the keys (add) and scalars (mul) that reach the hash-and-probe step, and every
+   add_range / mul_batch / mul_batch_raw call compares that count with what it asked for.  A call whose count differs returns
+   ECL_E_COVERAGE (-8): *nout = 0, nothing is left for fetch_found, and the context re-positions its walk on the next call.  A call
+   answered from a look-ahead sweep is covered by that sweep's count; a sweep that miscounts is never used, and the call that ran it
+   returns ECL_E_COVERAGE.  The reference cannot tell that a key was never hashed (pk_verify_hash, main.c:248-263, only re-derives the
+   hits that were reported), so a binding that treats every non-OK return as fatal - as the reference's own call sites do - stops here:
+   that is the point.  On a sound device the code never occurs; ecl_hip_get_coverage (section 4) gives the totals. */
 int ecl_hip_device_count(void);
 
 /* Create a context on `device`. ord_offs: stride between consecutive keys is 2^ord_offs (0..255, main.c:221-222).
@@ -251,6 +259,11 @@ int ecl_hip_get_setup_timing(ecl_hip *h, double *setup_ms, uint64_t *setups);
 /* ... of ecl_hip_mul_batch: HIP-event time from the first chunk's copy being awaited to the last kernel (host->device
    copies overlapped with the kernels), calls and scalars since the last reset. */
 int ecl_hip_get_mul_timing(ecl_hip *h, double *ms, uint64_t *calls, uint64_t *scalars);
+/* Coverage totals since open: requested = keys (add) and scalars (mul) of the calls that launched or were served from a sweep;
+   covered = those whose device count was checked equal to what was asked (by their own launch or by the sweep that held them);
+   device = keys counted by the kernels of this context's own launches, sweeps whole (so >= covered with the look-ahead on).
+   On a sound device requested == covered always.  Not reset by ecl_hip_reset_timing; the self-test's launches are left out. */
+int ecl_hip_get_coverage(ecl_hip *h, uint64_t *requested, uint64_t *covered, uint64_t *device_keys);
 
 /* Known-answer test of the device code (hash160 of 1*G, 2*G, 0xdc2a04*G, both encodings, via the double-and-add
    kernel; the P2SH-P2WPKH hash of 1*G) and a cross-check of the walk kernel against it over 4096 consecutive keys (with ECL_P2SH: the
@@ -273,6 +286,10 @@ int ecl_hip_diag_bloom(ecl_hip *h, const uint32_t (*h160)[5], uint8_t *hit, uint
 /* the probe's word index r[i] = x[i] mod nwords (the `% (blf->size * 64)` of utils.c:286-288 on the word index) as the
    device computes it, for any filter size 0 < nwords < 2^58 and x < 2^58; no filter needs to be resident */
 int ecl_hip_diag_bloom_mod(ecl_hip *h, uint64_t nwords, const uint64_t *x, uint64_t *r, uint32_t n);
+/* one-shot: the next search launch of this context (add_range, a look-ahead sweep, or the first piece of a mul call) runs one
+   round short - add: groups per lane nb - 1, mul: scalars per thread R - 1 - so that keys of the call are silently not hashed
+   (the call then returns ECL_E_COVERAGE: the check of section 1, under test).  Only a loop bound shrinks. */
+int ecl_hip_diag_drop_round(ecl_hip *h);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
