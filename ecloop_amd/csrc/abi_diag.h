@@ -175,7 +175,7 @@ extern "C" int ecl_hip_diag_drop_round(ecl_hip* h) {
 extern "C" int ecl_hip_selftest(ecl_hip* h) {
   if (!h) return ECL_E_ARG;
   // (1) known answers: hash160 of k*G for k = 1, 2, 0xdc2a04 (compressed, uncompressed), public vectors; the P2SH-P2WPKH hash of 1*G
-  // (address 3JvL6Ymt8MVWiCNHC7oWU6nLeHNJKLZGLN)
+  // (address 3JvL6Ymt8MVWiCNHC7oWU6nLeHNJKLZGLN) and its Ethereum address (7e5f4552091a69125d5dfcb7b8c2659029395bdf)
   static const uint64_t KS[3][4] = {{1, 0, 0, 0}, {2, 0, 0, 0}, {0xdc2a04, 0, 0, 0}};
   static const uint32_t KAT33[3][5] = {{0x751e76e8u, 0x199196d4u, 0x54941c45u, 0xd1b3a323u, 0xf1433bd6u},
                                        {112186475u, 3455918831u, 2494304810u, 2703172626u, 1151565516u},
@@ -186,13 +186,16 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   static const uint32_t KATP2SH[5] = {0xbcfeb728u, 0xb584253du, 0x5f3f70bcu, 0xb780e9efu, 0x218a68f4u};
   uint64_t x[3][4], y[3][4];
   uint8_t ok[3];
-  uint32_t h33[3][5], h65[3][5], hsh[1][5];
+  static const uint32_t KATETH[5] = {0x7e5f4552u, 0x091a6912u, 0x5d5dfcb7u, 0xb8c26590u, 0x29395bdfu};
+  uint32_t h33[3][5], h65[3][5], hsh[1][5], heth[1][5];
+  uint8_t oketh[1] = {0};
   int rc = ecl_hip_diag_mulg(h, KS, x, y, ok, 3);
   if (rc == ECL_OK) rc = ecl_hip_diag_hash160(h, x, y, h33, h65, 3);
   if (rc == ECL_OK) rc = ecl_hip_p2sh_hash(h, h33, hsh, 1);
+  if (rc == ECL_OK) rc = ecl_hip_verify_eth(h, KS, 1, heth, oketh);
   if (rc != ECL_OK) return rc;
   if (memcmp(h33, KAT33, sizeof KAT33) != 0 || memcmp(h65, KAT65, sizeof KAT65) != 0 || memcmp(hsh[0], KATP2SH, sizeof KATP2SH) != 0 ||
-      !(ok[0] && ok[1] && ok[2])) {
+      memcmp(heth[0], KATETH, sizeof KATETH) != 0 || !oketh[0] || !(ok[0] && ok[1] && ok[2])) {
     h->err = "known-answer test of k*G -> hash160 failed";
     return ECL_E_SELFTEST;
   }
@@ -208,14 +211,16 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   h->d_bloom = nullptr, h->bloom_words = 0;
   h->B = 16, h->Tmax = 256, h->B_auto = false;
   const uint64_t start[4] = {0x0123456789abcdefull, 0x1f, 0, 0};
-  const u32 per_key = ((h->flags & ECL_ADDR33) ? 1 : 0) + ((h->flags & ECL_ADDR65) ? 1 : 0) + ((h->flags & ECL_P2SH) ? 1 : 0);
+  const u32 per_key = ((h->flags & ECL_ADDR33) ? 1 : 0) + ((h->flags & ECL_ADDR65) ? 1 : 0) + ((h->flags & ECL_P2SH) ? 1 : 0) +
+                      ((h->flags & ECL_ETH) ? 1 : 0);
   const u32 cap = N * per_key * ((h->flags & ECL_ENDO) ? 6 : 1);
   std::vector<ecl_found> recs(cap);
   u32 n = 0;
   rc = ecl_hip_set_bloom(h, ones.data(), ones.size());
   if (rc == ECL_OK) rc = ecl_hip_add_range(h, start, N, recs.data(), cap, &n);
   std::vector<uint64_t> ks((size_t)N * 4), xs((size_t)N * 4), ys((size_t)N * 4);
-  std::vector<uint32_t> r33((size_t)N * 5), r65((size_t)N * 5), rsh((size_t)N * 5);
+  std::vector<uint32_t> r33((size_t)N * 5), r65((size_t)N * 5), rsh((size_t)N * 5), reth((size_t)N * 5);
+  std::vector<uint8_t> eok(N);
   const u256 s = sc_pow2(h->offs);
   u256 cur = sc_reduce(u256_from(start));
   for (u32 i = 0; i < N; ++i) {
@@ -226,6 +231,8 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   if (rc == ECL_OK) rc = ecl_hip_diag_hash160(h, (const uint64_t(*)[4])xs.data(), (const uint64_t(*)[4])ys.data(),
                                               (uint32_t(*)[5])r33.data(), (uint32_t(*)[5])r65.data(), N);
   if (rc == ECL_OK && (h->flags & ECL_P2SH)) rc = ecl_hip_p2sh_hash(h, (const uint32_t(*)[5])r33.data(), (uint32_t(*)[5])rsh.data(), N);
+  // an ECL_ETH context: the walk's addresses against the window-table sum's (ecl_hip_verify_eth; (3) checks that sum against the double-and-add kernel)
+  if (rc == ECL_OK && (h->flags & ECL_ETH)) rc = ecl_hip_verify_eth(h, (const uint64_t(*)[4])ks.data(), N, (uint32_t(*)[5])reth.data(), eok.data());
   // restore the caller's state whatever happened
   if (h->d_bloom) (void)hipFree(h->d_bloom);
   h->d_bloom = save_bloom, h->bloom_words = save_words;
@@ -242,7 +249,7 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
     const ecl_found& f = recs[i];
     if (f.key_offset >= N) { good = false; break; }
     if (f.endo != 0) continue;  // the endomorphism images are covered by the parity tests; here: the walk itself
-    const uint32_t* want = f.compressed == 2 ? &rsh[f.key_offset * 5] : f.compressed ? &r33[f.key_offset * 5] : &r65[f.key_offset * 5];
+    const uint32_t* want = f.compressed == 3 ? &reth[f.key_offset * 5] : f.compressed == 2 ? &rsh[f.key_offset * 5] : f.compressed ? &r33[f.key_offset * 5] : &r65[f.key_offset * 5];
     good = memcmp(f.h160, want, 20) == 0;
     ++seen;
   }

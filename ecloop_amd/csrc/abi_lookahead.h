@@ -42,7 +42,7 @@ struct la_region {
 };
 
 struct la_key {
-  u32 flags, offs;  // all of ecl_hip_open's flags: contexts that search different address types (ECL_P2SH too) never share a sweep
+  u32 flags, offs;  // all of ecl_hip_open's flags: contexts that search different address types (ECL_P2SH, ECL_ETH too) never share a sweep
   u64 nwords, bloom_fp, list_n, list_fp;
   bool operator<(const la_key& o) const {
     if (flags != o.flags) return flags < o.flags;

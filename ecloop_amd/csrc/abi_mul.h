@@ -214,6 +214,10 @@ static void mul_launch_piece(ecl_hip* h, int lane, const u32* d_k, u32 m, u32 at
   mul_geometry(m, &R, &nt);
   if (short_round) R -= 1;
   dim3 grid(nt / 256), blk(256);
+  if (h->flags & ECL_ETH) {  // alone (ecl_hip_open)
+    hipLaunchKernelGGL(k_mul_check_eth, grid, blk, 0, st, d_k, m, at, gtab, a, tmp, nt, R);
+    return;
+  }
   switch (h->flags & (ECL_ADDR33 | ECL_ADDR65 | ECL_P2SH)) {  // every non-empty set of address types
   case ECL_ADDR33: hipLaunchKernelGGL((k_mul_check<true, false>), grid, blk, 0, st, d_k, m, at, gtab, a, tmp, nt, R); break;
   case ECL_ADDR65: hipLaunchKernelGGL((k_mul_check<false, true>), grid, blk, 0, st, d_k, m, at, gtab, a, tmp, nt, R); break;
@@ -524,6 +528,25 @@ extern "C" int ecl_hip_verify(ecl_hip* h, const uint64_t (*k)[4], uint32_t n, ui
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(h33, d33, (size_t)n * 20, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemcpyAsync(h65, d65, (size_t)n * 20, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return ECL_OK;
+}
+
+extern "C" int ecl_hip_verify_eth(ecl_hip* h, const uint64_t (*k)[4], uint32_t n, uint32_t (*addr)[5], uint8_t* ok) {
+  if (!h || !k || !addr || !ok || n == 0 || n > (1u << 31)) return ECL_E_ARG;
+  HIPCHK(h, hipSetDevice(h->dev));
+  int rc;
+  if ((rc = ensure_gtable(h)) != ECL_OK) return rc;
+  dbuf<u8> d;  // scalars 32 B, address 20 B, flag
+  HIPCHK(h, hipMalloc(&d.p, (size_t)n * 53));
+  u32* dk = (u32*)d.p;
+  u32* da = (u32*)(d.p + (size_t)n * 32);
+  u8* dok = d.p + (size_t)n * 52;
+  HIPCHK(h, hipMemcpyAsync(dk, k, (size_t)n * 32, hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_verify_eth, dim3((n + 63) / 64), dim3(64), 0, h->stream, dk, n, h->d_gtab, da, dok);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(addr, da, (size_t)n * 20, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return ECL_OK;

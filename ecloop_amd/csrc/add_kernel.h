@@ -22,11 +22,12 @@
 #pragma once
 #include "bloom.h"
 #include "hash160.h"
+#include "keccak.h"
 
 struct ecl_found_dev {
   u64 key_offset;
   u32 h160[5];
-  u32 tag;  // byte 0 = endo, byte 1 = address type (ecl_found.compressed: 1 addr33, 0 addr65, 2 p2sh)
+  u32 tag;  // byte 0 = endo, byte 1 = address type (ecl_found.compressed: 1 addr33, 0 addr65, 2 p2sh, 3 eth)
 };
 
 struct add_args {
@@ -175,7 +176,8 @@ __device__ __forceinline__ void keys_count(cand_queues& q, bool live) { q.keys +
 __device__ __forceinline__ void keys_flush(const add_args& a, const cand_queues& q) {
   if ((threadIdx.x & 63u) == 0) atomicAdd(a.keys, (unsigned long long)q.keys);
 }
-// P2SH: the kernel reports the address type 2 as well, so the type byte of a parked record keeps two bits instead of one
+// P2SH: the kernel reports the address type 2 as well, so the type byte of a parked record keeps two bits instead of one (the ETH
+// kernels, type 3, instantiate these with P2SH = true for the same reason)
 template <bool P2SH>
 __device__ __forceinline__ void cand_finish(const add_args& a, cand_queue& qb) {  // up to 64 records of ring B
   bool valid;
@@ -220,8 +222,10 @@ __device__ __forceinline__ void filter_check(const add_args& a, cand_queues* q, 
 // (check_found_add, main.c:287-347; endo images (x,-y) (bx,y) (bx,-y) (b2x,y) (b2x,-y), main.c:314-327).
 // P2SH (no reference counterpart): the script hash of the compressed key's hash160, one more SHA-256 and RIPEMD-160 block fed
 // by the addr33 hash, which is computed for it even when addr33 itself is not searched.
+// ETH (no reference counterpart, searched alone: A33 = A65 = P2SH = false): the Ethereum address of the point, Keccak-256 over x || y
+// (keccak.h), type 3; x and y are normalised and the endomorphism images formed as for addr65.
 // x: magnitude <= 4, y: magnitude <= 3.
-template <bool A33, bool A65, bool P2SH, bool ENDO>
+template <bool A33, bool A65, bool P2SH, bool ENDO, bool ETH = false>
 __device__ __forceinline__ void check_point(const add_args& a, cand_queues* q, bool live, fe x, fe y, u64 off) {
   u32 xw[3][8], yw[2][8], par = 0;
   if (ENDO) {
@@ -235,11 +239,11 @@ __device__ __forceinline__ void check_point(const add_args& a, cand_queues* q, b
   }
   fe_normalize(x);
   fe_to_words(xw[0], x);
-  if (A65) {
+  if (A65 || ETH) {
     fe_normalize(y);
     fe_to_words(yw[0], y);
     par = y.n[0] & 1u;
-    if (ENDO) {
+    if (ENDO && !ETH) {
       fe ny = fe_neg(y, 1);  // y != 0 on the curve, so this is p - y after normalisation
       fe_normalize(ny);
       fe_to_words(yw[1], ny);
@@ -268,6 +272,28 @@ __device__ __forceinline__ void check_point(const add_args& a, cand_queues* q, b
       for (int i = 0; i < 8; ++i) ys[i] = (ENDO && (e & 1)) ? yw[1][i] : yw[0][i];
       hash160_65(h, xs, ys);
       filter_check<P2SH>(a, q, live, off, h, e, 0);
+    }
+    if (ETH) {
+      u32 ys[8];
+      if (ENDO) {
+        // -y is formed here, per image, from y's words: p - y = ~y + (p + 1) (mod 2^256), under a mask made of the image number, so
+        // that it cannot be hoisted out of the loop - kept for the loop's length as addr65 keeps it, its eight words (beside Keccak's
+        // fifty-word state) pushed the walk's values into scratch inside the table loop.  16 instructions per address.
+        const u32 m = 0u - ((u32)e & 1u);
+        const u32 p1[8] = {0xFFFFFC30u, 0xFFFFFFFEu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+        u64 c = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          c += (u64)(yw[0][i] ^ m) + (p1[i] & m);
+          ys[i] = (u32)c;
+          c >>= 32;
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ys[i] = yw[0][i];
+      }
+      eth_address(h, xs, ys);
+      filter_check<true>(a, q, live, off, h, e, 3);
     }
   }
 }
@@ -300,5 +326,19 @@ __device__ __forceinline__ void check_point(const add_args& a, cand_queues* q, b
 #define ECL_WALK_WAVES ((A65 && ENDO) ? 3 : ECL_ADD_WAVES)
 #include "add_walk.inc"
 #undef ECL_WALK_KERNEL
+#undef ECL_WALK_P2SH
+#undef ECL_WALK_WAVES
+// ETH instantiations: k_add_eth<ENDO>, one address type, never combined with the others (ecl_hip_open), so two kernels.  Both at three
+// waves per SIMD (168 VGPRs): Keccak's state is 50 registers plus a dozen for the column parities beside the walk's live values, and at
+// four waves (128) the plain kernel reloaded the lane's two chain pointers from scratch once per table point; at three it has no spill
+// at all, and the -endo kernel spills in the launch loop only (tools/isa_mix.py --eth)
+#define ECL_ETH_WAVES 3
+#define ECL_WALK_KERNEL k_add_eth
+#define ECL_WALK_ETH
+#define ECL_WALK_P2SH false
+#define ECL_WALK_WAVES ECL_ETH_WAVES
+#include "add_walk.inc"
+#undef ECL_WALK_KERNEL
+#undef ECL_WALK_ETH
 #undef ECL_WALK_P2SH
 #undef ECL_WALK_WAVES

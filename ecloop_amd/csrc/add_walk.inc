@@ -1,9 +1,19 @@
 // add_walk.inc - the body of the add kernel, instantiated twice by add_kernel.h: as k_add (address types addr33 / addr65) and as
 // k_add_p2sh (the same sets plus P2SH, and P2SH alone).  Included with ECL_WALK_KERNEL (the kernel's name), ECL_WALK_P2SH and
 // ECL_WALK_WAVES (waves per SIMD of an instantiation, an expression of A33 / A65 / ENDO) defined; no include guard on purpose.
+// With ECL_WALK_ETH defined as well the kernel is k_add_eth<ENDO>: the Ethereum address alone (ECL_WALK_WAVES an expression of ENDO).
+#ifdef ECL_WALK_ETH
+template <bool ENDO>
+#else
 template <bool A33, bool A65, bool ENDO>
+#endif
 __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL(const add_args a) {
-  constexpr bool P2SH = ECL_WALK_P2SH;
+#ifdef ECL_WALK_ETH
+  constexpr bool A33 = false, A65 = false, ETH = true;
+#else
+  constexpr bool ETH = false;
+#endif
+  constexpr bool P2SH = ECL_WALK_P2SH || ETH;  // (for the rings: the record's type field keeps two bits)
   __shared__ u32 q_mem[ECL_ADD_BLOCK / 64][2][8 * ECL_Q_SLOTS];  // two candidate rings per wave
   cand_queues q;
   q.a.mem = q_mem[threadIdx.x >> 6][0], q.a.head = 0, q.a.count = 0;
@@ -85,7 +95,7 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
         if (valid) {
           const bool live = off < a.nkeys;
           keys_count(q, live);
-          check_point<A33, A65, P2SH, ENDO>(a, &q, live, px, py, off);
+          check_point<A33, A65, ECL_WALK_P2SH, ENDO, ETH>(a, &q, live, px, py, off);
         }
       }
     }

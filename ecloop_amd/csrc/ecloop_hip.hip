@@ -136,7 +136,8 @@ const char* ecl_hip_last_error(const ecl_hip* h) { return h ? h->err.c_str() : "
 
 int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   const u32 types = ECL_ADDR33 | ECL_ADDR65 | ECL_P2SH;
-  if (!out || ord_offs > 255 || !(flags & types) || (flags & ~(types | ECL_ENDO))) return ECL_E_ARG;
+  if (!out || ord_offs > 255 || !(flags & (types | ECL_ETH)) || (flags & ~(types | ECL_ETH | ECL_ENDO))) return ECL_E_ARG;
+  if ((flags & ECL_ETH) && (flags & types)) return ECL_E_ARG;  // eth is searched alone
   int n = ecl_hip_device_count();
   if (device < 0 || device >= n) return ECL_E_NODEV;
   ecl_hip* h = new ecl_hip();
@@ -158,7 +159,7 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   static std::mutex mu;
   static std::set<u32> passed;
   const char* skip = getenv("ECL_HIP_SKIP_SELFTEST");
-  const u32 key = (u32)device * 32u + flags;  // flags < 32
+  const u32 key = (u32)device * 128u + flags;  // flags < 128
   {
     std::lock_guard<std::mutex> lk(mu);
     if ((skip && skip[0] == '1') || passed.count(key)) return ECL_OK;
@@ -399,6 +400,7 @@ typedef void (*add_kernel_t)(const add_args);
 // every non-empty set of address types (ecl_hip_open refuses the empty one) x endo
 static add_kernel_t pick_add_kernel(u32 flags) {
   const bool endo = flags & ECL_ENDO;
+  if (flags & ECL_ETH) return endo ? k_add_eth<true> : k_add_eth<false>;  // alone (ecl_hip_open)
   switch (flags & (ECL_ADDR33 | ECL_ADDR65 | ECL_P2SH)) {
   case ECL_ADDR33: return endo ? k_add<true, false, true> : k_add<true, false, false>;
   case ECL_ADDR65: return endo ? k_add<false, true, true> : k_add<false, true, false>;

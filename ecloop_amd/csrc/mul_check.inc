@@ -1,10 +1,17 @@
 // mul_check.inc - the body of the `mul` kernel, instantiated twice by mul_kernels.h: as k_mul_check (address types addr33 / addr65)
 // and as k_mul_check_p2sh (the same sets plus P2SH, and P2SH alone), like add_walk.inc.  Included with ECL_MUL_KERNEL and ECL_MUL_P2SH
-// defined; no include guard on purpose.
+// defined; no include guard on purpose.  With ECL_MUL_ETH defined as well the kernel is k_mul_check_eth: the Ethereum address alone.
+#ifndef ECL_MUL_ETH
 template <bool A33, bool A65>
+#endif
 __global__ void __launch_bounds__(256, ECL_MUL_WAVES) ECL_MUL_KERNEL(const u32* __restrict__ k, u32 n, u32 base, const wtab gtab, add_args a,
                                                       u32* __restrict__ tmp, u32 nt, u32 R) {
-  constexpr bool P2SH = ECL_MUL_P2SH;
+#ifdef ECL_MUL_ETH
+  constexpr bool A33 = false, A65 = false, ETH = true;
+#else
+  constexpr bool ETH = false;
+#endif
+  constexpr bool P2SH = ECL_MUL_P2SH || ETH;  // (for the rings: the record's type field keeps two bits)
   __shared__ u32 q_mem[4][2][8 * ECL_Q_SLOTS];  // two candidate rings per wave (add_kernel.h)
   const u32 t = blockIdx.x * 256u + threadIdx.x;
   if (t >= nt) return;  // nt is a multiple of 256: whole workgroups leave
@@ -65,7 +72,7 @@ __global__ void __launch_bounds__(256, ECL_MUL_WAVES) ECL_MUL_KERNEL(const u32* 
     inv = ninv;
     fe_mul_pair(x, y, X, ti, Y, ti);
     keys_count(q, have);  // a scalar whose point is at infinity counts: it has nothing to hash
-    check_point<A33, A65, P2SH, false>(a, &q, have && !((infmask >> r) & 1u), x, y, (u64)base + i);
+    check_point<A33, A65, ECL_MUL_P2SH, false, ETH>(a, &q, have && !((infmask >> r) & 1u), x, y, (u64)base + i);
   }
   cand_flush<P2SH>(a, q);
   keys_flush(a, q);

@@ -200,6 +200,13 @@ __device__ __forceinline__ xyzz wtab_sum_fast(const u32* __restrict__ kw, const 
 #include "mul_check.inc"
 #undef ECL_MUL_KERNEL
 #undef ECL_MUL_P2SH
+#define ECL_MUL_KERNEL k_mul_check_eth
+#define ECL_MUL_ETH
+#define ECL_MUL_P2SH false
+#include "mul_check.inc"
+#undef ECL_MUL_KERNEL
+#undef ECL_MUL_ETH
+#undef ECL_MUL_P2SH
 // ---- k_mul_check's window sum (round 4): written for a small register budget (three waves per SIMD) --------
 // * the scalar stays in memory: a digit is one 8-byte load at the digit's word (L2 / L1 hits after the first window: a wave's scalars
 //   are 2 KiB of contiguous memory) + a shift, not a 16-way select over eight registers, and is fetched one window ahead;
@@ -377,6 +384,24 @@ __global__ void __launch_bounds__(64) k_verify(const u32* __restrict__ k, u32 n,
   hash160_65(h, xw, yw);
 #pragma unroll
   for (int w = 0; w < 5; ++w) h65[(size_t)i * 5 + w] = h[w];
+  ok[i] = (u8)fin;
+}
+// the ETH half of pk_verify_hash (ecl_hip_verify_eth): k_verify's path to the public key, then its Ethereum address
+__global__ void __launch_bounds__(64) k_verify_eth(const u32* __restrict__ k, u32 n, const u32* __restrict__ gtab, u32* __restrict__ addr,
+                                                   u8* __restrict__ ok) {
+  const u32 i = blockIdx.x * 64u + threadIdx.x;
+  if (i >= n) return;
+  u32 kk[9];
+#pragma unroll
+  for (int w = 0; w < 8; ++w) kk[w] = k[(size_t)i * 8 + w];
+  kk[8] = 0;
+  fe x, y;
+  const int fin = jac_to_affine(x, y, gtable_mul(kk, gtab));
+  u32 xw[8], yw[8], h[5];
+  fe_to_words(xw, x), fe_to_words(yw, y);
+  eth_address(h, xw, yw);
+#pragma unroll
+  for (int w = 0; w < 5; ++w) addr[(size_t)i * 5 + w] = h[w];
   ok[i] = (u8)fin;
 }
 // the P2SH half of pk_verify_hash (ecl_hip_p2sh_hash): the script hash of each given addr33 hash, one lane per hash

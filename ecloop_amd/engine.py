@@ -234,14 +234,19 @@ class KeySearch:
     """ctx_t + cmd_add / cmd_mul for one GPU."""
 
     def __init__(self, flt, device=0, a33=True, a65=False, endo=False, ord_offs=0, verify=True, launch_keys=1 << 32,
-                 half_group=0, max_lanes=0, device_cls=None, p2sh=False):
-        if not (a33 or a65 or p2sh):
+                 half_group=0, max_lanes=0, device_cls=None, p2sh=False, eth=False):
+        if eth:
+            a33 = False  # eth is searched alone (any other type beside it: the context refuses)
+        elif not (a33 or a65 or p2sh):
             a33 = True  # main.c:825-827
         self.flt, self.a33, self.a65, self.endo, self.offs, self.verify = flt, a33, a65, endo, ord_offs, verify
         self.p2sh = p2sh  # P2SH-P2WPKH (no reference counterpart): records labelled "p2sh"
+        self.eth = eth  # Ethereum addresses (no reference counterpart either): records labelled "eth"
         self.stride = 1 << ord_offs
         # device_cls: the GPU context (capi.Device); the CPU tests of the host logic pass a stand-in with the same surface
         kw = {"p2sh": True} if p2sh else {}  # (a stand-in without the P2SH type keeps working for the other types)
+        if eth:
+            kw["eth"] = True
         self.dev = (device_cls or Device)(device, a33=a33, a65=a65, endo=endo, ord_offs=ord_offs, **kw)
         if half_group or max_lanes:
             self.dev.set_geometry(half_group, max_lanes)
@@ -261,6 +266,15 @@ class KeySearch:
     def _verify(self, recs):
         if not recs:
             return
+        eth = [r for r in recs if r.label == "eth"]
+        if eth:
+            addr, ok = self.dev.verify_eth([r.pk for r in eth])
+            for i, r in enumerate(eth):
+                if not ok[i] or [int(v) for v in addr[i]] != [int(v) for v in r.h160]:
+                    raise EclError("[!] error: hash mismatch (%s) pk: %064x" % (r.label, r.pk))
+            recs = [r for r in recs if r.label != "eth"]
+            if not recs:
+                return
         h33, h65, ok = self.dev.verify([r.pk for r in recs])
         hsh = self.dev.p2sh_hash(h33) if any(r.label == "p2sh" for r in recs) else None
         for i, r in enumerate(recs):

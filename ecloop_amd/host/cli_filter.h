@@ -89,12 +89,17 @@ static bool hash160_from_hex(const char *s, u32 h[5]) {
    in pieces of 40 characters, and every FULL piece is an entry).  Stated on the file image: cut at '\n', walk each line
    in steps of 40, keep the pieces that are 40 clean hex digits (the reference parses garbage out of the others - one
    phantom entry for the comment line of data/btc-bw-hash; dropped here).  `out` has room for len / 40 + 1
-   entries (no piece is shorter than 40 characters). */
+   entries (no piece is shorter than 40 characters).
+   Ethereum lists (no reference counterpart): address dumps write `0x` in front of the 40 digits, a line of 42 characters whose 40-character
+   piece is never clean hex - no entry at all, silently.  With `-a e` on the command line (list_skip_0x; never otherwise) a line that starts
+   with 0x / 0X is walked from its third character.  EIP-55 mixed-case digits decode like any others (hash160_from_hex, both paths). */
+static bool list_skip_0x;
 static size_t hashlist_entries(const char *text, size_t len, u32 *out) {
   size_t n = 0;
   for (size_t at = 0; at < len;) {
     const char *nl = memchr(text + at, '\n', len - at);
     size_t eol = nl ? (size_t)(nl - text) : len;
+    if (list_skip_0x && at + 2 <= eol && text[at] == '0' && (text[at + 1] == 'x' || text[at + 1] == 'X')) at += 2;
     for (size_t p = at; p + 40 <= eol; p += 40)
       if (hash160_from_hex(text + p, out + n * 5)) n++;
     at = eol + 1;

@@ -114,7 +114,8 @@ static double bring_up(run_t *run, int shown, int real) {
     largest_call = scan_chunk(run, &keys, &fixed_shards);
     if (!(keys.w[1] | keys.w[2] | keys.w[3]) && keys.w[0] < largest_call) largest_call = keys.w[0];
   }
-  const u32 flags = (run->a33 ? ECL_ADDR33 : 0) | (run->a65 ? ECL_ADDR65 : 0) | (run->p2sh ? ECL_P2SH : 0) | (run->endo ? ECL_ENDO : 0);
+  const u32 flags = (run->a33 ? ECL_ADDR33 : 0) | (run->a65 ? ECL_ADDR65 : 0) | (run->p2sh ? ECL_P2SH : 0) | (run->eth ? ECL_ETH : 0) |
+                    (run->endo ? ECL_ENDO : 0);
   pthread_t th[MAX_GPUS];
   bringup_t job[MAX_GPUS];
   for (int g = 0; g < run->ngpus; ++g) {
@@ -145,7 +146,7 @@ int main(int argc, const char **argv) {
   setlocale(LC_NUMERIC, "");
   hexval_init();
 #if defined(__x86_64__)
-  have_ssse3 = __builtin_cpu_supports("ssse3");
+  have_ssse3 = __builtin_cpu_supports("ssse3") && !getenv("ECLOOP_HIP_NO_SSSE3"); /* (the variable: tests run the scalar hex decoder) */
   have_avx512 = __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512bw") && __builtin_cpu_supports("avx512vl") && !getenv("ECLOOP_HIP_NO_AVX512");
   have_avx2 = __builtin_cpu_supports("avx2") && !getenv("ECLOOP_HIP_NO_AVX2"); /* (the variable: tests run the SSSE3 form on a CPU that has both) */
 #endif
@@ -153,6 +154,14 @@ int main(int argc, const char **argv) {
   opts_t *o = &run.opt;
   opts_parse(o, argc, argv);
   const char *verb = argc > 1 ? argv[1] : "";
+  /* -a e (no reference counterpart): Ethereum addresses, searched alone - a Bitcoin list and an Ethereum list are different files.  Checked
+     before anything is opened; with it, list lines may start with 0x (hashlist_entries: the search commands' lists and blf-gen) */
+  run.eth = o->addr && strchr(o->addr, 'e');
+  if (run.eth && (strchr(o->addr, 'c') || strchr(o->addr, 'u') || strchr(o->addr, 's'))) {
+    fprintf(stderr, "invalid address type '%s': eth is searched alone (-a e), not together with c, u or s\n", o->addr);
+    exit(1);
+  }
+  list_skip_0x = run.eth;
   /* commands that need no search context */
   if (!strcmp(verb, "blf-gen")) return cmd_blf_gen(o, argv[0]), 0;
   if (!strcmp(verb, "blf-check")) return cmd_blf_check(o, argc, argv), 0;
@@ -176,8 +185,9 @@ int main(int argc, const char **argv) {
   if (!plan_only) filter_open(&run.flt, o->filter);
   if (o->quiet && !o->outfile && !plan_only) { fprintf(stderr, "quiet mode chosen without output file\n"); exit(1); }
   run.a33 = o->addr ? strchr(o->addr, 'c') != NULL : true, run.a65 = o->addr && strchr(o->addr, 'u');
+  if (run.eth) run.a33 = run.a65 = false;
   run.p2sh = o->addr && strchr(o->addr, 's'); /* no reference counterpart: P2SH-P2WPKH */
-  if (!run.a33 && !run.a65 && !run.p2sh) run.a33 = true; /* main.c:825-827 */
+  if (!run.a33 && !run.a65 && !run.p2sh && !run.eth) run.a33 = true; /* main.c:825-827 */
   run.endo = o->endo && run.cmd != CMD_MUL, run.bin = o->bin && run.cmd == CMD_MUL;
   report_init(&run.rep, o->outfile, o->quiet);
   range_from_option(o->range, &run.range_s, &run.range_e);
@@ -222,7 +232,8 @@ int main(int argc, const char **argv) {
     if (rc != ECL_OK) die_ecl(&run, g, rc, "drop_round");
   }
 
-  printf("gpus: %d ~ addr33: %d ~ addr65: %d ~ endo: %d%s | filter: ", shown, run.a33, run.a65, run.endo, run.p2sh ? " ~ p2sh: 1" : "");
+  printf("gpus: %d ~ addr33: %d ~ addr65: %d ~ endo: %d%s | filter: ", shown, run.a33, run.a65, run.endo,
+         run.p2sh ? " ~ p2sh: 1" : run.eth ? " ~ eth: 1" : "");
   if (run.flt.list) printf("list (%'llu)\n", (unsigned long long)run.flt.nlist);
   else printf("bloom\n");
   if (run.cmd == CMD_ADD) print_scalar_row("range_s", &run.range_s), print_scalar_row("range_e", &run.range_e);

@@ -33,7 +33,7 @@
  * section 3 (sweeps and their records belong to the group of contexts that share a filter; one mutex per group; records are immutable
  * once published).  ecl_hip_strerror returns static text; ecl_hip_last_error returns the handle's own buffer (same thread rule).
  *
- * Exports: exactly the 41 ecl_hip_* functions declared below (the library is linked with a version script; `nm -D` shows nothing else).
+ * Exports: exactly the 42 ecl_hip_* functions declared below (the library is linked with a version script; `nm -D` shows nothing else).
  */
 #ifndef ECLOOP_HIP_H
 #define ECLOOP_HIP_H
@@ -51,11 +51,17 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
 /* flags of ecl_hip_open: which encodings to hash (main.c:819-827) and the endomorphism switch (main.c:829).  ECL_P2SH has no reference
    counterpart: the nested-SegWit (BIP49, P2SH-P2WPKH "3..." address) hash, hash160(0x00 0x14 || hash160 of the compressed key).
    Any non-empty set of the three address types, with or without ECL_ENDO; every other bit is refused (ECL_E_ARG).  The bit 8 is not
-   used: releases before ECL_P2SH refused it as an unknown flag, and it stays refused, so ECL_P2SH is the next one. */
+   used: releases before ECL_P2SH refused it as an unknown flag, and it stays refused, so ECL_P2SH is the next one.
+   ECL_ETH (no reference counterpart either): the Ethereum address, the last 20 bytes of Keccak-256 (original padding) over the 64 bytes
+   x || y of the uncompressed key.  Eth is searched ALONE: ECL_ETH together with ECL_ADDR33, ECL_ADDR65 or ECL_P2SH is ECL_E_ARG (a Bitcoin
+   list and an Ethereum list are different files), with or without ECL_ENDO.  So the valid type sets are: any non-empty subset of the three
+   Bitcoin types, or ECL_ETH by itself.  (ecl_hip_open leaves no handle to ask after ECL_E_ARG - this comment is the message.)  The bits 8
+   and 32 stay refused as unknown flags. */
 #define ECL_ADDR33 1u
 #define ECL_ADDR65 2u
 #define ECL_ENDO 4u
 #define ECL_P2SH 16u
+#define ECL_ETH 64u
 
 /* return codes */
 #define ECL_OK 0
@@ -77,7 +83,8 @@ typedef struct ecl_found {
   uint64_t key_offset;
   uint32_t h160[5];
   uint8_t endo;
-  uint8_t compressed; /* the address type: 1 = addr33, 0 = addr65, 2 = P2SH-P2WPKH (only for a context opened with ECL_P2SH) */
+  uint8_t compressed; /* the address type: 1 = addr33, 0 = addr65, 2 = P2SH-P2WPKH (only for a context opened with ECL_P2SH),
+                         3 = Ethereum (ECL_ETH; h160 holds the address) */
   uint8_t pad[2];
 } ecl_found; /* 32 bytes */
 
@@ -161,6 +168,9 @@ int ecl_hip_verify(ecl_hip *h, const uint64_t (*k)[4], uint32_t n, uint32_t (*h3
    h160_t words), computed on the device by the hash function of the search kernels.  A caller verifies a type-2 hit by passing the h33 of
    ecl_hip_verify through this.  Any context can be asked, whatever its flags. */
 int ecl_hip_p2sh_hash(ecl_hip *h, const uint32_t (*h33)[5], uint32_t (*out)[5], uint32_t n);
+/* ... and its ETH half: addr[i] = the Ethereum address (h160_t words) of k[i]*G by ecl_hip_verify's path (window-table sum + own inversion,
+   not the walk kernel), ok[i] = 0 for k = 0 (mod n).  A caller verifies a type-3 hit with it.  Any context can be asked, whatever its flags. */
+int ecl_hip_verify_eth(ecl_hip *h, const uint64_t (*k)[4], uint32_t n, uint32_t (*addr)[5], uint8_t *ok);
 
 /* `mul -raw` (main.c:505-527: the scalar of a line is the SHA-256 of its bytes, read as a big-endian number): the same as
    ecl_hip_mul_batch with the hashing done on the device.  `text` holds the lines' bytes (anywhere, in any order, newline
@@ -209,7 +219,7 @@ int ecl_hip_reserve_mul(ecl_hip *h, uint32_t n, uint32_t cap);
 
 /* Look-ahead over small contiguous jobs.  The reference's scheduler hands out jobs of 2^21 keys (MAX_JOB_SIZE, main.c:16,418-431): 0.17 ms
    of work for this GPU, where a launch needs 2^28 keys and more to reach the kernel's rate.  When the ecl_hip_add_range calls of the
-   contexts that share a filter (same flags - so a context with ECL_P2SH never shares a sweep with one without it -, stride and filter
+   contexts that share a filter (same flags - so a context with ECL_P2SH or ECL_ETH never shares a sweep with one without it -, stride and filter
    contents, any device) form that pattern - equal sizes, each starting where
    the one before ended - a call that finds nothing prepared runs ONE sweep of up to `max_keys` keys from its start, keeps the sweep's hit
    records on the host and the following calls are answered from them without a launch: each call still receives exactly the hits of its
@@ -266,8 +276,8 @@ int ecl_hip_get_mul_timing(ecl_hip *h, double *ms, uint64_t *calls, uint64_t *sc
 int ecl_hip_get_coverage(ecl_hip *h, uint64_t *requested, uint64_t *covered, uint64_t *device_keys);
 
 /* Known-answer test of the device code (hash160 of 1*G, 2*G, 0xdc2a04*G, both encodings, via the double-and-add
-   kernel; the P2SH-P2WPKH hash of 1*G) and a cross-check of the walk kernel against it over 4096 consecutive keys (with ECL_P2SH: the
-   script hashes too).  ecl_hip_open() runs it
+   kernel; the P2SH-P2WPKH hash and the Ethereum address of 1*G) and a cross-check of the walk kernel against it over 4096 consecutive
+   keys (with ECL_P2SH: the script hashes too; with ECL_ETH: the Ethereum addresses, against ecl_hip_verify_eth).  ecl_hip_open() runs it
    (a few ms) unless the environment has ECL_HIP_SKIP_SELFTEST=1; a failure makes open return ECL_E_SELFTEST. */
 int ecl_hip_selftest(ecl_hip *h);
 

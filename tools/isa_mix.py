@@ -19,7 +19,8 @@ What the numbers are used for:
     blocks, so it is an UPPER estimate) + half a trip of the table loop around it and of the prefix-product loop
     (each serves two keys).  The PMC count SQ_INSTS_VALU is the truth for the total; the class SHARES come from here.
 
-usage: tools/isa_mix.py [file.s] [mangled kernel name] [--json]     |     tools/isa_mix.py --all   (every instantiation: profiles/rNN_static_mix.json)"""
+usage: tools/isa_mix.py [file.s] [mangled kernel name] [--json]     |     tools/isa_mix.py --all   (every instantiation: profiles/rNN_static_mix.json)
+       tools/isa_mix.py --eth   (the three Ethereum kernels)"""
 import json
 import os
 import re
@@ -221,6 +222,30 @@ MUL_KERNELS = {"mul -a c": "_Z11k_mul_checkILb1ELb0EEvPKjjj4wtab8add_argsPjjj", 
                "mul -a cu": K_MUL_CU}
 
 
+# the Ethereum kernels (-a e, searched alone): a dictionary of their own - ADD_KERNELS / MUL_KERNELS are the sets the tracked profiles cover
+ETH_KERNELS = {"-a e": "_Z9k_add_ethILb0EEv8add_args", "-a e -endo": "_Z9k_add_ethILb1EEv8add_args",
+               "mul -a e": "_Z15k_mul_check_ethPKjjj4wtab8add_argsPjjj"}
+
+
+def analyse_eth(path=ASM):
+    """the three ETH kernels in analyse_all's form (tests/test_eth_host.py: no scratch in the per-key loops, the `which` loop's size)"""
+    sp = {**spills(path, "_Z9k_add_eth"), **spills(path, "_Z15k_mul_check_eth")}
+    out = {}
+    for label, k in ETH_KERNELS.items():
+        if "k_mul_check" in k:
+            m = analyse_mul(path, k)
+            out[label] = {"kernel": k, "fingerprint": m["fingerprint"], "registers": sp.get(k),
+                          "scratch_in_loops": {"window": m["window_loop"]["scratch"], "sum": m["sum_loop"]["scratch"], "walk_back": m["walk_back_loop"]["scratch"]},
+                          "per_scalar_static": {x: round(v, 1) for x, v in m["per_scalar_static"].items()}}
+        else:
+            a = analyse(path, k)
+            out[label] = {"kernel": k, "fingerprint": a["fingerprint"], "registers": sp.get(k),
+                          "scratch_in_loops": {"which": a["which_loop"]["scratch"], "table": a["table_loop"]["scratch"], "prefix": a["prefix_loop"]["scratch"],
+                                               "launch": a["launch_loop"]["scratch"]},
+                          "per_key_static": {x: round(v, 1) for x, v in a["per_key_static"].items()}}
+    return out
+
+
 def analyse_all(path=ASM):
     """every shipped instantiation of the two search kernels: fingerprint, registers / spills, and the scratch instructions inside the
     per-key loops (k_add: prefix-product, table and `which` loops; k_mul_check: window loop) - tests/test_profiles_fresh.py wants 0 there"""
@@ -242,6 +267,10 @@ def analyse_all(path=ASM):
 
 
 def main():
+    if "--eth" in sys.argv:
+        rest = [a for a in sys.argv[1:] if not a.startswith("--")]
+        print(json.dumps(analyse_eth(rest[0] if rest else ASM), indent=1))
+        return
     if "--all" in sys.argv:
         rest = [a for a in sys.argv[1:] if not a.startswith("--")]
         print(json.dumps(analyse_all(rest[0] if rest else ASM), indent=1))
