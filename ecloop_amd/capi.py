@@ -9,7 +9,7 @@ import numpy as np
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ECLOOP_HIP_LIB") or os.path.join(PKG, "libecloop_hip.so")  # override: A/B builds
 
-ADDR33, ADDR65, ENDO, P2SH, ETH = 1, 2, 4, 16, 64
+ADDR33, ADDR65, ENDO, P2SH, ETH, TR = 1, 2, 4, 16, 64, 128
 E_OVERFLOW = -4
 E_COVERAGE = -8  # the device did not hash every key of the call (include/ecloop_hip.h, section 1)
 
@@ -25,7 +25,7 @@ FOUND_DTYPE = np.dtype([("key_offset", "<u8"), ("h160", "<u4", (5,)), ("endo", "
                         ("pad", "u1", (2,))])
 assert FOUND_DTYPE.itemsize == C.sizeof(Found) == 32
 
-LABELS = {1: "addr33", 0: "addr65", 2: "p2sh", 3: "eth"}  # ecl_found.compressed (the address type) -> label of the found line
+LABELS = {1: "addr33", 0: "addr65", 2: "p2sh", 3: "eth", 4: "p2tr"}  # ecl_found.compressed (the address type) -> label of the found line
 
 
 def label_of(compressed):
@@ -36,7 +36,7 @@ EXPORTS = [
     "ecl_hip_mul_batch", "ecl_hip_bloom_insert", "ecl_hip_get_bloom", "ecl_hip_set_geometry", "ecl_hip_get_geometry", "ecl_hip_get_timing", "ecl_hip_reset_timing", "ecl_hip_selftest", "ecl_hip_strerror",
     "ecl_hip_last_error", "ecl_hip_diag_fe", "ecl_hip_diag_mulg", "ecl_hip_diag_hash160", "ecl_hip_diag_bloom", "ecl_hip_diag_bloom_mod", "ecl_hip_set_lookahead", "ecl_hip_set_scan_end", "ecl_hip_get_lookahead_stats",
     "ecl_hip_get_setup_timing", "ecl_hip_get_mul_timing", "ecl_hip_bloom_insert_count", "ecl_hip_alloc_host", "ecl_hip_free_host", "ecl_hip_verify", "ecl_hip_sort_list", "ecl_hip_reserve_mul", "ecl_hip_mul_batch_raw", "ecl_hip_set_mul_window", "ecl_hip_get_mul_window", "ecl_hip_fetch_found", "ecl_hip_plan_geometry",
-    "ecl_hip_p2sh_hash", "ecl_hip_get_coverage", "ecl_hip_diag_drop_round", "ecl_hip_verify_eth",
+    "ecl_hip_p2sh_hash", "ecl_hip_get_coverage", "ecl_hip_diag_drop_round", "ecl_hip_verify_eth", "ecl_hip_verify_tr", "ecl_hip_diag_tr",
 ]
 
 _lib = None
@@ -93,6 +93,8 @@ def load():
     lib.ecl_hip_verify.argtypes = [P, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ecl_hip_p2sh_hash.argtypes = [P, C.c_void_p, C.c_void_p, C.c_uint32]
     lib.ecl_hip_verify_eth.argtypes = [P, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.ecl_hip_verify_tr.argtypes = [P, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    lib.ecl_hip_diag_tr.argtypes = [P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     lib.ecl_hip_alloc_host.argtypes = [C.c_size_t]
     lib.ecl_hip_alloc_host.restype = C.c_void_p
     lib.ecl_hip_free_host.argtypes = [C.c_void_p]
@@ -127,13 +129,15 @@ def ints_of(arr):
 class Device:
     """One GPU context (ecl_hip handle)."""
 
-    def __init__(self, device=0, a33=True, a65=False, endo=False, ord_offs=0, p2sh=False, eth=False):
+    def __init__(self, device=0, a33=True, a65=False, endo=False, ord_offs=0, p2sh=False, eth=False, tr=False):
         self.lib = load()
         self.h = C.c_void_p()
-        self.a33, self.a65, self.endo, self.p2sh, self.eth = bool(a33), bool(a65), bool(endo), bool(p2sh), bool(eth)
+        self.a33, self.a65, self.endo, self.p2sh, self.eth, self.tr = bool(a33), bool(a65), bool(endo), bool(p2sh), bool(eth), bool(tr)
         if eth and (a33 or a65 or p2sh):
             raise ValueError("eth is searched alone: Device(a33=False, eth=True)")
-        flags = (ADDR33 if a33 else 0) | (ADDR65 if a65 else 0) | (P2SH if p2sh else 0) | (ETH if eth else 0) | (ENDO if endo else 0)
+        if tr and (a33 or a65 or p2sh or eth or endo):
+            raise ValueError("Taproot is searched alone and without the endomorphism: Device(a33=False, tr=True)")
+        flags = (ADDR33 if a33 else 0) | (ADDR65 if a65 else 0) | (P2SH if p2sh else 0) | (ETH if eth else 0) | (TR if tr else 0) | (ENDO if endo else 0)
         rc = self.lib.ecl_hip_open(C.byref(self.h), device, flags, ord_offs)
         if rc != 0:
             msg = self.lib.ecl_hip_last_error(self.h).decode() if self.h else ""
@@ -295,6 +299,24 @@ class Device:
         ok = np.zeros(len(K), dtype=np.uint8)
         self._chk(self.lib.ecl_hip_verify_eth(self.h, K.ctypes.data, len(K), addr.ctypes.data, ok.ctypes.data))
         return addr, ok
+
+    def verify_tr(self, ks):
+        """-> (qx, ok): the Taproot output key (n x 8 big-endian uint32 words) of each private key by verify's path, ok = 0 for k = 0 (mod n)
+        or a tweak >= n"""
+        K = limbs_array(ks)
+        qx = np.zeros((len(K), 8), dtype=np.uint32)
+        ok = np.zeros(len(K), dtype=np.uint8)
+        self._chk(self.lib.ecl_hip_verify_tr(self.h, K.ctypes.data, len(K), qx.ctypes.data, ok.ctypes.data))
+        return qx, ok
+
+    def diag_tr(self, xs, ys):
+        """the two stages of the Taproot search path for affine points -> (tweaks as ints, output keys n x 8 big-endian words, ok)"""
+        X, Y = limbs_array(xs), limbs_array(ys)
+        T = np.zeros_like(X)
+        qx = np.zeros((len(X), 8), dtype=np.uint32)
+        ok = np.zeros(len(X), dtype=np.uint8)
+        self._chk(self.lib.ecl_hip_diag_tr(self.h, X.ctypes.data, Y.ctypes.data, T.ctypes.data, qx.ctypes.data, ok.ctypes.data, len(X)))
+        return ints_of(T), qx, ok
 
     def selftest(self):
         self._chk(self.lib.ecl_hip_selftest(self.h))

@@ -189,13 +189,20 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   static const uint32_t KATETH[5] = {0x7e5f4552u, 0x091a6912u, 0x5d5dfcb7u, 0xb8c26590u, 0x29395bdfu};
   uint32_t h33[3][5], h65[3][5], hsh[1][5], heth[1][5];
   uint8_t oketh[1] = {0};
+  // the Taproot output keys of the same three private keys (BIP86 key path; k = 1: bc1pmfr3p9j00pfxjh0zmgp99y8zftmd3s5pmedqhyptwy6lm87hf5sspknck9)
+  static const uint32_t KATTR[3][8] = {{0xda471096u, 0x4f785269u, 0x5de2da02u, 0x5290e24au, 0xf6d8c281u, 0xde5a0b90u, 0x2b7135fdu, 0x9fd74d21u},
+                                       {0xcafd90c7u, 0x026f0b6au, 0xb98df894u, 0x90d02732u, 0x881f2f4bu, 0x59008563u, 0x58dddff4u, 0x679c2ffbu},
+                                       {0x509eeff5u, 0xf103f276u, 0x7a17d328u, 0x9d857dd5u, 0x38a62a94u, 0x49646107u, 0xe5b4b6d0u, 0xa7898714u}};
+  uint32_t qtr[3][8];
+  uint8_t oktr[3] = {0, 0, 0};
   int rc = ecl_hip_diag_mulg(h, KS, x, y, ok, 3);
   if (rc == ECL_OK) rc = ecl_hip_diag_hash160(h, x, y, h33, h65, 3);
   if (rc == ECL_OK) rc = ecl_hip_p2sh_hash(h, h33, hsh, 1);
   if (rc == ECL_OK) rc = ecl_hip_verify_eth(h, KS, 1, heth, oketh);
+  if (rc == ECL_OK) rc = ecl_hip_verify_tr(h, KS, 3, qtr, oktr);
   if (rc != ECL_OK) return rc;
   if (memcmp(h33, KAT33, sizeof KAT33) != 0 || memcmp(h65, KAT65, sizeof KAT65) != 0 || memcmp(hsh[0], KATP2SH, sizeof KATP2SH) != 0 ||
-      memcmp(heth[0], KATETH, sizeof KATETH) != 0 || !oketh[0] || !(ok[0] && ok[1] && ok[2])) {
+      memcmp(heth[0], KATETH, sizeof KATETH) != 0 || !oketh[0] || memcmp(qtr, KATTR, sizeof KATTR) != 0 || !(oktr[0] && oktr[1] && oktr[2]) || !(ok[0] && ok[1] && ok[2])) {
     h->err = "known-answer test of k*G -> hash160 failed";
     return ECL_E_SELFTEST;
   }
@@ -212,7 +219,7 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   h->B = 16, h->Tmax = 256, h->B_auto = false;
   const uint64_t start[4] = {0x0123456789abcdefull, 0x1f, 0, 0};
   const u32 per_key = ((h->flags & ECL_ADDR33) ? 1 : 0) + ((h->flags & ECL_ADDR65) ? 1 : 0) + ((h->flags & ECL_P2SH) ? 1 : 0) +
-                      ((h->flags & ECL_ETH) ? 1 : 0);
+                      ((h->flags & ECL_ETH) ? 1 : 0) + ((h->flags & ECL_TR) ? 1 : 0);
   const u32 cap = N * per_key * ((h->flags & ECL_ENDO) ? 6 : 1);
   std::vector<ecl_found> recs(cap);
   u32 n = 0;
@@ -221,6 +228,7 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   std::vector<uint64_t> ks((size_t)N * 4), xs((size_t)N * 4), ys((size_t)N * 4);
   std::vector<uint32_t> r33((size_t)N * 5), r65((size_t)N * 5), rsh((size_t)N * 5), reth((size_t)N * 5);
   std::vector<uint8_t> eok(N);
+  std::vector<uint32_t> rtr((h->flags & ECL_TR) ? (size_t)N * 8 : 0);
   const u256 s = sc_pow2(h->offs);
   u256 cur = sc_reduce(u256_from(start));
   for (u32 i = 0; i < N; ++i) {
@@ -233,6 +241,8 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   if (rc == ECL_OK && (h->flags & ECL_P2SH)) rc = ecl_hip_p2sh_hash(h, (const uint32_t(*)[5])r33.data(), (uint32_t(*)[5])rsh.data(), N);
   // an ECL_ETH context: the walk's addresses against the window-table sum's (ecl_hip_verify_eth; (3) checks that sum against the double-and-add kernel)
   if (rc == ECL_OK && (h->flags & ECL_ETH)) rc = ecl_hip_verify_eth(h, (const uint64_t(*)[4])ks.data(), N, (uint32_t(*)[5])reth.data(), eok.data());
+  // an ECL_TR context: the walk's and k_tr_check's output keys against the window-table path's (ecl_hip_verify_tr)
+  if (rc == ECL_OK && (h->flags & ECL_TR)) rc = ecl_hip_verify_tr(h, (const uint64_t(*)[4])ks.data(), N, (uint32_t(*)[8])rtr.data(), eok.data());
   // restore the caller's state whatever happened
   if (h->d_bloom) (void)hipFree(h->d_bloom);
   h->d_bloom = save_bloom, h->bloom_words = save_words;
@@ -249,7 +259,7 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
     const ecl_found& f = recs[i];
     if (f.key_offset >= N) { good = false; break; }
     if (f.endo != 0) continue;  // the endomorphism images are covered by the parity tests; here: the walk itself
-    const uint32_t* want = f.compressed == 3 ? &reth[f.key_offset * 5] : f.compressed == 2 ? &rsh[f.key_offset * 5] : f.compressed ? &r33[f.key_offset * 5] : &r65[f.key_offset * 5];
+    const uint32_t* want = f.compressed == 4 ? &rtr[f.key_offset * 8] : f.compressed == 3 ? &reth[f.key_offset * 5] : f.compressed == 2 ? &rsh[f.key_offset * 5] : f.compressed ? &r33[f.key_offset * 5] : &r65[f.key_offset * 5];
     good = memcmp(f.h160, want, 20) == 0;
     ++seen;
   }

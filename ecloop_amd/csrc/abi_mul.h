@@ -144,6 +144,7 @@ static int ensure_multable(ecl_hip* h, u32 W) {
   return ECL_OK;
 }
 
+static u64 tr_checked_keys(const ecl_hip* h);
 extern "C" int ecl_hip_set_mul_window(ecl_hip* h, uint32_t bits) {
   if (!h || (bits != 0 && (bits < MUL_W_MIN || bits > MUL_W_MAX))) return ECL_E_ARG;
   h->mul_W_fixed = bits;
@@ -158,9 +159,7 @@ extern "C" int ecl_hip_get_mul_window(ecl_hip* h, uint32_t* bits) {
 // what a mul_batch of n scalars needs before its first copy: the window table of the width in force, the copy stream, the second
 // compute stream and the events, the device staging (MUL_NBUF buffers: the copy engine runs ahead of the kernels) and the parking
 // space of two pieces in flight - sized to the call, grown on demand
-static int mul_setup(ecl_hip* h, u32 n, u32 W) {
-  int rc;
-  if ((rc = ensure_multable(h, W)) != ECL_OK) return rc;
+static int mul_streams(ecl_hip* h) {
   if (!h->copy_stream) {
     HIPCHK(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
     HIPCHK(h, hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
@@ -171,6 +170,12 @@ static int mul_setup(ecl_hip* h, u32 n, u32 W) {
     HIPCHK(h, hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
     HIPCHK(h, hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming));
   }
+  return ECL_OK;
+}
+static int mul_setup(ecl_hip* h, u32 n, u32 W) {
+  int rc;
+  if ((rc = ensure_multable(h, W)) != ECL_OK) return rc;
+  if ((rc = mul_streams(h)) != ECL_OK) return rc;
   u32 want = 1u << 16;
   while (want < MUL_CHUNK && want < n) want <<= 1;
   if (want > h->kbuf_cap) {
@@ -194,6 +199,17 @@ static int mul_setup(ecl_hip* h, u32 n, u32 W) {
     for (int i = 0; i < 2; ++i) HIPCHK(h, hipMalloc(&h->d_multmp[i], ((size_t)want + MUL_R * 256u) * 36 * sizeof(u32)));
     h->kbuf_cap = want;
   }
+  if ((h->flags & ECL_TR) && h->trslab_mul_cap < h->kbuf_cap) {  // Taproot: a piece is its own slab, one per compute stream
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream2));
+    for (int i = 0; i < 2; ++i) {
+      if (h->d_trslab_mul[i]) HIPCHK(h, hipFree(h->d_trslab_mul[i]));
+      h->d_trslab_mul[i] = nullptr;
+    }
+    h->trslab_mul_cap = 0;
+    for (int i = 0; i < 2; ++i) HIPCHK(h, hipMalloc(&h->d_trslab_mul[i], (size_t)h->kbuf_cap * TR_SLAB_WORDS * sizeof(u32)));
+    h->trslab_mul_cap = h->kbuf_cap;
+  }
   return ECL_OK;
 }
 // threads and scalars per thread of one k_mul_check launch over m scalars: as many scalars per thread (one shared inversion, at most
@@ -207,6 +223,7 @@ static void mul_geometry(u32 m, u32* R_out, u32* nt_out) {
 }
 // one piece on compute stream `lane` (0: the context's stream, 1: the second one), parking space `lane`; short_round: one scalar per
 // thread fewer (the test hook ecl_hip_diag_drop_round - (R - 1) * nt < m, so the last round always holds scalars)
+static void tr_mul_launch_piece(ecl_hip* h, int lane, const u32* d_k, u32 m, u32 at, const wtab& gtab, const add_args& a, bool short_round);
 static void mul_launch_piece(ecl_hip* h, int lane, const u32* d_k, u32 m, u32 at, const wtab& gtab, const add_args& a, bool short_round) {
   u32 R, nt;
   hipStream_t st = lane ? h->stream2 : h->stream;
@@ -214,6 +231,10 @@ static void mul_launch_piece(ecl_hip* h, int lane, const u32* d_k, u32 m, u32 at
   mul_geometry(m, &R, &nt);
   if (short_round) R -= 1;
   dim3 grid(nt / 256), blk(256);
+  if (h->flags & ECL_TR) {  // alone (ecl_hip_open): two kernels (abi_tr.h)
+    tr_mul_launch_piece(h, lane, d_k, m, at, gtab, a, short_round);
+    return;
+  }
   if (h->flags & ECL_ETH) {  // alone (ecl_hip_open)
     hipLaunchKernelGGL(k_mul_check_eth, grid, blk, 0, st, d_k, m, at, gtab, a, tmp, nt, R);
     return;
@@ -376,6 +397,8 @@ extern "C" int ecl_hip_mul_batch(ecl_hip* h, const uint64_t (*scalars)[4], uint3
     HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));  // copies + kernels of this call, as the stream saw them
     h->mul_ms += ms, h->mul_calls += 1, h->mul_scalars += n;
     rc = check_coverage(h, "mul_batch", n, rc, nout);  // the counts of all pieces, summed on the device
+    if (rc != ECL_E_COVERAGE && (h->flags & ECL_TR) && tr_checked_keys(h) != n)  // Taproot: ... and the entries that reached k_tr_check's probe step
+      rc = coverage_failed(h, "mul_batch (Taproot, output keys)", n, tr_checked_keys(h), nout);
   }
   return count_call(h, n, rc);
 }
@@ -487,6 +510,7 @@ extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t t
     const u64 got = counted_keys(h);
     h->cov_device += got;
     if (got != n && !missed) missed = true, missed_got = got;
+    if ((h->flags & ECL_TR) && tr_checked_keys(h) != n && !missed) missed = true, missed_got = tr_checked_keys(h);
     if (flags[0] || !flags[1]) break;
   }
   if (flags[0]) {

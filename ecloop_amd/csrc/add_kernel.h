@@ -27,7 +27,7 @@
 struct ecl_found_dev {
   u64 key_offset;
   u32 h160[5];
-  u32 tag;  // byte 0 = endo, byte 1 = address type (ecl_found.compressed: 1 addr33, 0 addr65, 2 p2sh, 3 eth)
+  u32 tag;  // byte 0 = endo, byte 1 = address type (ecl_found.compressed: 1 addr33, 0 addr65, 2 p2sh, 3 eth, 4 p2tr)
 };
 
 struct add_args {
@@ -37,9 +37,15 @@ struct add_args {
   uint4* __restrict__ scratch;  // prefix products (9x29 limbs 0..7), [(k*2 + half) * T + lane]
   u32* __restrict__ scratch2;   // prefix products (limb 8), [k * T + lane]
   bloom_t bloom;
-  ecl_found_dev* found;
+  union {
+    ecl_found_dev* found;
+    u32* slab;  // the Taproot emit kernels (no filter, no records): where the points and tweaks go, TR_SLAB_WORDS words per key (tr_emit)
+  };
   u32* counter;
-  u32 cap;
+  union {
+    u32 cap;
+    u32 epoch;  // the Taproot emit kernels: 0 / 1, the mark of this launch's slab entries
+  };
   u32 B;      // table points per group (group = 2B keys)
   u32 T;      // lanes
   u32 nb;     // groups per lane in this launch
@@ -298,6 +304,59 @@ __device__ __forceinline__ void check_point(const add_args& a, cand_queues* q, b
   }
 }
 
+// ---- Taproot (BIP341 / BIP86 key path), stage A: what the emit kernels (k_add_tr, k_mul_points_tr) do with a point instead of hashing
+// and probing it.  The output key of P is the x of a SECOND point, Q = P' + t G with P' the even-y lift of P and t = taptweak(P.x), so a
+// key costs a fixed-base scalar multiplication: the point's entry - t (8 words, the layout of a `mul` scalar), P'.x, P'.y (canonical
+// words) - goes to a slab in HBM at the key's offset, and k_tr_check (tr_kernels.h) runs `mul`'s machinery over the slab.  96 bytes per
+// key, written as six 16-byte stores.  P'.y is even, so bit 0 of its first word is free: it carries the launch's epoch (0 / 1, the host
+// alternates it), by which stage B tells an entry of this launch from what an earlier one left there.  isinf (a `mul` scalar that is
+// 0 mod n): the entry is x = y = 0, which is no point - stage B counts it as a key without an output.
+#define TR_SLAB_WORDS 24u
+__device__ __forceinline__ void tr_emit(const add_args& a, bool have, bool isinf, fe x, fe y, u64 off) {
+  fe_normalize(x);
+  fe_normalize(y);
+  u32 xw[8], yw[8], t[8];
+  fe_to_words(xw, x);
+  fe_to_words(yw, y);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) xw[i] = isinf ? 0u : xw[i], yw[i] = isinf ? 0u : yw[i];
+  tr_lift_y(yw);
+  taptweak(t, xw);
+  if (have) {
+    uint4* e = (uint4*)(a.slab + (size_t)off * TR_SLAB_WORDS);
+    e[0] = make_uint4(t[0], t[1], t[2], t[3]), e[1] = make_uint4(t[4], t[5], t[6], t[7]);
+    e[2] = make_uint4(xw[0], xw[1], xw[2], xw[3]), e[3] = make_uint4(xw[4], xw[5], xw[6], xw[7]);
+    e[4] = make_uint4(yw[0] | a.epoch, yw[1], yw[2], yw[3]), e[5] = make_uint4(yw[4], yw[5], yw[6], yw[7]);
+  }
+}
+// the candidate rings for a kernel that reports ONE address type (k_tr_check: type 4, which the two bits the rings keep for the type
+// of the other kernels do not hold): the type is a constant of the kernel, the ring's tag is not read
+template <u32 TYPE>
+__device__ __forceinline__ void cand1_finish(const add_args& a, cand_queue& qb) {
+  bool valid;
+  const cand_rec r = cand_take(qb, valid);
+  const int from = bloom_mid_two(a.bloom) ? 3 : 2;
+  if (valid && bloom_probes_from(a.bloom, r.h, from)) found_push(a, r.off, r.h, 0, TYPE);
+}
+template <u32 TYPE>
+__device__ __forceinline__ void cand1_mid(const add_args& a, cand_queues& q) {
+  bool valid;
+  const cand_rec r = cand_take(q.a, valid);
+  const bool pass = valid && bloom_mid(a.bloom, r.h, bloom_mid_two(a.bloom));
+  if (cand_append(q.b, pass, r.off, r.h, 0)) cand1_finish<TYPE>(a, q.b);
+}
+template <u32 TYPE>
+__device__ __forceinline__ void cand1_check(const add_args& a, cand_queues& q, bool live, u64 off, const u32 h[5]) {
+  const bool pass = live && bloom_stage1(a.bloom, h);
+  if (cand_append(q.a, pass, off, h, 0)) cand1_mid<TYPE>(a, q);
+}
+template <u32 TYPE>
+__device__ __forceinline__ void cand1_flush(const add_args& a, cand_queues& q) {
+  cand1_mid<TYPE>(a, q);
+  cand1_finish<TYPE>(a, q.b);
+  cand1_finish<TYPE>(a, q.b);
+}
+
 // waves per SIMD the register allocator must leave room for (256-thread blocks: blocks per CU = this value).  Final kernel:
 // 2 is 2 % slower, 5 is 0.9 % and 6 is 4.8 % slower, 4 is 0.2-0.5 % faster than 3 except for -a cu -endo (0.4 % slower: it
 // stays at 3); -a u -endo spills inside its per-point loop at 4 (17 scratch instructions per table point), so it takes 3 as well
@@ -340,5 +399,17 @@ __device__ __forceinline__ void check_point(const add_args& a, cand_queues* q, b
 #include "add_walk.inc"
 #undef ECL_WALK_KERNEL
 #undef ECL_WALK_ETH
+#undef ECL_WALK_P2SH
+#undef ECL_WALK_WAVES
+// Taproot emit instantiation: k_add_tr, the walk with tr_emit in place of the hash-and-probe step (no rings, no filter; it still counts
+// the keys it emits).  Taproot is searched alone and without the endomorphism (ecl_hip_open), so one kernel.
+#define ECL_TR_WAVES 4
+#define ECL_WALK_KERNEL k_add_tr
+#define ECL_WALK_TR
+#define ECL_WALK_P2SH false
+#define ECL_WALK_WAVES ECL_TR_WAVES
+#include "add_walk.inc"
+#undef ECL_WALK_KERNEL
+#undef ECL_WALK_TR
 #undef ECL_WALK_P2SH
 #undef ECL_WALK_WAVES

@@ -2,7 +2,9 @@
 // k_add_p2sh (the same sets plus P2SH, and P2SH alone).  Included with ECL_WALK_KERNEL (the kernel's name), ECL_WALK_P2SH and
 // ECL_WALK_WAVES (waves per SIMD of an instantiation, an expression of A33 / A65 / ENDO) defined; no include guard on purpose.
 // With ECL_WALK_ETH defined as well the kernel is k_add_eth<ENDO>: the Ethereum address alone (ECL_WALK_WAVES an expression of ENDO).
-#ifdef ECL_WALK_ETH
+// With ECL_WALK_TR defined the kernel is k_add_tr (no template): the Taproot emit kernel, tr_emit in place of check_point, no rings.
+#if defined(ECL_WALK_TR)
+#elif defined(ECL_WALK_ETH)
 template <bool ENDO>
 #else
 template <bool A33, bool A65, bool ENDO>
@@ -13,12 +15,17 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
 #else
   constexpr bool ETH = false;
 #endif
+#ifdef ECL_WALK_TR
+  cand_queues q;  // (the key count alone)
+  q.keys = 0;
+#else
   constexpr bool P2SH = ECL_WALK_P2SH || ETH;  // (for the rings: the record's type field keeps two bits)
   __shared__ u32 q_mem[ECL_ADD_BLOCK / 64][2][8 * ECL_Q_SLOTS];  // two candidate rings per wave
   cand_queues q;
   q.a.mem = q_mem[threadIdx.x >> 6][0], q.a.head = 0, q.a.count = 0;
   q.b.mem = q_mem[threadIdx.x >> 6][1], q.b.head = 0, q.b.count = 0;
   q.keys = 0;
+#endif
   const u32 g = blockIdx.x * (u32)ECL_ADD_BLOCK + threadIdx.x;
   const u32 T = a.T, B = a.B;
   if (g >= T) return;  // (never taken: T is a multiple of the block size)
@@ -95,7 +102,11 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
         if (valid) {
           const bool live = off < a.nkeys;
           keys_count(q, live);
+#ifdef ECL_WALK_TR
+          tr_emit(a, live, false, px, py, off);
+#else
           check_point<A33, A65, ECL_WALK_P2SH, ENDO, ETH>(a, &q, live, px, py, off);
+#endif
         }
       }
     }
@@ -113,7 +124,9 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
     fe_normalize_weak(Yn);
     X = Xn, Y = Yn;
   }
+#ifndef ECL_WALK_TR
   cand_flush<P2SH>(a, q);
+#endif
   keys_flush(a, q);
   fe_st_words2(a.cxy + g, plane, X);
   fe_st_words2(a.cxy + 2 * (size_t)T + g, plane, Y);

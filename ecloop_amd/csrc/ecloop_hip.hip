@@ -24,11 +24,12 @@
 #include "abi_lookahead_ctx.h"
 #include "setup_kernels.h"
 #include "mul_kernels.h"
+#include "tr_kernels.h"
 #include "aux_kernels.h"
 
 // ------------------------------------------------------------------------------------------------ context
 
-#define ECL_COUNTER_WORDS 6u  /* d_counter: see ecl_hip_open */
+#define ECL_COUNTER_WORDS 8u  /* d_counter: see ecl_hip_open */
 
 struct ecl_hip {
   int dev = 0;
@@ -57,6 +58,11 @@ struct ecl_hip {
   uint64_t mul_seen = 0;                       // scalars this context has multiplied (never reset: the automatic width goes by it)
   bool mul_long_failed = false;                // the long table could not be allocated: do not try again
   void* d_ver = nullptr; u32 ver_cap = 0;      // staging of ecl_hip_verify
+  // Taproot (ECL_TR): the slab of `add` (t, P' of up to one slab of keys, 96 bytes each) and the parking space of its k_tr_check; one slab
+  // per compute stream for the pieces of `mul`; the mark the next emit launch gives its entries (tr_emit)
+  u32* d_trslab = nullptr; u64 trslab_cap = 0; u32* d_trtmp[2] = {}; u64 trtmp_words = 0;
+  u32* d_trslab_mul[2] = {}; u32 trslab_mul_cap = 0;
+  u32 tr_epoch = 0, tr_epoch_mul[2] = {};
   u32* d_rawtext = nullptr; size_t rawtext_cap = 0; u64* d_rawlines = nullptr; u32 rawlines_cap = 0;  // `mul -raw`: text and line table of one call
   hipStream_t copy_stream = nullptr, stream2 = nullptr;  // `mul`: the copy engine's stream; the second compute stream (pieces alternate)
   hipEvent_t ev_copied[MUL_NBUF] = {}, ev_free[MUL_NBUF] = {}, ev_fork = nullptr, ev_join = nullptr;
@@ -136,8 +142,9 @@ const char* ecl_hip_last_error(const ecl_hip* h) { return h ? h->err.c_str() : "
 
 int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   const u32 types = ECL_ADDR33 | ECL_ADDR65 | ECL_P2SH;
-  if (!out || ord_offs > 255 || !(flags & (types | ECL_ETH)) || (flags & ~(types | ECL_ETH | ECL_ENDO))) return ECL_E_ARG;
+  if (!out || ord_offs > 255 || !(flags & (types | ECL_ETH | ECL_TR)) || (flags & ~(types | ECL_ETH | ECL_TR | ECL_ENDO))) return ECL_E_ARG;
   if ((flags & ECL_ETH) && (flags & types)) return ECL_E_ARG;  // eth is searched alone
+  if ((flags & ECL_TR) && flags != ECL_TR) return ECL_E_ARG;   // Taproot is searched alone and without the endomorphism
   int n = ecl_hip_device_count();
   if (device < 0 || device >= n) return ECL_E_NODEV;
   ecl_hip* h = new ecl_hip();
@@ -152,6 +159,7 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   HIPCHK(h, hipMalloc(&h->d_aux, 34 * 16 * sizeof(u32)));
   HIPCHK(h, hipMalloc(&h->d_auxk, 34 * 8 * sizeof(u32)));
   // [0] records appended, [1] records confirmed by the list, [2] [3] input flags of mul_batch_raw, [4] [5] the u64 count of keys hashed
+  // (Taproot: of points emitted), [6] [7] Taproot: the u64 count of slab entries that reached k_tr_check's probe step
   HIPCHK(h, hipMalloc(&h->d_counter, ECL_COUNTER_WORDS * sizeof(u32)));
   HIPCHK(h, hipHostMalloc((void**)&h->pin_counter, ECL_COUNTER_WORDS * sizeof(u32), hipHostMallocDefault));
   // the self-test checks the CODE (known answers, walk kernel against the double-and-add kernel): once per process
@@ -159,7 +167,7 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   static std::mutex mu;
   static std::set<u32> passed;
   const char* skip = getenv("ECL_HIP_SKIP_SELFTEST");
-  const u32 key = (u32)device * 128u + flags;  // flags < 128
+  const u32 key = (u32)device * 256u + flags;  // flags < 256
   {
     std::lock_guard<std::mutex> lk(mu);
     if ((skip && skip[0] == '1') || passed.count(key)) return ECL_OK;
@@ -194,6 +202,7 @@ void ecl_hip_close(ecl_hip* h) {
   if (h->prep_stream) (void)hipStreamDestroy(h->prep_stream);
   if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
   if (h->ev_join) (void)hipEventDestroy(h->ev_join);
+  (void)hipFree(h->d_trslab), (void)hipFree(h->d_trtmp[0]), (void)hipFree(h->d_trtmp[1]), (void)hipFree(h->d_trslab_mul[0]), (void)hipFree(h->d_trslab_mul[1]);
   (void)hipFree(h->d_multmp[0]), (void)hipFree(h->d_multmp[1]), (void)hipFree(h->d_ver), (void)hipFree(h->d_rawtext), (void)hipFree(h->d_rawlines);
   release_multable(h);
   if (h->ev_s0) (void)hipEventDestroy(h->ev_s0);
@@ -400,6 +409,7 @@ typedef void (*add_kernel_t)(const add_args);
 // every non-empty set of address types (ecl_hip_open refuses the empty one) x endo
 static add_kernel_t pick_add_kernel(u32 flags) {
   const bool endo = flags & ECL_ENDO;
+  if (flags & ECL_TR) return k_add_tr;  // alone, no endomorphism (ecl_hip_open): the emit kernel
   if (flags & ECL_ETH) return endo ? k_add_eth<true> : k_add_eth<false>;  // alone (ecl_hip_open)
   switch (flags & (ECL_ADDR33 | ECL_ADDR65 | ECL_P2SH)) {
   case ECL_ADDR33: return endo ? k_add<true, false, true> : k_add<true, false, false>;
@@ -669,6 +679,8 @@ static int ensure_walk_buffers(ecl_hip* h, u32 B, u32 T) {
 }
 
 static int ensure_gtable(ecl_hip* h);
+static int tr_reserve(ecl_hip* h, uint64_t nkeys);
+static int tr_add_core(ecl_hip* h, const u256& k0, uint64_t nkeys, ecl_found* out, uint32_t cap, uint32_t* nout);
 
 extern "C" int ecl_hip_reserve(ecl_hip* h, uint64_t nkeys, uint32_t cap) {
   if (!h || nkeys == 0 || cap > ECL_CAP_MAX) return ECL_E_ARG;
@@ -680,6 +692,7 @@ extern "C" int ecl_hip_reserve(ecl_hip* h, uint64_t nkeys, uint32_t cap) {
   if (!nkeys_ok(h, nkeys)) return ECL_E_ARG;
   const u32 rcap = raw_cap_of(h, cap ? cap : 1);
   if ((rc = ensure_found(h, found_words_of(h, rcap))) != ECL_OK) return rc;
+  if (h->flags & ECL_TR) return tr_reserve(h, nkeys);
   u32 B, nb, T;
   call_geometry(h, nkeys, B, nb, T);
   return ensure_walk_buffers(h, B, T);
@@ -687,8 +700,10 @@ extern "C" int ecl_hip_reserve(ecl_hip* h, uint64_t nkeys, uint32_t cap) {
 
 // one launch of the search kernel over exactly the keys k0, k0 + s, ..., k0 + (nkeys - 1) s  (k0 reduced mod n): the body of
 // ecl_hip_add_range; the look-ahead (abi_lookahead.h) calls it with a sweep instead of the caller's job
-static int add_core(ecl_hip* h, const u256& k0, uint64_t nkeys, ecl_found* out, uint32_t cap, uint32_t* nout) {
-  *nout = 0;
+// the launch itself: geometry, buffers, the walk positioned at k0 (or continued), the kernel queued on h->stream.  own_call: the launch
+// is a call of its own (counters reset and ev0 recorded in front of it); a Taproot call queues one launch per slab between its own
+// reset and read-back, each into `slab` with the mark `epoch` (tr_emit).  *cont: the resident walk was continued; *walked: keys the launch walks
+static int add_launch(ecl_hip* h, const u256& k0, uint64_t nkeys, u32 rcap, bool own_call, u32* slab, u32 epoch, bool* cont_out, u64* walked_out) {
   int rc;
   if ((rc = default_lanes(h)) != ECL_OK) return rc;
   if (!nkeys_ok(h, nkeys)) {
@@ -696,9 +711,6 @@ static int add_core(ecl_hip* h, const u256& k0, uint64_t nkeys, ecl_found* out, 
     return ECL_E_ARG;
   }
   if ((rc = ensure_table(h)) != ECL_OK) return rc;
-  h->last_held = h->last_total = 0, h->last_from_host = false;  // the records of the call before are about to be overwritten
-  const u32 rcap = raw_cap_of(h, cap ? cap : 1);
-  if ((rc = ensure_found(h, found_words_of(h, rcap))) != ECL_OK) return rc;
 
   u32 B, nb, T;
   call_geometry(h, nkeys, B, nb, T);
@@ -775,12 +787,30 @@ static int add_core(ecl_hip* h, const u256& k0, uint64_t nkeys, ecl_found* out, 
   a.cxy = h->d_cxy, a.scratch = h->d_scr, a.scratch2 = h->d_scr2;
   a.bloom = bloom_make(h->d_bloom, h->bloom_words);
   a.found = h->d_found, a.counter = h->d_counter, a.cap = rcap, a.keys = (unsigned long long*)(h->d_counter + 4);
+  if (slab) a.slab = slab, a.epoch = epoch;
   a.B = B, a.T = T, a.nb = nb, a.nkeys = nkeys;
   if (h->diag_drop) h->diag_drop = false, a.nb = nb - 1;  // (test hook: lane 0's last group is in the range, so keys go missing)
-  HIPCHK(h, hipMemsetAsync(h->d_counter, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  if (own_call) {
+    HIPCHK(h, hipMemsetAsync(h->d_counter, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  }
   hipLaunchKernelGGL(pick_add_kernel(h->flags), dim3(T / ECL_ADD_BLOCK), dim3(ECL_ADD_BLOCK), 0, h->stream, a);
   HIPCHK(h, hipGetLastError());
+  *cont_out = cont, *walked_out = (u64)nb * T * group;
+  return ECL_OK;
+}
+
+static int add_core(ecl_hip* h, const u256& k0, uint64_t nkeys, ecl_found* out, uint32_t cap, uint32_t* nout) {
+  *nout = 0;
+  if (h->flags & ECL_TR) return tr_add_core(h, k0, nkeys, out, cap, nout);
+  int rc;
+  h->last_held = h->last_total = 0, h->last_from_host = false;  // the records of the call before are about to be overwritten
+  const u32 rcap = raw_cap_of(h, cap ? cap : 1);
+  if ((rc = ensure_found(h, found_words_of(h, rcap))) != ECL_OK) return rc;
+  bool cont = false;
+  u64 walked = 0;
+  if ((rc = add_launch(h, k0, nkeys, rcap, true, nullptr, 0, &cont, &walked)) != ECL_OK) return rc;
+  const u256 s = sc_pow2(h->offs);
   HIPCHK(h, hipEventRecord(h->ev1, h->stream));
   u32 cnt = 0;
   rc = collect_found(h, cap, rcap, out, &cnt, true);
@@ -795,7 +825,6 @@ static int add_core(ecl_hip* h, const u256& k0, uint64_t nkeys, ecl_found* out, 
   if (check_coverage(h, "add_range", nkeys, rc, nout) == ECL_E_COVERAGE) return ECL_E_COVERAGE;
 
   // the centres now sit at the start of group nb*T + g: valid continuation only if the launch was exact
-  const u64 walked = (u64)nb * T * group;
   h->walk_valid = walked == nkeys;
   if (h->walk_valid) h->walk_next = sc_add(k0, sc_mul_u64(s, walked));
   *nout = cnt;
@@ -842,4 +871,5 @@ extern "C" int ecl_hip_add_range(ecl_hip* h, const uint64_t start[4], uint64_t n
 }
 
 #include "abi_mul.h"
+#include "abi_tr.h"
 #include "abi_diag.h"

@@ -254,6 +254,44 @@ H_FN void hash160_p2sh(u32 h[5], const u32 h33[5]) {
   sha256_iv_22(st, m);
   rmd160_of_sha(h, st);
 }
+// Taproot (BIP341 / BIP86 key path, no script tree): t = SHA-256(T || T || x), T = SHA-256("TapTweak").  T || T is one whole block, so
+// its state is a constant and a key costs ONE compression: the 32 bytes of x, the pad byte, zeros and the length 96 * 8 as literals
+// (the form of hash160_p2sh's fixed block).  x: 8 canonical little-endian words; t: the digest read as a big-endian number, 8
+// little-endian words (the layout a `mul` scalar has).
+H_FN void taptweak(u32 t[8], const u32 x[8]) {
+  u32 st[8] = {0xd129a2f3u, 0x701c655du, 0x6583b6c3u, 0xb9419727u, 0x95f4e232u, 0x94fd54f4u, 0xa2ae8d85u, 0x47ca590bu};
+  u32 w[16];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) w[i] = x[7 - i];
+  w[8] = 0x80000000u;
+#pragma unroll
+  for (int i = 9; i < 15; ++i) w[i] = 0;
+  w[15] = 96 * 8;
+  sha256_compress(st, w);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) t[i] = st[7 - i];
+}
+// t >= n (the group order): such a key has no Taproot output (BIP341 fails it; probability 2^-128).  t: 8 little-endian words.
+H_FN bool tr_tweak_ge_n(const u32 t[8]) {
+  const u32 nw[8] = {0xD0364141u, 0xBFD25E8Cu, 0xAF48A03Bu, 0xBAAEDCE6u, 0xFFFFFFFEu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+  u32 borrow = 0;  // of t - n
+#pragma unroll
+  for (int i = 0; i < 8; ++i) borrow = (t[i] < nw[i]) | ((t[i] == nw[i]) & borrow);
+  return !borrow;
+}
+// the even-y lift of an affine point (BIP340 lift_x of its x): y stays if it is even, else p - y = ~y + (p + 1) (mod 2^256), under a
+// mask (the form of the ETH branch of check_point).  y: 8 canonical little-endian words, y != 0.
+H_FN void tr_lift_y(u32 y[8]) {
+  const u32 m = 0u - (y[0] & 1u);
+  const u32 p1[8] = {0xFFFFFC30u, 0xFFFFFFFEu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+  u64 c = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    c += (u64)(y[i] ^ m) + (p1[i] & m);
+    y[i] = (u32)c;
+    c >>= 32;
+  }
+}
 // hash160 of the uncompressed key 04 || X || Y  (lib/addr.c:47-67, 116-131)
 H_FN void hash160_65(u32 h[5], const u32 x[8], const u32 y[8]) {
   u32 w[16], st[8];

@@ -1,7 +1,8 @@
 // mul_check.inc - the body of the `mul` kernel, instantiated twice by mul_kernels.h: as k_mul_check (address types addr33 / addr65)
 // and as k_mul_check_p2sh (the same sets plus P2SH, and P2SH alone), like add_walk.inc.  Included with ECL_MUL_KERNEL and ECL_MUL_P2SH
 // defined; no include guard on purpose.  With ECL_MUL_ETH defined as well the kernel is k_mul_check_eth: the Ethereum address alone.
-#ifndef ECL_MUL_ETH
+// With ECL_MUL_TR defined the kernel is k_mul_points_tr: the Taproot emit kernel, tr_emit in place of check_point, no rings.
+#if !defined(ECL_MUL_ETH) && !defined(ECL_MUL_TR)
 template <bool A33, bool A65>
 #endif
 __global__ void __launch_bounds__(256, ECL_MUL_WAVES) ECL_MUL_KERNEL(const u32* __restrict__ k, u32 n, u32 base, const wtab gtab, add_args a,
@@ -11,8 +12,10 @@ __global__ void __launch_bounds__(256, ECL_MUL_WAVES) ECL_MUL_KERNEL(const u32* 
 #else
   constexpr bool ETH = false;
 #endif
+#ifndef ECL_MUL_TR
   constexpr bool P2SH = ECL_MUL_P2SH || ETH;  // (for the rings: the record's type field keeps two bits)
   __shared__ u32 q_mem[4][2][8 * ECL_Q_SLOTS];  // two candidate rings per wave (add_kernel.h)
+#endif
   const u32 t = blockIdx.x * 256u + threadIdx.x;
   if (t >= nt) return;  // nt is a multiple of 256: whole workgroups leave
   fe prod = fe_one();
@@ -53,8 +56,10 @@ __global__ void __launch_bounds__(256, ECL_MUL_WAVES) ECL_MUL_KERNEL(const u32* 
   // comes along with live = false and leaves the inversion chain alone - so that the rings' wave-uniform state stays uniform
   // (+1.7 % at the .blf design density against finishing every hash's test in place, profiles/r04_mul_rings.txt)
   cand_queues q;
+#ifndef ECL_MUL_TR
   q.a.mem = q_mem[threadIdx.x >> 6][0], q.a.head = 0, q.a.count = 0;
   q.b.mem = q_mem[threadIdx.x >> 6][1], q.b.head = 0, q.b.count = 0;
+#endif
   q.keys = 0;
 #pragma unroll 1
   for (u32 r = R; r-- > 0;) {
@@ -72,8 +77,13 @@ __global__ void __launch_bounds__(256, ECL_MUL_WAVES) ECL_MUL_KERNEL(const u32* 
     inv = ninv;
     fe_mul_pair(x, y, X, ti, Y, ti);
     keys_count(q, have);  // a scalar whose point is at infinity counts: it has nothing to hash
+#ifdef ECL_MUL_TR
+    tr_emit(a, have, (infmask >> r) & 1u, x, y, (u64)base + i);  // (base = 0: the piece is its own slab)
+  }
+#else
     check_point<A33, A65, ECL_MUL_P2SH, false, ETH>(a, &q, have && !((infmask >> r) & 1u), x, y, (u64)base + i);
   }
   cand_flush<P2SH>(a, q);
+#endif
   keys_flush(a, q);
 }

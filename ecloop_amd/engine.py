@@ -234,19 +234,24 @@ class KeySearch:
     """ctx_t + cmd_add / cmd_mul for one GPU."""
 
     def __init__(self, flt, device=0, a33=True, a65=False, endo=False, ord_offs=0, verify=True, launch_keys=1 << 32,
-                 half_group=0, max_lanes=0, device_cls=None, p2sh=False, eth=False):
-        if eth:
+                 half_group=0, max_lanes=0, device_cls=None, p2sh=False, eth=False, tr=False):
+        if tr:
+            a33 = False  # Taproot is searched alone and without the endomorphism (the context refuses anything beside it)
+        elif eth:
             a33 = False  # eth is searched alone (any other type beside it: the context refuses)
         elif not (a33 or a65 or p2sh):
             a33 = True  # main.c:825-827
         self.flt, self.a33, self.a65, self.endo, self.offs, self.verify = flt, a33, a65, endo, ord_offs, verify
         self.p2sh = p2sh  # P2SH-P2WPKH (no reference counterpart): records labelled "p2sh"
         self.eth = eth  # Ethereum addresses (no reference counterpart either): records labelled "eth"
+        self.tr = tr  # Taproot output keys (BIP341 / BIP86 key path): records labelled "p2tr", h160 = the leading 20 bytes of the key
         self.stride = 1 << ord_offs
         # device_cls: the GPU context (capi.Device); the CPU tests of the host logic pass a stand-in with the same surface
         kw = {"p2sh": True} if p2sh else {}  # (a stand-in without the P2SH type keeps working for the other types)
         if eth:
             kw["eth"] = True
+        if tr:
+            kw["tr"] = True
         self.dev = (device_cls or Device)(device, a33=a33, a65=a65, endo=endo, ord_offs=ord_offs, **kw)
         if half_group or max_lanes:
             self.dev.set_geometry(half_group, max_lanes)
@@ -266,6 +271,16 @@ class KeySearch:
     def _verify(self, recs):
         if not recs:
             return
+        tr = [r for r in recs if r.label == "p2tr"]
+        if tr:  # the first 20 bytes of the re-derived output key against the record, which then carries all 32
+            qx, ok = self.dev.verify_tr([r.pk for r in tr])
+            for i, r in enumerate(tr):
+                if not ok[i] or [int(v) for v in qx[i][:5]] != [int(v) for v in r.h160[:5]]:
+                    raise EclError("[!] error: hash mismatch (%s) pk: %064x" % (r.label, r.pk))
+                r.h160 = [int(v) for v in qx[i]]
+            recs = [r for r in recs if r.label != "p2tr"]
+            if not recs:
+                return
         eth = [r for r in recs if r.label == "eth"]
         if eth:
             addr, ok = self.dev.verify_eth([r.pk for r in eth])
@@ -337,11 +352,14 @@ class KeySearch:
             ks = scalars[at : at + chunk]
             c = max(cap, 2 * len(ks))
             raw, total = self.dev.mul_batch(ks, cap=c)
+            new = []
             for r in raw:
                 if self.flt.confirm(r["h160"]):
-                    self.found.append(FoundRecord(label_of(r["compressed"]), [int(v) for v in r["h160"]],
-                                                  ks[int(r["key_offset"])]))
+                    new.append(FoundRecord(label_of(r["compressed"]), [int(v) for v in r["h160"]], ks[int(r["key_offset"])]))
                     self.k_found += 1
+            if self.tr and self.verify:
+                self._verify(new)  # (a p2tr record gets its whole output key from the verification)
+            self.found.extend(new)
             self.k_checked += len(ks)
         return self.found
 

@@ -93,12 +93,26 @@ static bool hash160_from_hex(const char *s, u32 h[5]) {
    Ethereum lists (no reference counterpart): address dumps write `0x` in front of the 40 digits, a line of 42 characters whose 40-character
    piece is never clean hex - no entry at all, silently.  With `-a e` on the command line (list_skip_0x; never otherwise) a line that starts
    with 0x / 0X is walked from its third character.  EIP-55 mixed-case digits decode like any others (hash160_from_hex, both paths). */
-static bool list_skip_0x;
+/* Taproot lists (no reference counterpart): a line is the 64 hex digits of an output key and its entry the leading 40 of them - what the
+   rule above already makes of such a line, so .blf files and the default reader are as they were.  With `-a t` on the command line
+   (list_strict_64; never otherwise) ONLY lines of exactly 64 clean hex digits are entries: a hash160 list given by mistake then ends in
+   "no hashes in filter file" instead of a search that can find nothing. */
+static bool list_skip_0x, list_strict_64;
 static size_t hashlist_entries(const char *text, size_t len, u32 *out) {
   size_t n = 0;
   for (size_t at = 0; at < len;) {
     const char *nl = memchr(text + at, '\n', len - at);
     size_t eol = nl ? (size_t)(nl - text) : len;
+    if (list_strict_64) {
+      u32 tail[5];
+      char pad[40];
+      if (eol - at == 64) {
+        memset(pad, '0', 16), memcpy(pad + 16, text + at + 40, 24); /* the last 24 digits checked through the same decoder */
+        if (hash160_from_hex(pad, tail) && hash160_from_hex(text + at, out + n * 5)) n++;
+      }
+      at = eol + 1;
+      continue;
+    }
     if (list_skip_0x && at + 2 <= eol && text[at] == '0' && (text[at + 1] == 'x' || text[at + 1] == 'X')) at += 2;
     for (size_t p = at; p + 40 <= eol; p += 40)
       if (hash160_from_hex(text + p, out + n * 5)) n++;

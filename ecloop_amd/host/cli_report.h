@@ -42,12 +42,14 @@ static void status_show_locked(report_t *r) {
   fflush(stderr);
 }
 /* one found key: "addr33: <hash160> <- <key>" on stdout, "addr33\t<hash160>\t<key>" in the file; counts it.  type: the address type of
-   ecl_found.compressed (1 addr33, 0 addr65, 2 p2sh, 3 eth - the last two have no reference counterpart, their labels are this program's) */
-static void report_hit(report_t *r, u8 type, const u32 h160[5], const sc *key) {
-  char hh[41], kk[65];
-  hex_of_words(hh, h160, 5);
+   ecl_found.compressed (1 addr33, 0 addr65, 2 p2sh, 3 eth, 4 p2tr - the last three have no reference counterpart, their labels are this
+   program's).  A p2tr hit is printed with all 32 bytes of its output key (h: the eight words of ecl_hip_verify_tr), the others with the 20
+   bytes of the record */
+static void report_hit(report_t *r, u8 type, const u32 *h, const sc *key) {
+  char hh[65], kk[65];
+  hex_of_words(hh, h, type == 4 ? 8 : 5);
   hex_of_scalar(kk, key);
-  const char *label = type == 3 ? "eth" : type == 2 ? "p2sh" : type ? "addr33" : "addr65";
+  const char *label = type == 4 ? "p2tr" : type == 3 ? "eth" : type == 2 ? "p2sh" : type ? "addr33" : "addr65";
   const struct { FILE *to; const char *fmt; } dest[2] = {{r->quiet ? NULL : stdout, "%s: %s <- %s\n"}, {r->file, "%s\t%s\t%s\n"}};
   pthread_mutex_lock(&r->mu);
   for (int d = 0; d < 2; ++d) {
@@ -98,7 +100,7 @@ typedef struct run_t {
   report_t rep;
   int ngpus; /* device contexts (threads); `mul` opens two per GPU */
   ecl_hip *dev[MAX_GPUS];
-  bool a33, a65, p2sh, eth, endo, colour, bin, parse_only, seeded;
+  bool a33, a65, p2sh, eth, tr, endo, colour, bin, parse_only, seeded;
   sc range_s, range_e, stride_k;
   u32 ord_offs, ord_size;
 } run_t;
@@ -119,7 +121,8 @@ static void die_ecl(run_t *run, int g, int rc, const char *what) {
 /* pk_verify_hash (main.c:248-263) for all hits of one device call at once: both hash160 values of every reported key are
    derived again on the device by the window-table sum (ecl_hip_verify: not the walk kernel; own inversion per key) and
    compared with what the walk reported; a p2sh hit is compared with the script hash of that addr33 hash (ecl_hip_p2sh_hash);
-   an eth hit with the address ecl_hip_verify_eth derives from the key (an eth run has no other hits);
+   an eth hit with the address ecl_hip_verify_eth derives from the key (an eth run has no other hits); a p2tr hit with the first 20 bytes
+   of the output key ecl_hip_verify_tr derives (a Taproot run has no other hits), whose 32 bytes go to tr_qx for the found line;
    a mismatch is fatal, with the reference's diagnostics */
 static void verify_fail(const sc *key, const ecl_found *hit, const u32 *want) {
   char kk[65], lh[41], rh[41];
@@ -127,8 +130,17 @@ static void verify_fail(const sc *key, const ecl_found *hit, const u32 *want) {
   fprintf(stderr, "[!] error: hash mismatch (compressed: %d endo: %d)\npk: %s\nlh: %s\nrh: %s\n", hit->compressed, hit->endo, kk, lh, rh);
   exit(1);
 }
-static void verify_hits(run_t *run, int g, const sc *keys, const ecl_found *hits, u32 n) {
+static void verify_hits(run_t *run, int g, const sc *keys, const ecl_found *hits, u32 n, u32 (*tr_qx)[8]) {
   if (!n) return;
+  if (run->tr) {
+    u8 *fin = malloc(n);
+    int rc = ecl_hip_verify_tr(run->dev[g], (const uint64_t(*)[4])keys, n, tr_qx, fin);
+    if (rc != ECL_OK) die_ecl(run, g, rc, "verify");
+    for (u32 i = 0; i < n; ++i)
+      if (hits[i].compressed != 4 || !fin[i] || memcmp(tr_qx[i], hits[i].h160, 20)) verify_fail(&keys[i], &hits[i], tr_qx[i]);
+    free(fin);
+    return;
+  }
   if (run->eth) {
     u32 (*addr)[5] = malloc((size_t)n * 20);
     u8 *fin = malloc(n);

@@ -33,7 +33,7 @@
  * section 3 (sweeps and their records belong to the group of contexts that share a filter; one mutex per group; records are immutable
  * once published).  ecl_hip_strerror returns static text; ecl_hip_last_error returns the handle's own buffer (same thread rule).
  *
- * Exports: exactly the 42 ecl_hip_* functions declared below (the library is linked with a version script; `nm -D` shows nothing else).
+ * Exports: exactly the 44 ecl_hip_* functions declared below (the library is linked with a version script; `nm -D` shows nothing else).
  */
 #ifndef ECLOOP_HIP_H
 #define ECLOOP_HIP_H
@@ -56,12 +56,25 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
    x || y of the uncompressed key.  Eth is searched ALONE: ECL_ETH together with ECL_ADDR33, ECL_ADDR65 or ECL_P2SH is ECL_E_ARG (a Bitcoin
    list and an Ethereum list are different files), with or without ECL_ENDO.  So the valid type sets are: any non-empty subset of the three
    Bitcoin types, or ECL_ETH by itself.  (ecl_hip_open leaves no handle to ask after ECL_E_ARG - this comment is the message.)  The bits 8
-   and 32 stay refused as unknown flags. */
+   and 32 stay refused as unknown flags.
+   ECL_TR (no reference counterpart): Taproot, the BIP341 / BIP86 key-path output ("bc1p..." addresses) of the key with no script tree.  Its
+   output key is not a hash of the public key P but the x of a second point, Q = P' + t G with P' the even-y lift of P and
+   t = SHA-256(T || T || P.x), T = SHA-256("TapTweak"); a key with t >= n has no output (probability 2^-128: it counts as covered and is
+   not probed).  Filters, lists and records keep their 20-byte entries: a Taproot entry is the LEADING 20 BYTES of the 32-byte output key
+   (160 bits, the strength every other type is matched at); the caller verifies a hit with ecl_hip_verify_tr, which gives all 32.  k and
+   n - k have the same output key; the key reported is the one that was walked.  Taproot is searched alone and without the endomorphism:
+   ECL_TR together with any of ECL_ADDR33, ECL_ADDR65, ECL_P2SH, ECL_ETH or ECL_ENDO is ECL_E_ARG (a Taproot list is a different file;
+   the endomorphism amortises the walk, which is a few per cent of a Taproot key, and its (x, -y) images have the same output key).
+   A Taproot key costs one fixed-base scalar multiplication, about what a `mul` scalar costs: ecl_hip_add_range walks a call in slabs
+   (2^26 keys: the points and tweaks of a slab are parked in 6.4 GB of HBM, then multiplied on the `mul` table of the context;
+   environment ECL_HIP_TR_SLAB_LOG2 = 12 ... 28 changes the slab, not the results), and tweaked keys count as scalars for the width
+   of that table. */
 #define ECL_ADDR33 1u
 #define ECL_ADDR65 2u
 #define ECL_ENDO 4u
 #define ECL_P2SH 16u
 #define ECL_ETH 64u
+#define ECL_TR 128u
 
 /* return codes */
 #define ECL_OK 0
@@ -84,7 +97,8 @@ typedef struct ecl_found {
   uint32_t h160[5];
   uint8_t endo;
   uint8_t compressed; /* the address type: 1 = addr33, 0 = addr65, 2 = P2SH-P2WPKH (only for a context opened with ECL_P2SH),
-                         3 = Ethereum (ECL_ETH; h160 holds the address) */
+                         3 = Ethereum (ECL_ETH; h160 holds the address), 4 = Taproot (ECL_TR, label p2tr; h160 holds the leading
+                         20 bytes of the output key) */
   uint8_t pad[2];
 } ecl_found; /* 32 bytes */
 
@@ -172,6 +186,12 @@ int ecl_hip_p2sh_hash(ecl_hip *h, const uint32_t (*h33)[5], uint32_t (*out)[5], 
    not the walk kernel), ok[i] = 0 for k = 0 (mod n).  A caller verifies a type-3 hit with it.  Any context can be asked, whatever its flags. */
 int ecl_hip_verify_eth(ecl_hip *h, const uint64_t (*k)[4], uint32_t n, uint32_t (*addr)[5], uint8_t *ok);
 
+/* ... and its Taproot half: qx[i] = the 32-byte output key of k[i] as eight big-endian words (the h160_t convention continued: word j =
+   bytes 4j..4j+3), by ecl_hip_verify's path (the 14-bit window table and an inversion of its own per key, for k G and again for
+   t G + P' - not the search kernels); ok[i] = 0 for k = 0 (mod n) or t >= n.  A caller verifies a type-4 hit by comparing the first five
+   words with the record's h160.  Any context can be asked, whatever its flags. */
+int ecl_hip_verify_tr(ecl_hip *h, const uint64_t (*k)[4], uint32_t n, uint32_t (*qx)[8], uint8_t *ok);
+
 /* `mul -raw` (main.c:505-527: the scalar of a line is the SHA-256 of its bytes, read as a big-endian number): the same as
    ecl_hip_mul_batch with the hashing done on the device.  `text` holds the lines' bytes (anywhere, in any order, newline
    bytes or not), lines[i] = offset of line i in `text` (low 32 bits) | its length in bytes (high 32 bits); n <= 2^26 lines
@@ -209,7 +229,7 @@ void ecl_hip_free_host(void *p);
 /* ==== 3. TUNING: none of these changes a result ==== */
 /* Optional: allocate now what a later ecl_hip_add_range of `nkeys` keys with record capacity `cap` will need (table,
    lane centres, prefix-product chains, record buffer), so that the first call does not pay for it.  The reference has
-   no counterpart (its per-thread buffers live on the stack, main.c:350-352). */
+   no counterpart (its per-thread buffers live on the stack, main.c:350-352).  On a Taproot context also the slab and the `mul` table. */
 int ecl_hip_reserve(ecl_hip *h, uint64_t nkeys, uint32_t cap);
 
 /* Optional: set up now what a later ecl_hip_mul_batch of up to n scalars with record capacity `cap` needs (the window
@@ -259,7 +279,8 @@ int ecl_hip_get_geometry(ecl_hip *h, uint32_t *half_group, uint32_t *lanes);
 int ecl_hip_plan_geometry(ecl_hip *h, uint64_t nkeys, uint32_t *half_group, uint32_t *lanes, uint32_t *groups_per_lane);
 
 /* ==== 4. MEASUREMENT ==== */
-/* Measurement: accumulated HIP-event time of the main add kernel since the last reset, and launch count. */
+/* Measurement: accumulated HIP-event time of the main add kernel since the last reset, and launch count (Taproot: of both stages of
+   every slab, one launch counted per slab). */
 int ecl_hip_get_timing(ecl_hip *h, double *kernel_ms, uint64_t *launches, uint64_t *keys);
 int ecl_hip_reset_timing(ecl_hip *h);
 /* ... of the set-up a non-contiguous ecl_hip_add_range pays before its search kernel (base centre through the window
@@ -277,7 +298,8 @@ int ecl_hip_get_coverage(ecl_hip *h, uint64_t *requested, uint64_t *covered, uin
 
 /* Known-answer test of the device code (hash160 of 1*G, 2*G, 0xdc2a04*G, both encodings, via the double-and-add
    kernel; the P2SH-P2WPKH hash and the Ethereum address of 1*G) and a cross-check of the walk kernel against it over 4096 consecutive
-   keys (with ECL_P2SH: the script hashes too; with ECL_ETH: the Ethereum addresses, against ecl_hip_verify_eth).  ecl_hip_open() runs it
+   keys (with ECL_P2SH: the script hashes too; with ECL_ETH: the Ethereum addresses, against ecl_hip_verify_eth; with ECL_TR: the output
+   keys, against ecl_hip_verify_tr), and the Taproot output keys of the three private keys (ecl_hip_verify_tr).  ecl_hip_open() runs it
    (a few ms) unless the environment has ECL_HIP_SKIP_SELFTEST=1; a failure makes open return ECL_E_SELFTEST. */
 int ecl_hip_selftest(ecl_hip *h);
 
@@ -300,6 +322,10 @@ int ecl_hip_diag_bloom_mod(ecl_hip *h, uint64_t nwords, const uint64_t *x, uint6
    round short - add: groups per lane nb - 1, mul: scalars per thread R - 1 - so that keys of the call are silently not hashed
    (the call then returns ECL_E_COVERAGE: the check of section 1, under test).  Only a loop bound shrinks. */
 int ecl_hip_diag_drop_round(ecl_hip *h);
+/* Taproot: the search path's two stages for n AFFINE POINTS (x, y on the curve) instead of keys - stage A's even-y lift and tweak, stage B's
+   window sum, addition and normalisation (k_tr_check) - so that a published vector whose private key nobody has runs on the device code
+   of the search: t[i] = the tweak of x[i], qx[i] = the output key (eight big-endian words), ok[i] = 0 where there is none.  n <= 2^20. */
+int ecl_hip_diag_tr(ecl_hip *h, const uint64_t (*x)[4], const uint64_t (*y)[4], uint64_t (*t)[4], uint32_t (*qx)[8], uint8_t *ok, uint32_t n);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -20,7 +20,8 @@ What the numbers are used for:
     (each serves two keys).  The PMC count SQ_INSTS_VALU is the truth for the total; the class SHARES come from here.
 
 usage: tools/isa_mix.py [file.s] [mangled kernel name] [--json]     |     tools/isa_mix.py --all   (every instantiation: profiles/rNN_static_mix.json)
-       tools/isa_mix.py --eth   (the three Ethereum kernels)"""
+       tools/isa_mix.py --eth   (the three Ethereum kernels)
+       tools/isa_mix.py --tr    (the Taproot kernels: registers, loops, the static VALU counts of the tagged hash and the window loop)"""
 import json
 import os
 import re
@@ -246,6 +247,39 @@ def analyse_eth(path=ASM):
     return out
 
 
+# the Taproot kernels (-a t, searched alone): stage A (the emit kernels from the walk and from `mul`'s window sums) and stage B (k_tr_check;
+# <true>: ecl_hip_diag_tr's instantiation, which writes whole output keys instead of probing)
+TR_KERNELS = {"-a t emit": "_Z8k_add_tr8add_args", "mul -a t emit": "_Z15k_mul_points_trPKjjj4wtab8add_argsPjjj",
+              "tr check": "_Z10k_tr_checkILb0EEvPKjjm4wtab8add_argsjPjjjS4_Ph", "tr check (diag)": "_Z10k_tr_checkILb1EEvPKjjm4wtab8add_argsjPjjjS4_Ph"}
+
+
+def analyse_tr(path=ASM):
+    """every Taproot kernel: registers / spills, its loops (depth, VALU, scratch), `scratch_below_top`: scratch instructions in the loops below
+    its launch loop (k_add_tr) / round loops (the others) - tests/test_tr_host.py wants 0 - and `scratch_in_round_loops` for the `mul`-shaped
+    kernels; the static VALU count of the loop that holds the tagged hash (the emit kernels: the `which` loop / the walk-back loop) and of
+    the window loop (one mixed addition)"""
+    out = {}
+    for label, k in TR_KERNELS.items():
+        a = analyse(path, k)
+        sp = spills(path, k).get(k)
+        loops = a["loops"]
+        deep = [l for l in loops if l["depth"] >= 2]
+        top = [l for l in loops if l["depth"] == 1]
+        r = {"kernel": k, "registers": sp, "total": a["total"],
+             "loops": [{x: l[x] for x in ("header", "depth", "parent", "valu", "mad64", "scratch", "scratch_at_calls")} for l in loops],
+             "scratch_below_top": sum(l["scratch"] for l in deep)}
+        if label == "-a t emit":
+            r["tagged_hash_loop_valu"] = a["which_loop"]["valu"]
+        else:
+            r["scratch_in_round_loops"] = sum(l["scratch"] for l in top)
+            win = max(deep, key=lambda l: l["mad64"])
+            r["window_loop_valu"], r["window_loop_mad64"] = win["valu"], win["mad64"]
+            back = max((l for l in top if l["header"] != win["parent"]), key=lambda l: l["valu"])
+            r["walk_back_loop_valu"] = back["valu"]
+        out[label] = r
+    return out
+
+
 def analyse_all(path=ASM):
     """every shipped instantiation of the two search kernels: fingerprint, registers / spills, and the scratch instructions inside the
     per-key loops (k_add: prefix-product, table and `which` loops; k_mul_check: window loop) - tests/test_profiles_fresh.py wants 0 there"""
@@ -270,6 +304,10 @@ def main():
     if "--eth" in sys.argv:
         rest = [a for a in sys.argv[1:] if not a.startswith("--")]
         print(json.dumps(analyse_eth(rest[0] if rest else ASM), indent=1))
+        return
+    if "--tr" in sys.argv:
+        rest = [a for a in sys.argv[1:] if not a.startswith("--")]
+        print(json.dumps(analyse_tr(rest[0] if rest else ASM), indent=1))
         return
     if "--all" in sys.argv:
         rest = [a for a in sys.argv[1:] if not a.startswith("--")]
