@@ -9,7 +9,7 @@ import numpy as np
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ECLOOP_HIP_LIB") or os.path.join(PKG, "libecloop_hip.so")  # override: A/B builds
 
-ADDR33, ADDR65, ENDO, P2SH, ETH, TR = 1, 2, 4, 16, 64, 128
+ADDR33, ADDR65, ENDO, P2SH, ETH, TR, PUB = 1, 2, 4, 16, 64, 128, 256
 E_OVERFLOW = -4
 E_COVERAGE = -8  # the device did not hash every key of the call (include/ecloop_hip.h, section 1)
 
@@ -25,7 +25,7 @@ FOUND_DTYPE = np.dtype([("key_offset", "<u8"), ("h160", "<u4", (5,)), ("endo", "
                         ("pad", "u1", (2,))])
 assert FOUND_DTYPE.itemsize == C.sizeof(Found) == 32
 
-LABELS = {1: "addr33", 0: "addr65", 2: "p2sh", 3: "eth", 4: "p2tr"}  # ecl_found.compressed (the address type) -> label of the found line
+LABELS = {1: "addr33", 0: "addr65", 2: "p2sh", 3: "eth", 4: "p2tr", 5: "pub"}  # ecl_found.compressed (the address type) -> label of the found line
 
 
 def label_of(compressed):
@@ -129,15 +129,18 @@ def ints_of(arr):
 class Device:
     """One GPU context (ecl_hip handle)."""
 
-    def __init__(self, device=0, a33=True, a65=False, endo=False, ord_offs=0, p2sh=False, eth=False, tr=False):
+    def __init__(self, device=0, a33=True, a65=False, endo=False, ord_offs=0, p2sh=False, eth=False, tr=False, pub=False):
+        if pub and (a33 or a65 or p2sh or eth or tr):  # (before the library is asked)
+            raise ValueError("public keys are searched alone: Device(a33=False, pub=True), with or without endo")
         self.lib = load()
         self.h = C.c_void_p()
         self.a33, self.a65, self.endo, self.p2sh, self.eth, self.tr = bool(a33), bool(a65), bool(endo), bool(p2sh), bool(eth), bool(tr)
+        self.pub = bool(pub)
         if eth and (a33 or a65 or p2sh):
             raise ValueError("eth is searched alone: Device(a33=False, eth=True)")
         if tr and (a33 or a65 or p2sh or eth or endo):
             raise ValueError("Taproot is searched alone and without the endomorphism: Device(a33=False, tr=True)")
-        flags = (ADDR33 if a33 else 0) | (ADDR65 if a65 else 0) | (P2SH if p2sh else 0) | (ETH if eth else 0) | (TR if tr else 0) | (ENDO if endo else 0)
+        flags = (ADDR33 if a33 else 0) | (ADDR65 if a65 else 0) | (P2SH if p2sh else 0) | (ETH if eth else 0) | (TR if tr else 0) | (PUB if pub else 0) | (ENDO if endo else 0)
         rc = self.lib.ecl_hip_open(C.byref(self.h), device, flags, ord_offs)
         if rc != 0:
             msg = self.lib.ecl_hip_last_error(self.h).decode() if self.h else ""
@@ -308,6 +311,14 @@ class Device:
         ok = np.zeros(len(K), dtype=np.uint8)
         self._chk(self.lib.ecl_hip_verify_tr(self.h, K.ctypes.data, len(K), qx.ctypes.data, ok.ctypes.data))
         return qx, ok
+
+    def verify_pub(self, ks):
+        """-> (x, parity, ok): the public key of each private key by the double-and-add kernel (diag_mulg: neither the walk nor the window
+        sum) - x as n x 8 big-endian uint32 words (the first five are what a pub record's h160 holds), the parity of y, ok = 0 for k = 0 (mod n)"""
+        xs, ys, ok = self.diag_mulg(ks)
+        x = np.array([[(v >> (32 * (7 - j))) & 0xFFFFFFFF for j in range(8)] for v in xs], dtype=np.uint32).reshape(len(xs), 8)
+        par = np.array([v & 1 for v in ys], dtype=np.uint8)
+        return x, par, ok
 
     def diag_tr(self, xs, ys):
         """the two stages of the Taproot search path for affine points -> (tweaks as ints, output keys n x 8 big-endian words, ok)"""

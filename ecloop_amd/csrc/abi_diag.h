@@ -219,8 +219,8 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   h->B = 16, h->Tmax = 256, h->B_auto = false;
   const uint64_t start[4] = {0x0123456789abcdefull, 0x1f, 0, 0};
   const u32 per_key = ((h->flags & ECL_ADDR33) ? 1 : 0) + ((h->flags & ECL_ADDR65) ? 1 : 0) + ((h->flags & ECL_P2SH) ? 1 : 0) +
-                      ((h->flags & ECL_ETH) ? 1 : 0) + ((h->flags & ECL_TR) ? 1 : 0);
-  const u32 cap = N * per_key * ((h->flags & ECL_ENDO) ? 6 : 1);
+                      ((h->flags & ECL_ETH) ? 1 : 0) + ((h->flags & ECL_TR) ? 1 : 0) + ((h->flags & ECL_PUB) ? 1 : 0);
+  const u32 cap = N * per_key * ((h->flags & ECL_ENDO) ? ((h->flags & ECL_PUB) ? 3 : 6) : 1);  // (a public key and its negative share x: three images)
   std::vector<ecl_found> recs(cap);
   u32 n = 0;
   rc = ecl_hip_set_bloom(h, ones.data(), ones.size());
@@ -243,6 +243,11 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   if (rc == ECL_OK && (h->flags & ECL_ETH)) rc = ecl_hip_verify_eth(h, (const uint64_t(*)[4])ks.data(), N, (uint32_t(*)[5])reth.data(), eok.data());
   // an ECL_TR context: the walk's and k_tr_check's output keys against the window-table path's (ecl_hip_verify_tr)
   if (rc == ECL_OK && (h->flags & ECL_TR)) rc = ecl_hip_verify_tr(h, (const uint64_t(*)[4])ks.data(), N, (uint32_t(*)[8])rtr.data(), eok.data());
+  // an ECL_PUB context: the walk's x against the double-and-add kernel's, its leading 20 bytes as five big-endian words
+  std::vector<uint32_t> rpub((h->flags & ECL_PUB) ? (size_t)N * 5 : 0);
+  if (h->flags & ECL_PUB)
+    for (u32 i = 0; i < N; ++i)
+      for (u32 j = 0; j < 5; ++j) rpub[(size_t)i * 5 + j] = (uint32_t)(xs[(size_t)i * 4 + (7 - j) / 2] >> (32 * ((7 - j) & 1)));
   // restore the caller's state whatever happened
   if (h->d_bloom) (void)hipFree(h->d_bloom);
   h->d_bloom = save_bloom, h->bloom_words = save_words;
@@ -259,7 +264,7 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
     const ecl_found& f = recs[i];
     if (f.key_offset >= N) { good = false; break; }
     if (f.endo != 0) continue;  // the endomorphism images are covered by the parity tests; here: the walk itself
-    const uint32_t* want = f.compressed == 4 ? &rtr[f.key_offset * 8] : f.compressed == 3 ? &reth[f.key_offset * 5] : f.compressed == 2 ? &rsh[f.key_offset * 5] : f.compressed ? &r33[f.key_offset * 5] : &r65[f.key_offset * 5];
+    const uint32_t* want = f.compressed == 5 ? &rpub[f.key_offset * 5] : f.compressed == 4 ? &rtr[f.key_offset * 8] : f.compressed == 3 ? &reth[f.key_offset * 5] : f.compressed == 2 ? &rsh[f.key_offset * 5] : f.compressed ? &r33[f.key_offset * 5] : &r65[f.key_offset * 5];
     good = memcmp(f.h160, want, 20) == 0;
     ++seen;
   }

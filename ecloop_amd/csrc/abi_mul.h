@@ -235,6 +235,10 @@ static void mul_launch_piece(ecl_hip* h, int lane, const u32* d_k, u32 m, u32 at
     tr_mul_launch_piece(h, lane, d_k, m, at, gtab, a, short_round);
     return;
   }
+  if (h->flags & ECL_PUB) {  // alone (ecl_hip_open)
+    hipLaunchKernelGGL(k_mul_check_pub, grid, blk, 0, st, d_k, m, at, gtab, a, tmp, nt, R);
+    return;
+  }
   if (h->flags & ECL_ETH) {  // alone (ecl_hip_open)
     hipLaunchKernelGGL(k_mul_check_eth, grid, blk, 0, st, d_k, m, at, gtab, a, tmp, nt, R);
     return;

@@ -23,11 +23,12 @@
 #include "bloom.h"
 #include "hash160.h"
 #include "keccak.h"
+#include "pub_emit.h"
 
 struct ecl_found_dev {
   u64 key_offset;
   u32 h160[5];
-  u32 tag;  // byte 0 = endo, byte 1 = address type (ecl_found.compressed: 1 addr33, 0 addr65, 2 p2sh, 3 eth, 4 p2tr)
+  u32 tag;  // byte 0 = endo, byte 1 = address type (ecl_found.compressed: 1 addr33, 0 addr65, 2 p2sh, 3 eth, 4 p2tr, 5 pub)
 };
 
 struct add_args {
@@ -329,32 +330,59 @@ __device__ __forceinline__ void tr_emit(const add_args& a, bool have, bool isinf
     e[4] = make_uint4(yw[0] | a.epoch, yw[1], yw[2], yw[3]), e[5] = make_uint4(yw[4], yw[5], yw[6], yw[7]);
   }
 }
-// the candidate rings for a kernel that reports ONE address type (k_tr_check: type 4, which the two bits the rings keep for the type
-// of the other kernels do not hold): the type is a constant of the kernel, the ring's tag is not read
-template <u32 TYPE>
+// the candidate rings for a kernel that reports ONE address type (k_tr_check: type 4, the public-key kernels: type 5, which the two bits
+// the rings keep for the type of the other kernels do not hold): the type is a constant of the kernel.  TAG = false (k_tr_check): the
+// ring's tag is not read; TAG = true: it carries the record's endo field (the image number of a public key searched with the endomorphism)
+template <u32 TYPE, bool TAG = false>
 __device__ __forceinline__ void cand1_finish(const add_args& a, cand_queue& qb) {
   bool valid;
   const cand_rec r = cand_take(qb, valid);
   const int from = bloom_mid_two(a.bloom) ? 3 : 2;
-  if (valid && bloom_probes_from(a.bloom, r.h, from)) found_push(a, r.off, r.h, 0, TYPE);
+  if (valid && bloom_probes_from(a.bloom, r.h, from)) found_push(a, r.off, r.h, TAG ? r.tag & 0xffu : 0u, TYPE);
 }
-template <u32 TYPE>
+template <u32 TYPE, bool TAG = false>
 __device__ __forceinline__ void cand1_mid(const add_args& a, cand_queues& q) {
   bool valid;
   const cand_rec r = cand_take(q.a, valid);
   const bool pass = valid && bloom_mid(a.bloom, r.h, bloom_mid_two(a.bloom));
-  if (cand_append(q.b, pass, r.off, r.h, 0)) cand1_finish<TYPE>(a, q.b);
+  if (cand_append(q.b, pass, r.off, r.h, TAG ? r.tag : 0u)) cand1_finish<TYPE, TAG>(a, q.b);
 }
-template <u32 TYPE>
-__device__ __forceinline__ void cand1_check(const add_args& a, cand_queues& q, bool live, u64 off, const u32 h[5]) {
+template <u32 TYPE, bool TAG = false>
+__device__ __forceinline__ void cand1_check(const add_args& a, cand_queues& q, bool live, u64 off, const u32 h[5], u32 tag = 0) {
   const bool pass = live && bloom_stage1(a.bloom, h);
-  if (cand_append(q.a, pass, off, h, 0)) cand1_mid<TYPE>(a, q);
+  if (cand_append(q.a, pass, off, h, TAG ? tag : 0u)) cand1_mid<TYPE, TAG>(a, q);
 }
-template <u32 TYPE>
+template <u32 TYPE, bool TAG = false>
 __device__ __forceinline__ void cand1_flush(const add_args& a, cand_queues& q) {
-  cand1_mid<TYPE>(a, q);
-  cand1_finish<TYPE>(a, q.b);
-  cand1_finish<TYPE>(a, q.b);
+  cand1_mid<TYPE, TAG>(a, q);
+  cand1_finish<TYPE, TAG>(a, q.b);
+  cand1_finish<TYPE, TAG>(a, q.b);
+}
+// ---- public keys by x (-a x, pub_emit.h): what the public-key kernels (k_add_pub<ENDO>, k_mul_check_pub) do with a point's x instead of
+// hashing it: the leading 20 bytes of the canonical x through the rings, record type 5.  ENDO: beta x and beta^2 x too, as the +y images
+// 0, 2, 4 of check_point's numbering (a key and its negative share x, so three probes stand for six keys and the host's calc_priv
+// needs no new case).  x: magnitude <= 4.
+template <bool ENDO>
+__device__ __forceinline__ void pub_check(const add_args& a, cand_queues& q, bool live, const fe& x, u64 off) {
+  u32 h[ENDO ? 3 : 1][5];
+  if (ENDO) {
+    fe bx, b2x;
+    pub_endo_x(bx, b2x, x);
+    pub_words20(h[1], bx);
+    pub_words20(h[2], b2x);
+  }
+  pub_words20(h[0], x);
+  if (ENDO) {
+#pragma unroll 1
+    for (u32 e = 0; e < 3; ++e) {
+      u32 hs[5];
+#pragma unroll
+      for (int i = 0; i < 5; ++i) hs[i] = e == 0 ? h[0][i] : (e == 1 ? h[1][i] : h[ENDO ? 2 : 0][i]);
+      cand1_check<5u, true>(a, q, live, off, hs, 2u * e);
+    }
+  } else {
+    cand1_check<5u, true>(a, q, live, off, h[0]);
+  }
 }
 
 // waves per SIMD the register allocator must leave room for (256-thread blocks: blocks per CU = this value).  Final kernel:
@@ -411,5 +439,20 @@ __device__ __forceinline__ void cand1_flush(const add_args& a, cand_queues& q) {
 #include "add_walk.inc"
 #undef ECL_WALK_KERNEL
 #undef ECL_WALK_TR
+#undef ECL_WALK_P2SH
+#undef ECL_WALK_WAVES
+// Public-key instantiations: k_add_pub<ENDO>, the walk with x-only emission (pub_emit.h: no y of a walked point, no hash), searched alone
+// (ecl_hip_open), so two kernels.  Four waves per SIMD (128 VGPRs, spills in the launch loop only) is the most this kernel can have: five
+// cannot be met (the compiler falls back to four: a field multiplication's operands, result and accumulators beside the walk's state do
+// not fit 96 VGPRs), and six or eight are out of reach of any register setting - the rings' 32 KiB of LDS per block cap a CU at five
+// blocks; asked for, the compiler builds a 159-VGPR kernel that runs at three (HISTORY section 11)
+#define ECL_PUB_WAVES 4
+#define ECL_WALK_KERNEL k_add_pub
+#define ECL_WALK_PUB
+#define ECL_WALK_P2SH false
+#define ECL_WALK_WAVES ECL_PUB_WAVES
+#include "add_walk.inc"
+#undef ECL_WALK_KERNEL
+#undef ECL_WALK_PUB
 #undef ECL_WALK_P2SH
 #undef ECL_WALK_WAVES

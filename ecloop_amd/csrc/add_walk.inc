@@ -3,14 +3,15 @@
 // ECL_WALK_WAVES (waves per SIMD of an instantiation, an expression of A33 / A65 / ENDO) defined; no include guard on purpose.
 // With ECL_WALK_ETH defined as well the kernel is k_add_eth<ENDO>: the Ethereum address alone (ECL_WALK_WAVES an expression of ENDO).
 // With ECL_WALK_TR defined the kernel is k_add_tr (no template): the Taproot emit kernel, tr_emit in place of check_point, no rings.
+// With ECL_WALK_PUB defined the kernel is k_add_pub<ENDO>: public keys by x - no y of a walked point, pub_check in place of check_point.
 #if defined(ECL_WALK_TR)
-#elif defined(ECL_WALK_ETH)
+#elif defined(ECL_WALK_ETH) || defined(ECL_WALK_PUB)
 template <bool ENDO>
 #else
 template <bool A33, bool A65, bool ENDO>
 #endif
 __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL(const add_args a) {
-#ifdef ECL_WALK_ETH
+#if defined(ECL_WALK_ETH)
   constexpr bool A33 = false, A65 = false, ETH = true;
 #else
   constexpr bool ETH = false;
@@ -80,6 +81,9 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
           // +-Gy - Y, magnitude 3.  The table side (Gy + 2p or 3p - Gy) is wave-uniform like `which`: selected on
           // the scalar unit, so the vector side is one subtraction per limb (written as a select of two vector
           // results the compiler emits both and nine v_cndmask)
+#ifdef ECL_WALK_PUB
+          px = pub_x(pub_num(gy, Y, which), invk, nxg);  // magnitude 4; no y (pub_emit.h: the same numerator, the code the host test runs)
+#else
           const fe c = which == 0 ? fe_add(gy, fe_neg(fe_zero(), 1)) : fe_neg(gy, 2);
           fe s;
 #pragma unroll
@@ -87,9 +91,16 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
           fe lam = fe_mul(s, invk);
           px = fe_add(fe_sqr(lam), nxg);                                   // magnitude 4
           py = fe_sub(fe_mul(lam, fe_add(X, fe_neg(px, 4))), Y);           // X - px: magnitude 6; py: magnitude 3
+#endif
           off = base + (which == 0 ? B + 1 + i : B - 1 - i);  // scalar select, one 64-bit add
           valid = which == 1 || i + 1 < B;
         } else {
+#ifdef ECL_WALK_PUB
+          px = X, off = base + B;
+#pragma unroll
+          for (int l = 0; l < FE_LIMBS; ++l) FE_HIDE24(px.n[l]);
+        }
+#else
           px = X, py = Y, off = base + B;
           // the centre itself, once per B iterations: keep the copies of X and Y inside this branch (left alone, the
           // compiler copies them into px / py at the head of EVERY iteration and overwrites them: 18 moves per key)
@@ -99,11 +110,14 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
             FE_HIDE24(py.n[l]);
           }
         }
+#endif
         if (valid) {
           const bool live = off < a.nkeys;
           keys_count(q, live);
-#ifdef ECL_WALK_TR
+#if defined(ECL_WALK_TR)
           tr_emit(a, live, false, px, py, off);
+#elif defined(ECL_WALK_PUB)
+          pub_check<ENDO>(a, q, live, px, off);
 #else
           check_point<A33, A65, ECL_WALK_P2SH, ENDO, ETH>(a, &q, live, px, py, off);
 #endif
@@ -124,7 +138,9 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
     fe_normalize_weak(Yn);
     X = Xn, Y = Yn;
   }
-#ifndef ECL_WALK_TR
+#if defined(ECL_WALK_PUB)
+  cand1_flush<5u, true>(a, q);
+#elif !defined(ECL_WALK_TR)
   cand_flush<P2SH>(a, q);
 #endif
   keys_flush(a, q);

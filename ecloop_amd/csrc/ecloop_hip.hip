@@ -142,9 +142,10 @@ const char* ecl_hip_last_error(const ecl_hip* h) { return h ? h->err.c_str() : "
 
 int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   const u32 types = ECL_ADDR33 | ECL_ADDR65 | ECL_P2SH;
-  if (!out || ord_offs > 255 || !(flags & (types | ECL_ETH | ECL_TR)) || (flags & ~(types | ECL_ETH | ECL_TR | ECL_ENDO))) return ECL_E_ARG;
+  if (!out || ord_offs > 255 || !(flags & (types | ECL_ETH | ECL_TR | ECL_PUB)) || (flags & ~(types | ECL_ETH | ECL_TR | ECL_PUB | ECL_ENDO))) return ECL_E_ARG;
   if ((flags & ECL_ETH) && (flags & types)) return ECL_E_ARG;  // eth is searched alone
   if ((flags & ECL_TR) && flags != ECL_TR) return ECL_E_ARG;   // Taproot is searched alone and without the endomorphism
+  if ((flags & ECL_PUB) && (flags & ~(ECL_PUB | ECL_ENDO))) return ECL_E_ARG;  // public keys are searched alone
   int n = ecl_hip_device_count();
   if (device < 0 || device >= n) return ECL_E_NODEV;
   ecl_hip* h = new ecl_hip();
@@ -167,7 +168,7 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   static std::mutex mu;
   static std::set<u32> passed;
   const char* skip = getenv("ECL_HIP_SKIP_SELFTEST");
-  const u32 key = (u32)device * 256u + flags;  // flags < 256
+  const u32 key = (u32)device * 512u + flags;  // flags < 512
   {
     std::lock_guard<std::mutex> lk(mu);
     if ((skip && skip[0] == '1') || passed.count(key)) return ECL_OK;
@@ -409,6 +410,7 @@ typedef void (*add_kernel_t)(const add_args);
 // every non-empty set of address types (ecl_hip_open refuses the empty one) x endo
 static add_kernel_t pick_add_kernel(u32 flags) {
   const bool endo = flags & ECL_ENDO;
+  if (flags & ECL_PUB) return endo ? k_add_pub<true> : k_add_pub<false>;  // alone (ecl_hip_open)
   if (flags & ECL_TR) return k_add_tr;  // alone, no endomorphism (ecl_hip_open): the emit kernel
   if (flags & ECL_ETH) return endo ? k_add_eth<true> : k_add_eth<false>;  // alone (ecl_hip_open)
   switch (flags & (ECL_ADDR33 | ECL_ADDR65 | ECL_P2SH)) {
@@ -586,7 +588,8 @@ extern "C" int ecl_hip_get_geometry(ecl_hip* h, uint32_t* half_group, uint32_t* 
 
 // Geometry of one call.  The table for half group h->B holds the tables of all smaller ones as prefixes, so a call may walk any
 // power-of-two half group up to h->B.  Two costs pull in opposite directions: a lane pays one inversion per group (the division
-// steps cost about five keys' worth of work: + 5 / 2B per key), and a walk with few lanes leaves the chip empty or in lock-step -
+// steps cost about five keys' worth of work: + 5 / 2B per key; inv_keys_worth: a public key costs a fraction of a hashed one, so the same
+// inversion is worth several times as many of them), and a walk with few lanes leaves the chip empty or in lock-step -
 // the kernel only reaches its rate when the slots are oversubscribed with blocks in different phases.  Both were measured
 // (profiles/r05_short_calls.txt: calls of 2^21 ... 2^26 keys at half groups 8 ... 128; profiles/r04_short_calls.txt: 2^29 ... 2^32):
 // the time per key relative to the long-call rate is, to a few per cent, lane_factor(lanes) x (1 + 5 / 2B) with
@@ -605,6 +608,16 @@ static double lane_factor(double lanes) {
   const int i = (int)l - 13;
   return f[i] + (f[i + 1] - f[i]) * (l - (13 + i));
 }
+// the group's inversion (fe_inv: about 16 400 VALU instructions, the same for every kernel) in keys' worth of the kernel's own per-key work.
+// Every hashing type keeps the measured 5 (a 3 117-op key: 16 400 / 3 117 = 5.3).  A public key is the static per-key count of its kernel
+// (tools/isa_mix.py --pub: the `which` loop + half the table loop's own body + half the prefix loop): 813 VALU instructions without the
+// endomorphism, 692 + 3 x 196 (the image loop) + 253 = 1 533 per walked key with it - 16 400 / 813 = 20 and 16 400 / 1 533 = 11.
+// These two are STATIC estimates (instruction counts of the assembly), standing in for the measured per-key count until a counter run
+// (tools/bench_pub.py add 28 under SQ_INSTS_VALU) gives it.  Results never depend on it: it only picks the half group.
+static double inv_keys_worth(u32 flags) {
+  if (flags & ECL_PUB) return (flags & ECL_ENDO) ? 11.0 : 20.0;
+  return 5.0;
+}
 static u32 auto_half_group(const ecl_hip* h, u64 nkeys) {
   u32 best = h->B;
   if (!h->B_auto) return best;
@@ -612,7 +625,7 @@ static u32 auto_half_group(const ecl_hip* h, u64 nkeys) {
   for (u32 B = h->B; B >= ECL_B_FLOOR; B >>= 1) {
     const u64 groups = (nkeys + 2ull * B - 1) / (2ull * B);
     const double lanes = groups < h->Tmax ? (double)groups : (double)h->Tmax;
-    const double cost = lane_factor(lanes) * (1.0 + 5.0 / (2.0 * B));
+    const double cost = lane_factor(lanes) * (1.0 + inv_keys_worth(h->flags) / (2.0 * B));
     if (B == h->B || cost < best_cost * 0.995) best = B, best_cost = cost;  // a smaller half group has to win by more than noise
     if (groups >= h->Tmax) break;  // every lane already has a group of its own: halving further only adds inversions
   }

@@ -2,7 +2,9 @@
 // and as k_mul_check_p2sh (the same sets plus P2SH, and P2SH alone), like add_walk.inc.  Included with ECL_MUL_KERNEL and ECL_MUL_P2SH
 // defined; no include guard on purpose.  With ECL_MUL_ETH defined as well the kernel is k_mul_check_eth: the Ethereum address alone.
 // With ECL_MUL_TR defined the kernel is k_mul_points_tr: the Taproot emit kernel, tr_emit in place of check_point, no rings.
-#if !defined(ECL_MUL_ETH) && !defined(ECL_MUL_TR)
+// With ECL_MUL_PUB defined the kernel is k_mul_check_pub: public keys by x - Y ZZ is neither formed nor parked (its planes of `tmp` stay
+// unused), x = X ZZZ / T alone goes to pub_check.
+#if !defined(ECL_MUL_ETH) && !defined(ECL_MUL_TR) && !defined(ECL_MUL_PUB)
 template <bool A33, bool A65>
 #endif
 __global__ void __launch_bounds__(256, ECL_MUL_WAVES) ECL_MUL_KERNEL(const u32* __restrict__ k, u32 n, u32 base, const wtab gtab, add_args a,
@@ -41,11 +43,19 @@ __global__ void __launch_bounds__(256, ECL_MUL_WAVES) ECL_MUL_KERNEL(const u32* 
     fe tt, xs, ys, nprod;
     fe_mul_pair(tt, xs, acc.ZZ, acc.ZZZ, acc.X, acc.ZZZ);
     if (acc.inf) tt = fe_one();
+#ifdef ECL_MUL_PUB
+    nprod = fe_mul(prod, tt);
+#else
     fe_mul_pair(ys, nprod, acc.Y, acc.ZZ, prod, tt);
+#endif
     u32* p = tmp + (size_t)r * 36 * nt + t;
 #pragma unroll
     for (int l = 0; l < FE_LIMBS; ++l) {
+#ifdef ECL_MUL_PUB
+      p[(size_t)l * nt] = xs.n[l];
+#else
       p[(size_t)l * nt] = xs.n[l], p[(size_t)(9 + l) * nt] = ys.n[l];
+#endif
       p[(size_t)(18 + l) * nt] = tt.n[l], p[(size_t)(27 + l) * nt] = prod.n[l];
     }
     prod = nprod;
@@ -69,15 +79,27 @@ __global__ void __launch_bounds__(256, ECL_MUL_WAVES) ECL_MUL_KERNEL(const u32* 
     fe X, Y, T, pre;
 #pragma unroll
     for (int l = 0; l < FE_LIMBS; ++l) {
+#ifdef ECL_MUL_PUB
+      X.n[l] = have ? p[(size_t)l * nt] : 0u;
+#else
       X.n[l] = have ? p[(size_t)l * nt] : 0u, Y.n[l] = have ? p[(size_t)(9 + l) * nt] : 0u;
+#endif
       T.n[l] = have ? p[(size_t)(18 + l) * nt] : (l == 0 ? 1u : 0u), pre.n[l] = have ? p[(size_t)(27 + l) * nt] : 0u;
     }
     fe ti, ninv, x, y;
     fe_mul_pair(ti, ninv, inv, pre, inv, T);  // T = 1 for a lane without a scalar in this round
     inv = ninv;
+#ifdef ECL_MUL_PUB
+    x = fe_mul(X, ti);
+#else
     fe_mul_pair(x, y, X, ti, Y, ti);
+#endif
     keys_count(q, have);  // a scalar whose point is at infinity counts: it has nothing to hash
-#ifdef ECL_MUL_TR
+#if defined(ECL_MUL_PUB)
+    pub_check<false>(a, q, have && !((infmask >> r) & 1u), x, (u64)base + i);
+  }
+  cand1_flush<5u, true>(a, q);
+#elif defined(ECL_MUL_TR)
     tr_emit(a, have, (infmask >> r) & 1u, x, y, (u64)base + i);  // (base = 0: the piece is its own slab)
   }
 #else

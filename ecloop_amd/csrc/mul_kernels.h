@@ -214,6 +214,13 @@ __device__ __forceinline__ xyzz wtab_sum_fast(const u32* __restrict__ kw, const 
 #undef ECL_MUL_KERNEL
 #undef ECL_MUL_TR
 #undef ECL_MUL_P2SH
+#define ECL_MUL_KERNEL k_mul_check_pub
+#define ECL_MUL_PUB
+#define ECL_MUL_P2SH false
+#include "mul_check.inc"
+#undef ECL_MUL_KERNEL
+#undef ECL_MUL_PUB
+#undef ECL_MUL_P2SH
 // ---- k_mul_check's window sum (round 4): written for a small register budget (three waves per SIMD) --------
 // * the scalar stays in memory: a digit is one 8-byte load at the digit's word (L2 / L1 hits after the first window: a wave's scalars
 //   are 2 KiB of contiguous memory) + a shift, not a 16-way select over eight registers, and is fetched one window ahead;

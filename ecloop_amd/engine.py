@@ -216,26 +216,29 @@ def max_over_ranks(seconds, dist=None):
 
 
 class FoundRecord:
-    __slots__ = ("label", "h160", "pk")
+    __slots__ = ("label", "h160", "pk", "prefix")
 
     def __init__(self, label, h160, pk):
         self.label, self.h160, self.pk = label, h160, pk
+        self.prefix = ""  # a verified pub record: "02" / "03", the first byte of the compressed key its line prints
 
     def line(self):
         """outfile format of ctx_write_found (main.c:193-195)"""
-        return "%s\t%s\t%064x" % (self.label, "".join("%08x" % int(w) for w in self.h160), self.pk)
+        return "%s\t%s\t%064x" % (self.label, self.prefix + "".join("%08x" % int(w) for w in self.h160), self.pk)
 
     def stdout_line(self):
         """stdout format (main.c:187-189)"""
-        return "%s: %s <- %064x" % (self.label, "".join("%08x" % int(w) for w in self.h160), self.pk)
+        return "%s: %s <- %064x" % (self.label, self.prefix + "".join("%08x" % int(w) for w in self.h160), self.pk)
 
 
 class KeySearch:
     """ctx_t + cmd_add / cmd_mul for one GPU."""
 
     def __init__(self, flt, device=0, a33=True, a65=False, endo=False, ord_offs=0, verify=True, launch_keys=1 << 32,
-                 half_group=0, max_lanes=0, device_cls=None, p2sh=False, eth=False, tr=False):
-        if tr:
+                 half_group=0, max_lanes=0, device_cls=None, p2sh=False, eth=False, tr=False, pub=False):
+        if pub:
+            a33 = False  # public keys are searched alone (with or without the endomorphism)
+        elif tr:
             a33 = False  # Taproot is searched alone and without the endomorphism (the context refuses anything beside it)
         elif eth:
             a33 = False  # eth is searched alone (any other type beside it: the context refuses)
@@ -245,6 +248,7 @@ class KeySearch:
         self.p2sh = p2sh  # P2SH-P2WPKH (no reference counterpart): records labelled "p2sh"
         self.eth = eth  # Ethereum addresses (no reference counterpart either): records labelled "eth"
         self.tr = tr  # Taproot output keys (BIP341 / BIP86 key path): records labelled "p2tr", h160 = the leading 20 bytes of the key
+        self.pub = pub  # public keys by x: records labelled "pub", h160 = the leading 20 bytes of x
         self.stride = 1 << ord_offs
         # device_cls: the GPU context (capi.Device); the CPU tests of the host logic pass a stand-in with the same surface
         kw = {"p2sh": True} if p2sh else {}  # (a stand-in without the P2SH type keeps working for the other types)
@@ -252,6 +256,8 @@ class KeySearch:
             kw["eth"] = True
         if tr:
             kw["tr"] = True
+        if pub:
+            kw["pub"] = True
         self.dev = (device_cls or Device)(device, a33=a33, a65=a65, endo=endo, ord_offs=ord_offs, **kw)
         if half_group or max_lanes:
             self.dev.set_geometry(half_group, max_lanes)
@@ -279,6 +285,16 @@ class KeySearch:
                     raise EclError("[!] error: hash mismatch (%s) pk: %064x" % (r.label, r.pk))
                 r.h160 = [int(v) for v in qx[i]]
             recs = [r for r in recs if r.label != "p2tr"]
+            if not recs:
+                return
+        pub = [r for r in recs if r.label == "pub"]
+        if pub:  # the first 20 bytes of the x of the key's point (double-and-add kernel) against the record, which then carries the whole key
+            x, par, ok = self.dev.verify_pub([r.pk for r in pub])
+            for i, r in enumerate(pub):
+                if not ok[i] or [int(v) for v in x[i][:5]] != [int(v) for v in r.h160[:5]]:
+                    raise EclError("[!] error: hash mismatch (%s) pk: %064x" % (r.label, r.pk))
+                r.h160, r.prefix = [int(v) for v in x[i]], "%02x" % (2 | int(par[i]))
+            recs = [r for r in recs if r.label != "pub"]
             if not recs:
                 return
         eth = [r for r in recs if r.label == "eth"]
@@ -357,8 +373,8 @@ class KeySearch:
                 if self.flt.confirm(r["h160"]):
                     new.append(FoundRecord(label_of(r["compressed"]), [int(v) for v in r["h160"]], ks[int(r["key_offset"])]))
                     self.k_found += 1
-            if self.tr and self.verify:
-                self._verify(new)  # (a p2tr record gets its whole output key from the verification)
+            if (self.tr or self.pub) and self.verify:
+                self._verify(new)  # (a p2tr / pub record gets its whole key from the verification)
             self.found.extend(new)
             self.k_checked += len(ks)
         return self.found

@@ -89,7 +89,7 @@ static void *scan_worker(void *arg) {
       pks[kept] = calc_priv(s, run->stride_k, buf[i].key_offset, buf[i].endo);
       buf[kept++] = buf[i];
     }
-    u32 (*qx)[8] = run->tr && kept ? malloc((size_t)kept * 32) : NULL; /* Taproot: the whole output keys, from the verification */
+    u32 (*qx)[FULL_WORDS] = (run->tr || run->pub) && kept ? malloc((size_t)kept * sizeof *qx) : NULL; /* Taproot / pub: the whole keys, from the verification */
     verify_hits(run, w->g, pks, buf, kept, qx);
     for (u32 i = 0; i < kept; ++i) report_hit(&run->rep, buf[i].compressed, qx ? qx[i] : buf[i].h160, &pks[i]);
     free(pks), free(qx);

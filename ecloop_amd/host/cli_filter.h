@@ -97,12 +97,79 @@ static bool hash160_from_hex(const char *s, u32 h[5]) {
    rule above already makes of such a line, so .blf files and the default reader are as they were.  With `-a t` on the command line
    (list_strict_64; never otherwise) ONLY lines of exactly 64 clean hex digits are entries: a hash160 list given by mistake then ends in
    "no hashes in filter file" instead of a search that can find nothing. */
-static bool list_skip_0x, list_strict_64;
+/* Public-key lists (no reference counterpart): with `-a x` on the command line (list_pub; never otherwise) a line is an entry if and only
+   if it is a public key in one of three forms - 66 hex digits starting 02 or 03 (compressed), 130 hex digits starting 04 whose point
+   satisfies y^2 = x^3 + 7 (uncompressed; checked here, x and y below p), or 64 hex digits (a bare x) - and the entry is the leading 20
+   bytes of x.  Anything else is no entry: a hash160 list given by mistake ends in "no hashes in filter file". */
+static bool list_skip_0x, list_strict_64, list_pub;
+/* 64 hex digits -> 8 big-endian words, through hash160_from_hex (either decoder): digits 0..39 and 24..63 */
+static bool words8_from_hex(const char *s, u32 w[8]) {
+  u32 a[5], b[5];
+  if (!hash160_from_hex(s, a) || !hash160_from_hex(s + 24, b)) return false;
+  memcpy(w, a, 20), memcpy(w + 5, b + 2, 12);
+  return true;
+}
+/* arithmetic mod p = 2^256 - 0x1000003D1 on four 64-bit limbs (per list line with an uncompressed key only) */
+#define FP_C 0x1000003D1ull
+static void fp_canon(u64 r[4]) { /* r < 2^256 -> r mod p: r >= p iff r + C carries out */
+  unsigned __int128 c = FP_C;
+  u64 t[4];
+  for (int i = 0; i < 4; ++i) c += r[i], t[i] = (u64)c, c >>= 64;
+  if (c) memcpy(r, t, 32);
+}
+static void fp_mul(u64 r[4], const u64 a[4], const u64 b[4]) {
+  u64 t[8] = {0};
+  for (int i = 0; i < 4; ++i) {
+    u64 carry = 0;
+    for (int j = 0; j < 4; ++j) {
+      unsigned __int128 m = (unsigned __int128)a[i] * b[j] + t[i + j] + carry;
+      t[i + j] = (u64)m, carry = (u64)(m >> 64);
+    }
+    t[i + 4] = carry;
+  }
+  unsigned __int128 c = 0;
+  u64 lo[4];
+  for (int i = 0; i < 4; ++i) c += (unsigned __int128)t[4 + i] * FP_C + t[i], lo[i] = (u64)c, c >>= 64;
+  c *= FP_C; /* what is left above 2^256: below 2^34 */
+  for (int i = 0; i < 4; ++i) c += lo[i], lo[i] = (u64)c, c >>= 64;
+  if (c) { /* once more: the sum wrapped, so it is small */
+    c = FP_C;
+    for (int i = 0; i < 4; ++i) c += lo[i], lo[i] = (u64)c, c >>= 64;
+  }
+  fp_canon(lo);
+  memcpy(r, lo, 32);
+}
+static bool on_curve(const u32 xw[8], const u32 yw[8]) { /* big-endian words */
+  u64 x[4], y[4], x3[4], y2[4], t[4];
+  for (int i = 0; i < 4; ++i) x[i] = (u64)xw[6 - 2 * i] << 32 | xw[7 - 2 * i], y[i] = (u64)yw[6 - 2 * i] << 32 | yw[7 - 2 * i];
+  memcpy(t, x, 32), fp_canon(t);
+  if (memcmp(t, x, 32)) return false; /* x >= p */
+  memcpy(t, y, 32), fp_canon(t);
+  if (memcmp(t, y, 32)) return false;
+  fp_mul(y2, y, y), fp_mul(x3, x, x), fp_mul(x3, x3, x);
+  unsigned __int128 c = 7;
+  for (int i = 0; i < 4; ++i) c += x3[i], x3[i] = (u64)c, c >>= 64; /* x3 < p < 2^256 - 7: no carry out */
+  fp_canon(x3);
+  return !memcmp(x3, y2, 32);
+}
+/* the entry of one line of a public-key list, or false */
+static bool pub_entry(const char *s, size_t n, u32 h[5]) {
+  u32 x[8], y[8];
+  if (n == 64) return words8_from_hex(s, x) && (memcpy(h, x, 20), true);
+  if (n == 66) return s[0] == '0' && (s[1] == '2' || s[1] == '3') && words8_from_hex(s + 2, x) && (memcpy(h, x, 20), true);
+  if (n == 130) return s[0] == '0' && s[1] == '4' && words8_from_hex(s + 2, x) && words8_from_hex(s + 66, y) && on_curve(x, y) && (memcpy(h, x, 20), true);
+  return false;
+}
 static size_t hashlist_entries(const char *text, size_t len, u32 *out) {
   size_t n = 0;
   for (size_t at = 0; at < len;) {
     const char *nl = memchr(text + at, '\n', len - at);
     size_t eol = nl ? (size_t)(nl - text) : len;
+    if (list_pub) {
+      if (pub_entry(text + at, eol - at, out + n * 5)) n++;
+      at = eol + 1;
+      continue;
+    }
     if (list_strict_64) {
       u32 tail[5];
       char pad[40];

@@ -120,9 +120,9 @@ static void mul_flush(run_t *run, int g, u64 (*ks)[4], u32 n) {
     if (!filter_confirms(&run->flt, buf[i].h160)) continue;
     sc pk;
     memcpy(pk.w, ks[buf[i].key_offset], 32);
-    u32 qx[1][8];
-    if (run->eth || run->tr) verify_hits(run, g, &pk, &buf[i], 1, qx); /* (an eth / p2tr hit has no reference behaviour to keep: verified like add's) */
-    report_hit(&run->rep, buf[i].compressed, run->tr ? qx[0] : buf[i].h160, &pk); /* no verify: main.c:469,474 */
+    u32 qx[1][FULL_WORDS];
+    if (run->eth || run->tr || run->pub) verify_hits(run, g, &pk, &buf[i], 1, qx); /* (an eth / p2tr / pub hit has no reference behaviour to keep: verified like add's) */
+    report_hit(&run->rep, buf[i].compressed, run->tr || run->pub ? qx[0] : buf[i].h160, &pk); /* no verify: main.c:469,474 */
   }
   free(buf);
   report_progress(&run->rep, n);
@@ -140,9 +140,9 @@ static void mul_flush_raw(run_t *run, int g, const u8 *text, size_t text_len, co
     u32 st[8];
     sha256_stream(st, text + (u32)ln, (size_t)(ln >> 32));
     sc pk = {{(u64)st[6] << 32 | st[7], (u64)st[4] << 32 | st[5], (u64)st[2] << 32 | st[3], (u64)st[0] << 32 | st[1]}};
-    u32 qx[1][8];
-    if (run->eth || run->tr) verify_hits(run, g, &pk, &buf[i], 1, qx);
-    report_hit(&run->rep, buf[i].compressed, run->tr ? qx[0] : buf[i].h160, &pk);
+    u32 qx[1][FULL_WORDS];
+    if (run->eth || run->tr || run->pub) verify_hits(run, g, &pk, &buf[i], 1, qx);
+    report_hit(&run->rep, buf[i].compressed, run->tr || run->pub ? qx[0] : buf[i].h160, &pk);
   }
   free(buf);
   report_progress(&run->rep, n);

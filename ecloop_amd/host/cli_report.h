@@ -42,14 +42,12 @@ static void status_show_locked(report_t *r) {
   fflush(stderr);
 }
 /* one found key: "addr33: <hash160> <- <key>" on stdout, "addr33\t<hash160>\t<key>" in the file; counts it.  type: the address type of
-   ecl_found.compressed (1 addr33, 0 addr65, 2 p2sh, 3 eth, 4 p2tr - the last three have no reference counterpart, their labels are this
+   ecl_found.compressed (1 addr33, 0 addr65, 2 p2sh, 3 eth, 4 p2tr, 5 pub - the last four have no reference counterpart, their labels are this
    program's).  A p2tr hit is printed with all 32 bytes of its output key (h: the eight words of ecl_hip_verify_tr), the others with the 20
    bytes of the record */
-static void report_hit(report_t *r, u8 type, const u32 *h, const sc *key) {
-  char hh[65], kk[65];
-  hex_of_words(hh, h, type == 4 ? 8 : 5);
+static void report_line(report_t *r, const char *label, const char *hh, const sc *key) {
+  char kk[65];
   hex_of_scalar(kk, key);
-  const char *label = type == 4 ? "p2tr" : type == 3 ? "eth" : type == 2 ? "p2sh" : type ? "addr33" : "addr65";
   const struct { FILE *to; const char *fmt; } dest[2] = {{r->quiet ? NULL : stdout, "%s: %s <- %s\n"}, {r->file, "%s\t%s\t%s\n"}};
   pthread_mutex_lock(&r->mu);
   for (int d = 0; d < 2; ++d) {
@@ -61,6 +59,14 @@ static void report_hit(report_t *r, u8 type, const u32 *h, const sc *key) {
   r->found++;
   status_show_locked(r);
   pthread_mutex_unlock(&r->mu);
+}
+/* A pub hit (type 5, -a x) is printed as the compressed public key of the key that was walked, re-derived: h = the eight words of x and,
+   as a ninth, the parity of y (verify_hits) - "pub: <02 / 03><64 hex digits> <- <key>" */
+static void report_hit(report_t *r, u8 type, const u32 *h, const sc *key) {
+  char hh[67];
+  if (type == 5) snprintf(hh, 3, "%02x", 2u | (h[8] & 1u)), hex_of_words(hh + 2, h, 8);
+  else hex_of_words(hh, h, type == 4 ? 8 : 5);
+  report_line(r, type == 5 ? "pub" : type == 4 ? "p2tr" : type == 3 ? "eth" : type == 2 ? "p2sh" : type ? "addr33" : "addr65", hh, key);
 }
 /* `units` more keys checked (status units: the reference counts job_size per job, x6 with -endo, main.c:431); the line
    is redrawn at most every 100 ms; a paused run parks the caller here, between two device calls */
@@ -100,7 +106,7 @@ typedef struct run_t {
   report_t rep;
   int ngpus; /* device contexts (threads); `mul` opens two per GPU */
   ecl_hip *dev[MAX_GPUS];
-  bool a33, a65, p2sh, eth, tr, endo, colour, bin, parse_only, seeded;
+  bool a33, a65, p2sh, eth, tr, pub, endo, colour, bin, parse_only, seeded;
   sc range_s, range_e, stride_k;
   u32 ord_offs, ord_size;
 } run_t;
@@ -122,7 +128,8 @@ static void die_ecl(run_t *run, int g, int rc, const char *what) {
    derived again on the device by the window-table sum (ecl_hip_verify: not the walk kernel; own inversion per key) and
    compared with what the walk reported; a p2sh hit is compared with the script hash of that addr33 hash (ecl_hip_p2sh_hash);
    an eth hit with the address ecl_hip_verify_eth derives from the key (an eth run has no other hits); a p2tr hit with the first 20 bytes
-   of the output key ecl_hip_verify_tr derives (a Taproot run has no other hits), whose 32 bytes go to tr_qx for the found line;
+   of the output key ecl_hip_verify_tr derives (a Taproot run has no other hits), whose 32 bytes go to `full` for the found line;
+   a pub hit with the first 20 bytes of the x of the key's point from ecl_hip_diag_mulg, whose 32 bytes and the parity of y go to `full`;
    a mismatch is fatal, with the reference's diagnostics */
 static void verify_fail(const sc *key, const ecl_found *hit, const u32 *want) {
   char kk[65], lh[41], rh[41];
@@ -130,15 +137,32 @@ static void verify_fail(const sc *key, const ecl_found *hit, const u32 *want) {
   fprintf(stderr, "[!] error: hash mismatch (compressed: %d endo: %d)\npk: %s\nlh: %s\nrh: %s\n", hit->compressed, hit->endo, kk, lh, rh);
   exit(1);
 }
-static void verify_hits(run_t *run, int g, const sc *keys, const ecl_found *hits, u32 n, u32 (*tr_qx)[8]) {
+#define FULL_WORDS 9 /* a whole key for the found line: eight words (p2tr: the output key; pub: x) and the parity of y (pub) */
+static void verify_hits(run_t *run, int g, const sc *keys, const ecl_found *hits, u32 n, u32 (*full)[FULL_WORDS]) {
   if (!n) return;
+  if (run->pub) { /* the key's point by the double-and-add kernel (ecl_hip_diag_mulg: neither the walk nor the window sum), x and y */
+    u64 (*x)[4] = malloc((size_t)n * 32), (*y)[4] = malloc((size_t)n * 32);
+    u8 *fin = malloc(n);
+    int rc = ecl_hip_diag_mulg(run->dev[g], (const uint64_t(*)[4])keys, x, y, fin, n);
+    if (rc != ECL_OK) die_ecl(run, g, rc, "verify");
+    for (u32 i = 0; i < n; ++i) {
+      for (int j = 0; j < 8; ++j) full[i][j] = (u32)(x[i][(7 - j) / 2] >> (32 * ((7 - j) & 1)));
+      full[i][8] = (u32)(y[i][0] & 1);
+      if (hits[i].compressed != 5 || !fin[i] || memcmp(full[i], hits[i].h160, 20)) verify_fail(&keys[i], &hits[i], full[i]);
+    }
+    free(x), free(y), free(fin);
+    return;
+  }
   if (run->tr) {
     u8 *fin = malloc(n);
-    int rc = ecl_hip_verify_tr(run->dev[g], (const uint64_t(*)[4])keys, n, tr_qx, fin);
+    u32 (*qx)[8] = malloc((size_t)n * 32);
+    int rc = ecl_hip_verify_tr(run->dev[g], (const uint64_t(*)[4])keys, n, qx, fin);
     if (rc != ECL_OK) die_ecl(run, g, rc, "verify");
-    for (u32 i = 0; i < n; ++i)
-      if (hits[i].compressed != 4 || !fin[i] || memcmp(tr_qx[i], hits[i].h160, 20)) verify_fail(&keys[i], &hits[i], tr_qx[i]);
-    free(fin);
+    for (u32 i = 0; i < n; ++i) {
+      memcpy(full[i], qx[i], 32), full[i][8] = 0;
+      if (hits[i].compressed != 4 || !fin[i] || memcmp(qx[i], hits[i].h160, 20)) verify_fail(&keys[i], &hits[i], qx[i]);
+    }
+    free(fin), free(qx);
     return;
   }
   if (run->eth) {

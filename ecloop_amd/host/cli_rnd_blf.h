@@ -247,10 +247,12 @@ static void usage(const char *prog) { /* the reference's help text (main.c:750-7
       "  -f <file>       - filter file to search (list of hashes or bloom fitler)\n",
       "  -o <file>       - output file to write found keys (default: stdout)\n",
       "  -t <gpus>       - number of GPUs to use (default: all)\n",
-      "  -a <addr_type>  - address type to search: c - addr33, u - addr65, s - p2sh (nested SegWit, 3...), e - eth (Ethereum), t - p2tr (Taproot, bc1p...) (default: c)\n",
+      "  -a <addr_type>  - address type to search: c - addr33, u - addr65, s - p2sh (nested SegWit, 3...), e - eth (Ethereum), t - p2tr (Taproot, bc1p...), x - pubkey (public key, by its x coordinate) (default: c)\n",
       "                    (c, u, s combine, e.g. cus; c is the default only when no letter is given; eth is searched alone, and with\n",
       "                    it list lines may start with 0x - for blf-gen too; p2tr is searched alone and without -endo: list lines are\n",
-      "                    the 64 hex digits of output keys (tools/p2tr_keys.py makes them from bc1p... addresses), matched on the leading 40)\n",
+      "                    the 64 hex digits of output keys (tools/p2tr_keys.py makes them from bc1p... addresses), matched on the leading 40;\n",
+      "                    pubkey is searched alone, with or without -endo: list lines are public keys (66 digits 02.. / 03.., 130 digits 04..,\n",
+      "                    or the 64 digits of x), matched on the leading 40 digits of x)\n",
       "  -r <range>      - search range in hex format (example: 8000:ffff, default all)\n",
       "  -d <offs:size>  - bit offset and size for search (example: 128:32, default: 0:32)\n",
       "  -q              - quiet mode (no output to stdout; -o required)\n",

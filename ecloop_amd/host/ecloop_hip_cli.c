@@ -115,7 +115,7 @@ static double bring_up(run_t *run, int shown, int real) {
     if (!(keys.w[1] | keys.w[2] | keys.w[3]) && keys.w[0] < largest_call) largest_call = keys.w[0];
   }
   const u32 flags = (run->a33 ? ECL_ADDR33 : 0) | (run->a65 ? ECL_ADDR65 : 0) | (run->p2sh ? ECL_P2SH : 0) | (run->eth ? ECL_ETH : 0) |
-                    (run->tr ? ECL_TR : 0) | (run->endo ? ECL_ENDO : 0);
+                    (run->tr ? ECL_TR : 0) | (run->pub ? ECL_PUB : 0) | (run->endo ? ECL_ENDO : 0);
   pthread_t th[MAX_GPUS];
   bringup_t job[MAX_GPUS];
   for (int g = 0; g < run->ngpus; ++g) {
@@ -154,6 +154,15 @@ int main(int argc, const char **argv) {
   opts_t *o = &run.opt;
   opts_parse(o, argc, argv);
   const char *verb = argc > 1 ? argv[1] : "";
+  /* -a x (no reference counterpart): public keys, matched by their x coordinate (lists of P2PK outputs, spent-from keys, revealed puzzle
+     keys), searched alone, with or without -endo.  Checked before anything is opened; with it the list reader takes public keys only
+     (list_pub: 66 digits 02 / 03, 130 digits 04 on the curve, or the 64 digits of a bare x - hashlist_entries) */
+  run.pub = o->addr && strchr(o->addr, 'x');
+  if (run.pub && strspn(o->addr, "x") != strlen(o->addr)) {
+    fprintf(stderr, "invalid address type '%s': public keys are searched alone (-a x), not together with c, u, s, e or t\n", o->addr);
+    exit(1);
+  }
+  list_pub = run.pub;
   /* -a t (no reference counterpart): Taproot output keys (BIP341 / BIP86 key path, bc1p...), searched alone and without the endomorphism - a
      Taproot list is a different file, and -endo's images collapse onto the same output key.  Checked before anything is opened; with
      it the list reader is strict: only lines of exactly 64 hex digits are entries (hashlist_entries: the search commands' lists and blf-gen) */
@@ -195,9 +204,9 @@ int main(int argc, const char **argv) {
   if (!plan_only) filter_open(&run.flt, o->filter);
   if (o->quiet && !o->outfile && !plan_only) { fprintf(stderr, "quiet mode chosen without output file\n"); exit(1); }
   run.a33 = o->addr ? strchr(o->addr, 'c') != NULL : true, run.a65 = o->addr && strchr(o->addr, 'u');
-  if (run.eth || run.tr) run.a33 = run.a65 = false;
+  if (run.eth || run.tr || run.pub) run.a33 = run.a65 = false;
   run.p2sh = o->addr && strchr(o->addr, 's'); /* no reference counterpart: P2SH-P2WPKH */
-  if (!run.a33 && !run.a65 && !run.p2sh && !run.eth && !run.tr) run.a33 = true; /* main.c:825-827 */
+  if (!run.a33 && !run.a65 && !run.p2sh && !run.eth && !run.tr && !run.pub) run.a33 = true; /* main.c:825-827 */
   run.endo = o->endo && run.cmd != CMD_MUL, run.bin = o->bin && run.cmd == CMD_MUL;
   report_init(&run.rep, o->outfile, o->quiet);
   range_from_option(o->range, &run.range_s, &run.range_e);
@@ -243,7 +252,7 @@ int main(int argc, const char **argv) {
   }
 
   printf("gpus: %d ~ addr33: %d ~ addr65: %d ~ endo: %d%s | filter: ", shown, run.a33, run.a65, run.endo,
-         run.p2sh ? " ~ p2sh: 1" : run.eth ? " ~ eth: 1" : run.tr ? " ~ p2tr: 1" : "");
+         run.p2sh ? " ~ p2sh: 1" : run.eth ? " ~ eth: 1" : run.tr ? " ~ p2tr: 1" : run.pub ? " ~ pub: 1" : "");
   if (run.flt.list) printf("list (%'llu)\n", (unsigned long long)run.flt.nlist);
   else printf("bloom\n");
   if (run.cmd == CMD_ADD) print_scalar_row("range_s", &run.range_s), print_scalar_row("range_e", &run.range_e);

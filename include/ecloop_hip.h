@@ -68,13 +68,23 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
    A Taproot key costs one fixed-base scalar multiplication, about what a `mul` scalar costs: ecl_hip_add_range walks a call in slabs
    (2^26 keys: the points and tweaks of a slab are parked in 6.4 GB of HBM, then multiplied on the `mul` table of the context;
    environment ECL_HIP_TR_SLAB_LOG2 = 12 ... 28 changes the slab, not the results), and tweaked keys count as scalars for the width
-   of that table. */
+   of that table.
+   ECL_PUB (no reference counterpart): the public key itself, matched by its x coordinate - lists of P2PK outputs, spent-from keys, puzzle
+   keys with a revealed public key.  Nothing is hashed on the device: the walk emits x alone (no y of a walked point) and the entry of
+   filters, lists and records is the LEADING 20 BYTES of x, 160 bits like every other type (the Taproot convention; no new format).  A key
+   and its negative share x: the key reported is the one that was walked, the caller re-derives a hit with ecl_hip_diag_mulg (the
+   double-and-add kernel: neither the walk nor the window sum; it returns x and y), compares its leading 20 bytes with the record - all a
+   record or a list entry holds - and has the whole key from it (all 32 bytes of x, and y for the prefix byte).  With ECL_ENDO a key gives
+   three records (x, beta x, beta^2 x: endo = 0, 2, 4), which stand for six keys.  Public keys are searched alone: ECL_PUB is valid by
+   itself or with ECL_ENDO; together with any of ECL_ADDR33, ECL_ADDR65, ECL_P2SH, ECL_ETH, ECL_TR (or the refused bits 8 and 32) it is
+   ECL_E_ARG. */
 #define ECL_ADDR33 1u
 #define ECL_ADDR65 2u
 #define ECL_ENDO 4u
 #define ECL_P2SH 16u
 #define ECL_ETH 64u
 #define ECL_TR 128u
+#define ECL_PUB 256u
 
 /* return codes */
 #define ECL_OK 0
@@ -98,7 +108,7 @@ typedef struct ecl_found {
   uint8_t endo;
   uint8_t compressed; /* the address type: 1 = addr33, 0 = addr65, 2 = P2SH-P2WPKH (only for a context opened with ECL_P2SH),
                          3 = Ethereum (ECL_ETH; h160 holds the address), 4 = Taproot (ECL_TR, label p2tr; h160 holds the leading
-                         20 bytes of the output key) */
+                         20 bytes of the output key), 5 = public key (ECL_PUB, label pub; h160 holds the leading 20 bytes of x) */
   uint8_t pad[2];
 } ecl_found; /* 32 bytes */
 
@@ -299,7 +309,7 @@ int ecl_hip_get_coverage(ecl_hip *h, uint64_t *requested, uint64_t *covered, uin
 /* Known-answer test of the device code (hash160 of 1*G, 2*G, 0xdc2a04*G, both encodings, via the double-and-add
    kernel; the P2SH-P2WPKH hash and the Ethereum address of 1*G) and a cross-check of the walk kernel against it over 4096 consecutive
    keys (with ECL_P2SH: the script hashes too; with ECL_ETH: the Ethereum addresses, against ecl_hip_verify_eth; with ECL_TR: the output
-   keys, against ecl_hip_verify_tr), and the Taproot output keys of the three private keys (ecl_hip_verify_tr).  ecl_hip_open() runs it
+   keys, against ecl_hip_verify_tr; with ECL_PUB: the leading 20 bytes of x of the double-and-add kernel's points), and the Taproot output keys of the three private keys (ecl_hip_verify_tr).  ecl_hip_open() runs it
    (a few ms) unless the environment has ECL_HIP_SKIP_SELFTEST=1; a failure makes open return ECL_E_SELFTEST. */
 int ecl_hip_selftest(ecl_hip *h);
 

@@ -21,7 +21,8 @@ What the numbers are used for:
 
 usage: tools/isa_mix.py [file.s] [mangled kernel name] [--json]     |     tools/isa_mix.py --all   (every instantiation: profiles/rNN_static_mix.json)
        tools/isa_mix.py --eth   (the three Ethereum kernels)
-       tools/isa_mix.py --tr    (the Taproot kernels: registers, loops, the static VALU counts of the tagged hash and the window loop)"""
+       tools/isa_mix.py --tr    (the Taproot kernels: registers, loops, the static VALU counts of the tagged hash and the window loop)
+       tools/isa_mix.py --pub   (the public-key kernels: registers, loops, the static per-key VALU count beside -a c's from the same assembly)"""
 import json
 import os
 import re
@@ -280,6 +281,43 @@ def analyse_tr(path=ASM):
     return out
 
 
+# the public-key kernels (-a x, searched alone): the walk with x-only emission and `mul`'s body with x alone; a dictionary of their own
+PUB_KERNELS = {"-a x": "_Z9k_add_pubILb0EEv8add_args", "-a x -endo": "_Z9k_add_pubILb1EEv8add_args",
+               "mul -a x": "_Z15k_mul_check_pubPKjjj4wtab8add_argsPjjj"}
+HASH160_VALU = 2248  # the two compression functions of one hash160, VALU lane-ops per key
+
+
+def analyse_pub(path=ASM):
+    """every public-key kernel: registers / spills, its loops (depth, VALU, scratch), `scratch_below_top`: scratch instructions in the loops
+    below its launch loop (k_add_pub) / round loops (k_mul_check_pub) - tests/test_pub_host.py wants 0; for the walk kernels the static
+    per-key VALU count (`which` loop + half the table loop's own body + half the prefix loop), and beside it `-a c`'s from the same assembly
+    and that figure less the hash160: the hash must be gone"""
+    out = {}
+    ref = analyse(path, K_ADD33)["per_key_static"]["valu"]
+    for label, k in PUB_KERNELS.items():
+        a = analyse(path, k)
+        sp = spills(path, k).get(k)
+        loops = a["loops"]
+        deep = [l for l in loops if l["depth"] >= 2]
+        r = {"kernel": k, "registers": sp, "total": a["total"],
+             "loops": [{x: l[x] for x in ("header", "depth", "parent", "valu", "mad64", "scratch", "scratch_at_calls")} for l in loops],
+             "scratch_below_top": sum(l["scratch"] for l in deep)}
+        if "k_add_pub" in k:
+            r["which_loop_valu"], r["table_loop_valu"], r["prefix_loop_valu"] = a["which_loop"]["valu"], a["table_loop"]["valu"], a["prefix_loop"]["valu"]
+            r["per_key_valu"] = a["per_key_static"]["valu"]
+            r["addr33_per_key_valu"], r["addr33_less_hash160"] = ref, ref - HASH160_VALU
+            if "ILb1E" in k:  # -endo: the loop over the three x values (one probe each), the child of the `which` loop that has children itself
+                which = max((l for l in loops if l["depth"] == 3), key=lambda l: l["valu"])["header"]
+                kids = [l for l in loops if l["parent"] == which and any(c["parent"] == l["header"] for c in loops)]
+                r["image_loop_valu"] = max((l["valu"] for l in kids), default=None)
+        else:
+            m = analyse_mul(path, k)
+            r["scratch_in_round_loops"] = sum(l["scratch"] for l in loops if l["depth"] == 1)
+            r["window_loop_valu"], r["window_loop_mad64"], r["walk_back_loop_valu"] = m["window_loop"]["valu"], m["window_loop"]["mad64"], m["walk_back_loop"]["valu"]
+        out[label] = r
+    return out
+
+
 def analyse_all(path=ASM):
     """every shipped instantiation of the two search kernels: fingerprint, registers / spills, and the scratch instructions inside the
     per-key loops (k_add: prefix-product, table and `which` loops; k_mul_check: window loop) - tests/test_profiles_fresh.py wants 0 there"""
@@ -308,6 +346,10 @@ def main():
     if "--tr" in sys.argv:
         rest = [a for a in sys.argv[1:] if not a.startswith("--")]
         print(json.dumps(analyse_tr(rest[0] if rest else ASM), indent=1))
+        return
+    if "--pub" in sys.argv:
+        rest = [a for a in sys.argv[1:] if not a.startswith("--")]
+        print(json.dumps(analyse_pub(rest[0] if rest else ASM), indent=1))
         return
     if "--all" in sys.argv:
         rest = [a for a in sys.argv[1:] if not a.startswith("--")]
