@@ -36,7 +36,7 @@ EXPORTS = [
     "ecl_hip_mul_batch", "ecl_hip_bloom_insert", "ecl_hip_get_bloom", "ecl_hip_set_geometry", "ecl_hip_get_geometry", "ecl_hip_get_timing", "ecl_hip_reset_timing", "ecl_hip_selftest", "ecl_hip_strerror",
     "ecl_hip_last_error", "ecl_hip_diag_fe", "ecl_hip_diag_mulg", "ecl_hip_diag_hash160", "ecl_hip_diag_bloom", "ecl_hip_diag_bloom_mod", "ecl_hip_set_lookahead", "ecl_hip_set_scan_end", "ecl_hip_get_lookahead_stats",
     "ecl_hip_get_setup_timing", "ecl_hip_get_mul_timing", "ecl_hip_bloom_insert_count", "ecl_hip_alloc_host", "ecl_hip_free_host", "ecl_hip_verify", "ecl_hip_sort_list", "ecl_hip_reserve_mul", "ecl_hip_mul_batch_raw", "ecl_hip_set_mul_window", "ecl_hip_get_mul_window", "ecl_hip_fetch_found", "ecl_hip_plan_geometry",
-    "ecl_hip_p2sh_hash", "ecl_hip_get_coverage", "ecl_hip_diag_drop_round", "ecl_hip_verify_eth", "ecl_hip_verify_tr", "ecl_hip_diag_tr",
+    "ecl_hip_p2sh_hash", "ecl_hip_get_coverage", "ecl_hip_diag_drop_round", "ecl_hip_verify_eth", "ecl_hip_verify_tr", "ecl_hip_diag_tr", "ecl_hip_diag_limbs",
 ]
 
 _lib = None
@@ -105,6 +105,7 @@ def load():
     lib.ecl_hip_last_error.argtypes = [P]
     lib.ecl_hip_last_error.restype = C.c_char_p
     lib.ecl_hip_diag_fe.argtypes = [P, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
+    lib.ecl_hip_diag_limbs.argtypes = [P, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     lib.ecl_hip_diag_mulg.argtypes = [P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     lib.ecl_hip_diag_hash160.argtypes = [P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     lib.ecl_hip_diag_bloom.argtypes = [P, C.c_void_p, C.c_void_p, C.c_uint32]
@@ -370,6 +371,17 @@ class Device:
         R = np.zeros_like(A)
         self._chk(self.lib.ecl_hip_diag_fe(self.h, op, A.ctypes.data, Bv.ctypes.data, R.ctypes.data, len(A)))
         return ints_of(R)
+
+    def diag_limbs(self, op, cases):
+        """one operation of csrc/limb_ops.h on raw 9x29 limbs: cases = (n, 6, 9) uint32 -> (results (n, 4, 9) uint32, flags (n,) uint32);
+        nothing is normalised on the way in or out"""
+        X = np.ascontiguousarray(cases, dtype=np.uint32)
+        if X.ndim != 3 or X.shape[1:] != (6, 9):
+            raise ValueError("cases must have the shape (n, 6, 9)")
+        out = np.zeros((len(X), 4, 9), dtype=np.uint32)
+        flag = np.zeros(len(X), dtype=np.uint32)
+        self._chk(self.lib.ecl_hip_diag_limbs(self.h, op, X.ctypes.data, out.ctypes.data, flag.ctypes.data, len(X)))
+        return out, flag
 
     def diag_mulg(self, ks):
         K = limbs_array(ks)

@@ -21,6 +21,24 @@ extern "C" int ecl_hip_diag_fe(ecl_hip* h, int op, const uint64_t (*a)[4], const
   return ECL_OK;
 }
 
+extern "C" int ecl_hip_diag_limbs(ecl_hip* h, int op, const uint32_t (*in)[LIMB_IN][FE_LIMBS], uint32_t (*out)[LIMB_OUT][FE_LIMBS],
+                                  uint32_t* flag, uint32_t n) {
+  if (!h || !in || !out || !flag || n == 0 || op < 0 || op >= LIMB_OPS) return ECL_E_ARG;
+  HIPCHK(h, hipSetDevice(h->dev));
+  const size_t bin = (size_t)n * LIMB_IN * FE_LIMBS * 4, bout = (size_t)n * LIMB_OUT * FE_LIMBS * 4;
+  dbuf<u32> di, dout, df;
+  HIPCHK(h, hipMalloc(&di.p, bin));
+  HIPCHK(h, hipMalloc(&dout.p, bout));
+  HIPCHK(h, hipMalloc(&df.p, (size_t)n * 4));
+  HIPCHK(h, hipMemcpy(di.p, in, bin, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_diag_limbs, dim3((unsigned)(((u64)n + 63) / 64)), dim3(64), 0, h->stream, op, di.p, dout.p, df.p, n);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, hipMemcpy(out, dout.p, bout, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(flag, df.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return ECL_OK;
+}
+
 extern "C" int ecl_hip_diag_mulg(ecl_hip* h, const uint64_t (*k)[4], uint64_t (*x)[4], uint64_t (*y)[4], uint8_t* ok,
                                  uint32_t n) {
   if (!h || !k || !x || !y || n == 0) return ECL_E_ARG;

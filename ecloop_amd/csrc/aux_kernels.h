@@ -3,6 +3,7 @@
 #pragma once
 #include "add_kernel.h"
 #include "ec.h"
+#include "limb_ops.h"
 // ------------------------------------------------------------------------------------------------ diagnostics
 __global__ void k_diag_fe(int op, const u32* a, const u32* b, u32* r, u32 n) {
   u32 i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -30,6 +31,23 @@ __global__ void k_diag_fe(int op, const u32* a, const u32* b, u32* r, u32 n) {
   fe_to_words(zw, z);
 #pragma unroll
   for (int w = 0; w < 8; ++w) r[(size_t)i * 8 + w] = zw[w];
+}
+// one operation of limb_ops.h per thread on raw limbs: in = n x LIMB_IN x 9, out = n x LIMB_OUT x 9 u32, nothing normalised on the way
+__global__ void k_diag_limbs(int op, const u32* in, u32* out, u32* flag, u32 n) {
+  u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  fe x[LIMB_IN], z[LIMB_OUT];
+#pragma unroll
+  for (int e = 0; e < LIMB_IN; ++e)
+#pragma unroll
+    for (int l = 0; l < FE_LIMBS; ++l) x[e].n[l] = in[((size_t)i * LIMB_IN + e) * FE_LIMBS + l];
+  u32 f;
+  limb_op(op, x, z, f);
+#pragma unroll
+  for (int e = 0; e < LIMB_OUT; ++e)
+#pragma unroll
+    for (int l = 0; l < FE_LIMBS; ++l) out[((size_t)i * LIMB_OUT + e) * FE_LIMBS + l] = z[e].n[l];
+  flag[i] = f;
 }
 __global__ void k_diag_hash(const u32* x, const u32* y, u32* h33, u32* h65, u32 n) {
   u32 i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -11,7 +11,19 @@
 // 2^256 = 0x1000003D1 (mod p) is two small multiplies per column.  29 bits is the widest limb that still leaves
 // room for lazy additions: 81 products per multiplication instead of 100 with 26-bit limbs.
 //
-// Magnitude discipline: a value has magnitude m if n[i] <= m * 2^29 (+ a few units) for i < 8 and n[8] <= m * 2^24.
+// Magnitude discipline: a value has magnitude m if n[i] <= m * (2^29 + E) for i < 8 and n[8] <= m * (2^24 + E), with E = 449:
+// the largest amount by which limb 2 of a product (fe_mul, fe_sqr, fe_mul2, fe_sqr2) can exceed 2^29 - 1.  Every other limb of a
+// product is masked (n[i] <= 2^29 - 1, n[8] <= 2^24 - 1); limb 2 takes the last carry of fe_mul_tail unmasked.  That carry, for
+// operands inside this definition with m1 * m2 = M <= 7 (write A = 2^29 + E, T = 2^24 + E):
+//   * every column sum stays below 2^64 (the largest, column 8: 9 M A^2 < 63.001 * 2^58), so every column carry is below 2^35;
+//   * column 15 = a7 b8 + a8 b7 + carry <= 2 M A T + 2^35, column 16 = a8 b8 + carry <= M T^2 + (2 M A T + 2^35) / 2^29, so what
+//     fe_mul_tail gets as d = column 16 >> 29 is at most 3 670 212 < 7 * 2^19 + 2^8 (< 2^23: it is used as a 32-bit factor);
+//   * c after ">>= 24" and "+= d << 13" is at most d * 2^13 + (2^35 + 2^37 + d * R0 + 2^29) / 2^24 < d * 2^13 + 2^15;
+//   * the carry into limb 2 is ((c * 977 + n[0]) / 2^29 + 8 c + n[1]) / 2^29 with n[0], n[1] < 2^29: below c / 2^26 + 1.001
+//     < d / 2^13 + 1.002 < 449.03, so at most 449.
+// The bound does not move for E up to 1024, so it holds for lazy sums of such products, and it is reached: a 1 x 7 product with every
+// limb at its ceiling has limb 2 = 2^29 - 1 + 449 (tests/limb_cases.py puts every function at these ceilings, on the host and on the
+// device).  fe_normalize_weak returns limbs below 2^29 and n[8] <= 2^24 + 6 (bit 24 and the carry of its one pass), a value below 2p.
 // fe_mul accepts magnitudes with m1*m2 <= 7 (9 * 7 * 2^58 < 2^64), fe_sqr magnitude <= 2; both return magnitude 1;
 // fe_add adds magnitudes; fe_neg(a, m) returns magnitude m+1; limbs must stay below 2^32, i.e. m <= 7.
 // Only fe_normalize() gives the canonical residue in [0, p), and only canonical values are serialised for hashing,
@@ -116,7 +128,8 @@ FE_FN void fe_to_words(u32 w[8], const fe& a) {
 }
 
 // magnitude 1 result: the overflow above 2^256 folded in first (2^256 = 2^32 + 977: limb 1 gets x * 8), then one
-// carry pass
+// carry pass.  Limbs 0..7 come out below 2^29; n[8] keeps what the pass carries into it: at most 2^24 - 1 + 7 for an
+// input of magnitude 7 (so bit 24 may be set); the value is below 2p
 FE_FN void fe_normalize_weak(fe& a) {
   u32 x = a.n[8] >> 24;
   a.n[8] &= FE_TOP;
@@ -207,7 +220,7 @@ FE_FN void fe_mul_tail(fe& r, u64 c, u64 d64, u32 t8) {
   // the carry into limb 2 as an opaque 32-bit value: left visible, the backend keeps limb 2 as the untruncated 64-bit
   // sum and multiplies the NEXT product by it as a 64 x 32 bit value (one more v_mad_u64_u32 and two moves per use:
   // 9 uses per multiplication) - the same dropped-truncation family as the FE_HIDE24 bug, harmless only because the
-  // carry is tiny
+  // carry is tiny (at most E = 449: the derivation is at the top of this file)
   u32 cy = (u32)e;
   FE_HIDE24(cy);
   r.n[2] += cy;

@@ -4,6 +4,7 @@
 #include "../bloom.h"
 #include "../ec.h"
 #include "../hash160.h"
+#include "../limb_ops.h"
 #include <string.h>
 
 static void words(u32 w[8], const uint64_t a[4]) {
@@ -56,6 +57,22 @@ void dh_fe_op(int op, uint64_t r[4], const uint64_t a[4], const uint64_t b[4]) {
   default: z = fe_zero();
   }
   st(r, z);
+}
+// n cases of one operation of limb_ops.h on raw limbs (the host side of ecl_hip_diag_limbs: same function, same layout); returns 0 for
+// an unknown op
+int dh_limb_op(int op, const uint32_t* in, uint32_t* out, uint32_t* flag, uint32_t n) {
+  if (op < 0 || op >= LIMB_OPS) return 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    fe x[LIMB_IN], z[LIMB_OUT];
+    for (int e = 0; e < LIMB_IN; ++e)
+      for (int l = 0; l < FE_LIMBS; ++l) x[e].n[l] = in[((size_t)i * LIMB_IN + e) * FE_LIMBS + l];
+    u32 f;
+    if (!limb_op(op, x, z, f)) return 0;
+    for (int e = 0; e < LIMB_OUT; ++e)
+      for (int l = 0; l < FE_LIMBS; ++l) out[((size_t)i * LIMB_OUT + e) * FE_LIMBS + l] = z[e].n[l];
+    flag[i] = f;
+  }
+  return 1;
 }
 void dh_hash160(uint32_t h33[5], uint32_t h65[5], const uint64_t x[4], const uint64_t y[4]) {
   u32 fx[8], fy[8];

@@ -33,7 +33,7 @@
  * section 3 (sweeps and their records belong to the group of contexts that share a filter; one mutex per group; records are immutable
  * once published).  ecl_hip_strerror returns static text; ecl_hip_last_error returns the handle's own buffer (same thread rule).
  *
- * Exports: exactly the 44 ecl_hip_* functions declared below (the library is linked with a version script; `nm -D` shows nothing else).
+ * Exports: exactly the 45 ecl_hip_* functions declared below (the library is linked with a version script; `nm -D` shows nothing else).
  */
 #ifndef ECLOOP_HIP_H
 #define ECLOOP_HIP_H
@@ -318,6 +318,11 @@ int ecl_hip_selftest(ecl_hip *h);
    10 inv by the addition chain of lib/ecc.c:463-520, 11 1 / (4b - 2a) by division steps from an unnormalised operand; a,b,r: n field
    elements as 4 little-endian u64 limbs */
 int ecl_hip_diag_fe(ecl_hip *h, int op, const uint64_t (*a)[4], const uint64_t (*b)[4], uint64_t (*r)[4], uint32_t n);
+/* one field or point function on RAW LIMBS (9 limbs of 29 bits per element, nothing normalised on the way in or out), for the tests at
+   the limits of the magnitude contract: op = an operation of csrc/limb_ops.h (the list is written there only), in = n cases of up to six
+   input elements, out = up to four result elements per case (unused ones zero), flag = a result word per case (parity, is-zero,
+   infinity).  The caller keeps every limb inside the magnitude the function documents; an unknown op is ECL_E_ARG. */
+int ecl_hip_diag_limbs(ecl_hip *h, int op, const uint32_t (*in)[6][9], uint32_t (*out)[4][9], uint32_t *flag, uint32_t n);
 /* affine public keys of n scalars (double-and-add kernel); ok[i] = 0 for the point at infinity */
 int ecl_hip_diag_mulg(ecl_hip *h, const uint64_t (*k)[4], uint64_t (*x)[4], uint64_t (*y)[4], uint8_t *ok, uint32_t n);
 /* hash160 of n affine points, both encodings */

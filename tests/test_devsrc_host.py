@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import limb_cases
 import orc
 from synth import synth_bloom_words
 
@@ -78,6 +79,34 @@ def test_inverse_by_division_steps_equals_the_addition_chain(D):
     for a in vals[:300]:
         b = rnd.randrange(P)
         assert op(12, a, b) == pow((4 * b - 2 * a) % P, P - 2, P)
+
+
+@pytest.mark.parametrize("base", limb_cases.BASES)
+def test_raw_limbs_at_the_magnitude_limits(D, base):
+    """Every field function and point step of fe256.h / ec.h / pub_emit.h on RAW limbs (csrc/limb_ops.h through dh_limb_op: nothing
+    normalised on the way in or out) at the ceilings of the magnitudes the headers document - every limb at m 2^29 + m E at once, limbs
+    at and just under the ceiling, multiples of p in limb form, values that take fe_normalize's final subtraction either way - against
+    Python integers (tests/limb_cases.py: the generator and the reference, shared with the GPU test).  Every product's limb 2 stays
+    within the bound E = 449 that fe256.h derives; the largest excess the host shows is exactly that bound (a 1 x 7 product).
+    One test case per operation (fe_neg for m = 1 .. 6 under LIMB_NEG1, the three jac_madd branches apart)."""
+    def call(op, cases):
+        out = np.zeros((len(cases), limb_cases.LIMB_OUT, 9), np.uint32)
+        flag = np.zeros(len(cases), np.uint32)
+        assert D.dh_limb_op(op, C.c_void_p(cases.ctypes.data), C.c_void_p(out.ctypes.data), C.c_void_p(flag.ctypes.data), C.c_uint32(len(cases))) == 1
+        return out, flag
+
+    got = limb_cases.run(call, base)
+    print("host:", base, got)
+    assert got["left_out"] == 0 and got["cases"] == got["planned"] + got["moved"] > 0, got
+    assert got["limb2_excess"] is None or got["limb2_excess"] <= limb_cases.E, got
+    if base == "LIMB_MUL":  # the bound is reached: a 1 x 7 product with every limb at its ceiling
+        assert got["limb2_excess"] == limb_cases.E, got
+
+
+def test_raw_limb_entry_refuses_an_unknown_operation(D):
+    one = np.zeros((1, limb_cases.LIMB_IN, 9), np.uint32)
+    for op in (-1, limb_cases.OP["LIMB_OPS"], 1 << 20):  # an unknown operation is refused, not run
+        assert D.dh_limb_op(op, C.c_void_p(one.ctypes.data), C.c_void_p(one.ctypes.data), C.c_void_p(one.ctypes.data), C.c_uint32(1)) == 0
 
 
 def test_scalar_mul_and_hash160(D):

@@ -4,6 +4,7 @@ import random
 import numpy as np
 import pytest
 
+import limb_cases
 import orc
 from synth import synth_bloom_words
 
@@ -54,6 +55,20 @@ def test_inverse_by_division_steps_and_by_the_addition_chain(dev):
     assert dev.diag_fe(10, a[:4000]) == want[:4000]
     b = [rnd.randrange(P) for _ in a[:4000]]
     assert dev.diag_fe(11, a[:4000], b) == [pow((4 * y - 2 * x) % P, P - 2, P) for x, y in zip(a, b)]
+
+
+@pytest.mark.parametrize("base", limb_cases.BASES)
+def test_raw_limbs_at_the_magnitude_limits(dev, base):
+    """The cases of tests/test_devsrc_host.py::test_raw_limbs_at_the_magnitude_limits (the same generator, the same seed, the same
+    reference in Python integers) through k_diag_limbs: the code the GPU runs for fe256.h / ec.h / pub_emit.h with every limb at the
+    ceiling of its documented magnitude, raw limbs in and out.  Every case equals Python, none is left out, and every product's limb 2
+    stays within fe256.h's bound E = 449; a 1 x 7 product with every limb at its ceiling reaches it."""
+    got = limb_cases.run(dev.diag_limbs, base)
+    print("device:", base, got)
+    assert got["left_out"] == 0 and got["cases"] == got["planned"] + got["moved"] > 0, got
+    assert got["limb2_excess"] is None or got["limb2_excess"] <= limb_cases.E, got
+    if base == "LIMB_MUL":  # the bound is reached: a 1 x 7 product with every limb at its ceiling
+        assert got["limb2_excess"] == limb_cases.E, got
 
 
 def test_scalar_mul_and_hash160(dev):
@@ -179,6 +194,16 @@ def test_c_abi_error_codes():
         assert lib.ecl_hip_set_lookahead(h, 0) == 0 and lib.ecl_hip_set_lookahead(h, 1 << 26) == 0 and lib.ecl_hip_set_scan_end(h, None) == 0
         assert lib.ecl_hip_set_scan_end(None, None) == -1 and lib.ecl_hip_get_lookahead_stats(None, None, None, None, None) == -1
         assert lib.ecl_hip_get_lookahead_stats(h, None, None, None, None) == 0
+        # raw-limb diagnostics: null pointers, no cases, an unknown operation
+        cin, cout, cfl = np.zeros((2, 6, 9), np.uint32), np.zeros((2, 4, 9), np.uint32), np.zeros(2, np.uint32)
+        assert lib.ecl_hip_diag_limbs(None, 0, cin.ctypes.data, cout.ctypes.data, cfl.ctypes.data, 2) == -1
+        assert lib.ecl_hip_diag_limbs(h, 0, None, cout.ctypes.data, cfl.ctypes.data, 2) == -1
+        assert lib.ecl_hip_diag_limbs(h, 0, cin.ctypes.data, None, cfl.ctypes.data, 2) == -1
+        assert lib.ecl_hip_diag_limbs(h, 0, cin.ctypes.data, cout.ctypes.data, None, 2) == -1
+        assert lib.ecl_hip_diag_limbs(h, 0, cin.ctypes.data, cout.ctypes.data, cfl.ctypes.data, 0) == -1
+        for bad in (-1, limb_cases.OP["LIMB_OPS"], 1 << 20):
+            assert lib.ecl_hip_diag_limbs(h, bad, cin.ctypes.data, cout.ctypes.data, cfl.ctypes.data, 2) == -1
+        assert lib.ecl_hip_diag_limbs(h, 0, cin.ctypes.data, cout.ctypes.data, cfl.ctypes.data, 2) == 0 and not cout.any() and not cfl.any()
     finally:
         lib.ecl_hip_close(h)
     lib.ecl_hip_close(None)  # no-op
