@@ -10,6 +10,9 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ECLOOP_HIP_LIB") or os.path.join(PKG, "libecloop_hip.so")  # override: A/B builds
 
 ADDR33, ADDR65, ENDO, P2SH, ETH, TR, PUB = 1, 2, 4, 16, 64, 128, 256
+ORIGIN, INSERT = 512, 1024  # the two walks of `bsgs`, each valid only beside PUB alone (include/ecloop_hip.h)
+E_ARG = -1
+E_RANGE = -6
 E_OVERFLOW = -4
 E_COVERAGE = -8  # the device did not hash every key of the call (include/ecloop_hip.h, section 1)
 
@@ -130,9 +133,13 @@ def ints_of(arr):
 class Device:
     """One GPU context (ecl_hip handle)."""
 
-    def __init__(self, device=0, a33=True, a65=False, endo=False, ord_offs=0, p2sh=False, eth=False, tr=False, pub=False):
+    def __init__(self, device=0, a33=True, a65=False, endo=False, ord_offs=0, p2sh=False, eth=False, tr=False, pub=False, origin=False,
+                 insert=False):
         if pub and (a33 or a65 or p2sh or eth or tr):  # (before the library is asked)
             raise ValueError("public keys are searched alone: Device(a33=False, pub=True), with or without endo")
+        if (origin or insert) and (not pub or endo or (origin and insert)):
+            raise ValueError("origin and insert are the walks of bsgs: Device(a33=False, pub=True, origin=True) or (..., insert=True), no endo")
+        self.origin, self.insert = bool(origin), bool(insert)
         self.lib = load()
         self.h = C.c_void_p()
         self.a33, self.a65, self.endo, self.p2sh, self.eth, self.tr = bool(a33), bool(a65), bool(endo), bool(p2sh), bool(eth), bool(tr)
@@ -141,7 +148,8 @@ class Device:
             raise ValueError("eth is searched alone: Device(a33=False, eth=True)")
         if tr and (a33 or a65 or p2sh or eth or endo):
             raise ValueError("Taproot is searched alone and without the endomorphism: Device(a33=False, tr=True)")
-        flags = (ADDR33 if a33 else 0) | (ADDR65 if a65 else 0) | (P2SH if p2sh else 0) | (ETH if eth else 0) | (TR if tr else 0) | (PUB if pub else 0) | (ENDO if endo else 0)
+        flags = (ADDR33 if a33 else 0) | (ADDR65 if a65 else 0) | (P2SH if p2sh else 0) | (ETH if eth else 0) | (TR if tr else 0) | (PUB if pub else 0) | (ENDO if endo else 0) | \
+                (ORIGIN if origin else 0) | (INSERT if insert else 0)
         rc = self.lib.ecl_hip_open(C.byref(self.h), device, flags, ord_offs)
         if rc != 0:
             msg = self.lib.ecl_hip_last_error(self.h).decode() if self.h else ""
@@ -206,11 +214,15 @@ class Device:
         self._chk(self.lib.ecl_hip_plan_geometry(self.h, nkeys, C.byref(b), C.byref(t), C.byref(nb)))
         return b.value, t.value, nb.value
 
-    def add_range(self, start, nkeys, cap=4096):
-        """-> (records as numpy structured array, total hit count). Raises on overflow unless total <= cap."""
+    def add_range(self, start, nkeys, cap=4096, origin=None):
+        """-> (records as numpy structured array, total hit count). Raises on overflow unless total <= cap.
+        A context opened with origin=True takes origin=(x, y), the affine origin point O: the call walks O + (start + j * stride) G.  One
+        opened with insert=True sets the keys' filter bits and reports nothing (total 0)."""
         out = np.zeros(cap, dtype=FOUND_DTYPE)
         n = C.c_uint32()
-        s = limbs(start)
+        if self.origin != (origin is not None):
+            raise ValueError("add_range(origin=(x, y)) goes with Device(origin=True), and only with it")
+        s = limbs(start) if origin is None else np.concatenate([limbs(start), limbs(origin[0]), limbs(origin[1])])
         rc = self.lib.ecl_hip_add_range(self.h, s.ctypes.data, nkeys, out.ctypes.data, cap, C.byref(n))
         self._chk(rc, allow=(E_OVERFLOW,))
         return out[: min(n.value, cap)], n.value

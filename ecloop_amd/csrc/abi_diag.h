@@ -232,23 +232,29 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   const u64 save_words = h->bloom_words, save_list_n = h->list_n;
   u32* save_list = h->d_list;
   h->d_list = nullptr, h->list_n = 0;
-  std::vector<u64> ones(64, ~0ull);
+  // ECL_ORIGIN: the same walk from the origin O = 0xdc2a04 G (its x, y from (1)), against the double-and-add kernel's (start + j s + 0xdc2a04) G;
+  // ECL_INSERT: the walk sets bits in a zeroed filter, compared with the filter the host builds from the double-and-add kernel's x
+  const bool origin = h->flags & ECL_ORIGIN, insert = h->flags & ECL_INSERT;
+  std::vector<u64> ones(insert ? 4099 : 64, insert ? 0ull : ~0ull), got_bits(insert ? 4099 : 0);
   h->d_bloom = nullptr, h->bloom_words = 0;
   h->B = 16, h->Tmax = 256, h->B_auto = false;
-  const uint64_t start[4] = {0x0123456789abcdefull, 0x1f, 0, 0};
+  uint64_t start[12] = {0x0123456789abcdefull, 0x1f, 0, 0};
+  memcpy(start + 4, x[2], 32), memcpy(start + 8, y[2], 32);
   const u32 per_key = ((h->flags & ECL_ADDR33) ? 1 : 0) + ((h->flags & ECL_ADDR65) ? 1 : 0) + ((h->flags & ECL_P2SH) ? 1 : 0) +
                       ((h->flags & ECL_ETH) ? 1 : 0) + ((h->flags & ECL_TR) ? 1 : 0) + ((h->flags & ECL_PUB) ? 1 : 0);
-  const u32 cap = N * per_key * ((h->flags & ECL_ENDO) ? ((h->flags & ECL_PUB) ? 3 : 6) : 1);  // (a public key and its negative share x: three images)
+  const u32 cap = insert ? 0 : N * per_key * ((h->flags & ECL_ENDO) ? ((h->flags & ECL_PUB) ? 3 : 6) : 1);  // (a public key and its negative share x: three images)
   std::vector<ecl_found> recs(cap);
   u32 n = 0;
   rc = ecl_hip_set_bloom(h, ones.data(), ones.size());
-  if (rc == ECL_OK) rc = ecl_hip_add_range(h, start, N, recs.data(), cap, &n);
+  if (rc == ECL_OK) rc = ecl_hip_add_range(h, start, N, cap ? recs.data() : nullptr, cap, &n);
+  if (rc == ECL_OK && insert) rc = ecl_hip_get_bloom(h, got_bits.data(), got_bits.size());
   std::vector<uint64_t> ks((size_t)N * 4), xs((size_t)N * 4), ys((size_t)N * 4);
   std::vector<uint32_t> r33((size_t)N * 5), r65((size_t)N * 5), rsh((size_t)N * 5), reth((size_t)N * 5);
   std::vector<uint8_t> eok(N);
   std::vector<uint32_t> rtr((h->flags & ECL_TR) ? (size_t)N * 8 : 0);
   const u256 s = sc_pow2(h->offs);
   u256 cur = sc_reduce(u256_from(start));
+  if (origin) cur = sc_add(cur, u256_from(KS[2]));
   for (u32 i = 0; i < N; ++i) {
     memcpy(&ks[(size_t)i * 4], cur.w, 32);
     cur = sc_add(cur, s);
@@ -276,7 +282,22 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   h->kernel_ms = 0, h->launches = 0, h->keys = 0, h->setup_ms = 0, h->setups = 0;
   h->cov_requested = save_cov[0], h->cov_covered = save_cov[1], h->cov_device = save_cov[2];
   if (rc != ECL_OK) return rc;
-  u32 seen = 0;
+  if (insert) {
+    const bloom_t bl = bloom_make(nullptr, ones.size());
+    for (u32 i = 0; i < N; ++i) {
+      u64 a[5];
+      bloom_words_of(a, &rpub[(size_t)i * 5]);
+      for (int p = 0; p < 20; ++p) {
+        const u64 idx = bloom_index(a, p);
+        ones[bloom_mod(bl, idx >> 6)] |= 1ull << (idx & 63);
+      }
+    }
+    if (n != 0 || ones != got_bits) {
+      h->err = "the filter the insert walk built disagrees with the double-and-add kernel's";
+      return ECL_E_SELFTEST;
+    }
+  }
+  u32 seen = insert ? N * per_key : 0;
   bool good = n == cap;
   for (u32 i = 0; i < n && good; ++i) {
     const ecl_found& f = recs[i];

@@ -385,6 +385,18 @@ __device__ __forceinline__ void pub_check(const add_args& a, cand_queues& q, boo
   }
 }
 
+// ---- the baby table of `bsgs` (ECL_INSERT): what k_add_pub_ins does with a point's x instead of probing it - the 20 bits of its leading
+// 20 bytes are SET in the resident filter (blf_add; 20 atomic ORs).  Only keys of the call (live): the centres, jump points and the keys of
+// a last group beyond nkeys that the walk computes as well leave no bit.  No rings, no records.
+__device__ __forceinline__ void pub_insert(const add_args& a, bool live, const fe& x) {
+  if (!live) return;
+  u64 idx[20];
+  pub_insert_idx(idx, x);
+  unsigned long long* bits = (unsigned long long*)a.bloom.bits;
+#pragma unroll
+  for (int p = 0; p < 20; ++p) atomicOr(bits + bloom_mod(a.bloom, idx[p] >> 6), 1ull << (idx[p] & 63));
+}
+
 // waves per SIMD the register allocator must leave room for (256-thread blocks: blocks per CU = this value).  Final kernel:
 // 2 is 2 % slower, 5 is 0.9 % and 6 is 4.8 % slower, 4 is 0.2-0.5 % faster than 3 except for -a cu -endo (0.4 % slower: it
 // stays at 3); -a u -endo spills inside its per-point loop at 4 (17 scratch instructions per table point), so it takes 3 as well
@@ -454,5 +466,18 @@ __device__ __forceinline__ void pub_check(const add_args& a, cand_queues& q, boo
 #include "add_walk.inc"
 #undef ECL_WALK_KERNEL
 #undef ECL_WALK_PUB
+#undef ECL_WALK_P2SH
+#undef ECL_WALK_WAVES
+// Insert instantiation: k_add_pub_ins, the x-only walk with pub_insert in place of pub_check (no rings, no records, no template: the baby
+// table of `bsgs` is built without the endomorphism).  It still counts the keys it inserts.
+#define ECL_WALK_KERNEL k_add_pub_ins
+#define ECL_WALK_PUB
+#define ECL_WALK_INSERT
+#define ECL_WALK_P2SH false
+#define ECL_WALK_WAVES ECL_PUB_WAVES
+#include "add_walk.inc"
+#undef ECL_WALK_KERNEL
+#undef ECL_WALK_PUB
+#undef ECL_WALK_INSERT
 #undef ECL_WALK_P2SH
 #undef ECL_WALK_WAVES

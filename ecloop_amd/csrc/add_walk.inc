@@ -4,7 +4,8 @@
 // With ECL_WALK_ETH defined as well the kernel is k_add_eth<ENDO>: the Ethereum address alone (ECL_WALK_WAVES an expression of ENDO).
 // With ECL_WALK_TR defined the kernel is k_add_tr (no template): the Taproot emit kernel, tr_emit in place of check_point, no rings.
 // With ECL_WALK_PUB defined the kernel is k_add_pub<ENDO>: public keys by x - no y of a walked point, pub_check in place of check_point.
-#if defined(ECL_WALK_TR)
+// With ECL_WALK_INSERT defined beside ECL_WALK_PUB the kernel is k_add_pub_ins (no template): pub_insert in place of pub_check, no rings.
+#if defined(ECL_WALK_TR) || defined(ECL_WALK_INSERT)
 #elif defined(ECL_WALK_ETH) || defined(ECL_WALK_PUB)
 template <bool ENDO>
 #else
@@ -16,7 +17,7 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
 #else
   constexpr bool ETH = false;
 #endif
-#ifdef ECL_WALK_TR
+#if defined(ECL_WALK_TR) || defined(ECL_WALK_INSERT)
   cand_queues q;  // (the key count alone)
   q.keys = 0;
 #else
@@ -116,6 +117,8 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
           keys_count(q, live);
 #if defined(ECL_WALK_TR)
           tr_emit(a, live, false, px, py, off);
+#elif defined(ECL_WALK_INSERT)
+          pub_insert(a, live, px);
 #elif defined(ECL_WALK_PUB)
           pub_check<ENDO>(a, q, live, px, off);
 #else
@@ -138,7 +141,8 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
     fe_normalize_weak(Yn);
     X = Xn, Y = Yn;
   }
-#if defined(ECL_WALK_PUB)
+#if defined(ECL_WALK_INSERT)
+#elif defined(ECL_WALK_PUB)
   cand1_flush<5u, true>(a, q);
 #elif !defined(ECL_WALK_TR)
   cand_flush<P2SH>(a, q);

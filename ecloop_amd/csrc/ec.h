@@ -150,6 +150,19 @@ FE_FN int jac_to_affine(fe& x, fe& y, const jac& p) {
   return 1;
 }
 
+// E + O for two finite affine points given as canonical words {x[8], y[8]}, by the complete formulas (jac_madd: E = O doubles, E = -O is the
+// point at infinity): the origin shift of an ECL_ORIGIN walk (k_origin_add; host build: csrc/tools/bsgs_host.cpp).  Returns 1 and the sum's
+// canonical words in out, or 0 for the point at infinity - out is then left as it was: that is no point to walk from.
+FE_FN int ec_add_origin(u32 out[16], const u32 e[16], const u32 o[16]) {
+  jac acc;
+  acc.X = fe_from_words(e), acc.Y = fe_from_words(e + 8), acc.Z = fe_one(), acc.inf = 0;
+  acc = jac_madd(acc, fe_from_words(o), fe_from_words(o + 8));
+  fe x, y;
+  if (!jac_to_affine(x, y, acc)) return 0;
+  fe_to_words(out, x), fe_to_words(out + 8, y);
+  return 1;
+}
+
 // k*G, MSB-first double-and-add (the reference's ec_jacobi_mulrdc(&G1, k), lib/ecc.c:821-853, by value)
 __host__ __device__ __noinline__ inline int ec_mul_g_affine(fe& x, fe& y, const u32 k[8]) {
   const u32 gxw[8] = FE_GX_W, gyw[8] = FE_GY_W;

@@ -30,6 +30,7 @@
 // ------------------------------------------------------------------------------------------------ context
 
 #define ECL_COUNTER_WORDS 8u  /* d_counter: see ecl_hip_open */
+#define ECL_AUX_WORDS (34u * 16u)  /* d_aux: 34 points; one word more behind them: k_origin_add's infinity flag (its host copy: pin_counter[ECL_COUNTER_WORDS]) */
 
 struct ecl_hip {
   int dev = 0;
@@ -84,6 +85,9 @@ struct ecl_hip {
   u256 walk_next;  // scalar (mod n) the resident centres are positioned for
   u32 jump_host[16];
   u32 aux_B = 0, aux_T = 0;  // geometry the jump and the ladder in d_aux / jump_host were computed for
+  // ECL_ORIGIN: the origin point of the call in hand (canonical words x[8], y[8]; set by ecl_hip_add_range) and the one the resident
+  // walk was positioned with: a call continues the walk only if they are equal
+  u32 origin_w[16] = {}, walk_origin[16] = {};
   LA_CONTEXT_MEMBERS
   // timing
   double kernel_ms = 0, setup_ms = 0, mul_ms = 0;
@@ -142,10 +146,15 @@ const char* ecl_hip_last_error(const ecl_hip* h) { return h ? h->err.c_str() : "
 
 int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   const u32 types = ECL_ADDR33 | ECL_ADDR65 | ECL_P2SH;
-  if (!out || ord_offs > 255 || !(flags & (types | ECL_ETH | ECL_TR | ECL_PUB)) || (flags & ~(types | ECL_ETH | ECL_TR | ECL_PUB | ECL_ENDO))) return ECL_E_ARG;
+  if (!out || ord_offs > 255 || !(flags & (types | ECL_ETH | ECL_TR | ECL_PUB)) ||
+      (flags & ~(types | ECL_ETH | ECL_TR | ECL_PUB | ECL_ENDO | ECL_ORIGIN | ECL_INSERT)))
+    return ECL_E_ARG;
+  // the two walks of `bsgs`: each valid only as ECL_PUB | ECL_ORIGIN / ECL_PUB | ECL_INSERT (no endomorphism, no other type, not both)
+  if ((flags & ECL_ORIGIN) && flags != (ECL_PUB | ECL_ORIGIN)) return ECL_E_ARG;
+  if ((flags & ECL_INSERT) && flags != (ECL_PUB | ECL_INSERT)) return ECL_E_ARG;
   if ((flags & ECL_ETH) && (flags & types)) return ECL_E_ARG;  // eth is searched alone
   if ((flags & ECL_TR) && flags != ECL_TR) return ECL_E_ARG;   // Taproot is searched alone and without the endomorphism
-  if ((flags & ECL_PUB) && (flags & ~(ECL_PUB | ECL_ENDO))) return ECL_E_ARG;  // public keys are searched alone
+  if ((flags & ECL_PUB) && (flags & ~(ECL_PUB | ECL_ENDO | ECL_ORIGIN | ECL_INSERT))) return ECL_E_ARG;  // public keys are searched alone
   int n = ecl_hip_device_count();
   if (device < 0 || device >= n) return ECL_E_NODEV;
   ecl_hip* h = new ecl_hip();
@@ -157,18 +166,19 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   HIPCHK(h, hipEventCreate(&h->ev1));
   HIPCHK(h, hipEventCreate(&h->ev_s0));
   HIPCHK(h, hipEventCreate(&h->ev_s1));
-  HIPCHK(h, hipMalloc(&h->d_aux, 34 * 16 * sizeof(u32)));
+  HIPCHK(h, hipMalloc(&h->d_aux, (ECL_AUX_WORDS + 1) * sizeof(u32)));
   HIPCHK(h, hipMalloc(&h->d_auxk, 34 * 8 * sizeof(u32)));
   // [0] records appended, [1] records confirmed by the list, [2] [3] input flags of mul_batch_raw, [4] [5] the u64 count of keys hashed
   // (Taproot: of points emitted), [6] [7] Taproot: the u64 count of slab entries that reached k_tr_check's probe step
   HIPCHK(h, hipMalloc(&h->d_counter, ECL_COUNTER_WORDS * sizeof(u32)));
-  HIPCHK(h, hipHostMalloc((void**)&h->pin_counter, ECL_COUNTER_WORDS * sizeof(u32), hipHostMallocDefault));
+  HIPCHK(h, hipHostMalloc((void**)&h->pin_counter, (ECL_COUNTER_WORDS + 1) * sizeof(u32), hipHostMallocDefault));
+  h->pin_counter[ECL_COUNTER_WORDS] = 0;
   // the self-test checks the CODE (known answers, walk kernel against the double-and-add kernel): once per process
   // for every (device, kernel selection) is enough - eight handles for eight shards of one scan do not repeat it
   static std::mutex mu;
   static std::set<u32> passed;
   const char* skip = getenv("ECL_HIP_SKIP_SELFTEST");
-  const u32 key = (u32)device * 512u + flags;  // flags < 512
+  const u32 key = (u32)device * 2048u + flags;  // flags < 2048
   {
     std::lock_guard<std::mutex> lk(mu);
     if ((skip && skip[0] == '1') || passed.count(key)) return ECL_OK;
@@ -410,6 +420,7 @@ typedef void (*add_kernel_t)(const add_args);
 // every non-empty set of address types (ecl_hip_open refuses the empty one) x endo
 static add_kernel_t pick_add_kernel(u32 flags) {
   const bool endo = flags & ECL_ENDO;
+  if (flags & ECL_INSERT) return k_add_pub_ins;  // ECL_PUB | ECL_INSERT alone (ecl_hip_open): sets filter bits, no records
   if (flags & ECL_PUB) return endo ? k_add_pub<true> : k_add_pub<false>;  // alone (ecl_hip_open)
   if (flags & ECL_TR) return k_add_tr;  // alone, no endomorphism (ecl_hip_open): the emit kernel
   if (flags & ECL_ETH) return endo ? k_add_eth<true> : k_add_eth<false>;  // alone (ecl_hip_open)
@@ -743,6 +754,9 @@ static int add_launch(ecl_hip* h, const u256& k0, uint64_t nkeys, u32 rcap, bool
     }
   }
   bool cont = h->walk_valid && h->walk_T == T && h->walk_B == B && u256_eq(h->walk_next, k0);
+  const bool origin = h->flags & ECL_ORIGIN;
+  if (origin && memcmp(h->walk_origin, h->origin_w, sizeof h->origin_w) != 0) cont = false;  // another origin: re-position
+  h->pin_counter[ECL_COUNTER_WORDS] = 0;
   if (!cont) {
     if ((rc = ensure_gtable(h)) != ECL_OK) return rc;
     HIPCHK(h, hipEventRecord(h->ev_s0, h->stream));
@@ -781,6 +795,14 @@ static int add_launch(ecl_hip* h, const u256& k0, uint64_t nkeys, u32 rcap, bool
     words_of(c0.w, from_table ? es : c0s);
     hipLaunchKernelGGL(k_mul_window_one, dim3(1), dim3(64), 0, h->stream, c0, h->d_gtab, h->d_aux);
     HIPCHK(h, hipGetLastError());
+    if (origin) {  // the base point shifted by O; the flag comes home with the call's one wait (add_core)
+      origin_arg o;
+      memcpy(o.w, h->origin_w, sizeof o.w);
+      hipLaunchKernelGGL(k_origin_add, dim3(1), dim3(64), 0, h->stream, h->d_aux, o, h->d_aux + ECL_AUX_WORDS);
+      HIPCHK(h, hipGetLastError());
+      HIPCHK(h, hipMemcpyAsync(h->pin_counter + ECL_COUNTER_WORDS, h->d_aux + ECL_AUX_WORDS, sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+      memcpy(h->walk_origin, h->origin_w, sizeof h->walk_origin);
+    }
     if (from_table && T >= (1u << 19))
       hipLaunchKernelGGL(k_init_centres_table<8u>, dim3((T / 8u + 255) / 256), dim3(256), 0, h->stream, h->d_aux, h->d_ctab, h->d_cxy, T);
     else if (from_table)
@@ -836,12 +858,32 @@ static int add_core(ecl_hip* h, const u256& k0, uint64_t nkeys, ecl_found* out, 
     h->setup_ms += ms, h->setups += 1;
   }
   if (check_coverage(h, "add_range", nkeys, rc, nout) == ECL_E_COVERAGE) return ECL_E_COVERAGE;
+  if ((h->flags & ECL_ORIGIN) && h->pin_counter[ECL_COUNTER_WORDS]) {  // origin + base point = the point at infinity: nothing was walked from it
+    h->err = "the origin is the negative of the walk's base point";
+    h->walk_valid = false, h->last_held = h->last_total = 0;
+    return ECL_E_RANGE;
+  }
 
   // the centres now sit at the start of group nb*T + g: valid continuation only if the launch was exact
   h->walk_valid = walked == nkeys;
   if (h->walk_valid) h->walk_next = sc_add(k0, sc_mul_u64(s, walked));
   *nout = cnt;
   return rc;
+}
+
+// ECL_ORIGIN: x and y of the origin (little-endian u64 limbs) checked on the host - both below p, y^2 = x^3 + 7 - and as canonical words
+static bool origin_from_limbs(u32 w[16], const uint64_t xy[8]) {
+  static const uint64_t P_LIMBS[4] = {0xfffffffefffffc2fULL, ~0ULL, ~0ULL, ~0ULL};
+  for (int c = 0; c < 2; ++c) {
+    if (u256_cmp(u256_from(xy + 4 * c), u256_from(P_LIMBS)) >= 0) return false;
+    words_of(w + 8 * c, u256_from(xy + 4 * c));
+  }
+  const fe x = fe_from_words(w), y = fe_from_words(w + 8);
+  fe seven = fe_zero();
+  seven.n[0] = 7;
+  fe rhs = fe_add(fe_mul(fe_sqr(x), x), seven);
+  fe_normalize_weak(rhs);  // magnitude 1
+  return fe_is_zero(fe_sub(fe_sqr(y), rhs));
 }
 
 #include "abi_lookahead.h"
@@ -880,7 +922,16 @@ extern "C" int ecl_hip_add_range(ecl_hip* h, const uint64_t start[4], uint64_t n
   if (!h->d_bloom) return ECL_E_NOBLOOM;
   if (nkeys == 0) return ECL_OK;
   HIPCHK(h, hipSetDevice(h->dev));
-  return count_call(h, nkeys, la_dispatch(h, sc_reduce(u256_from(start)), nkeys, out, cap, nout));
+  const u256 k0 = sc_reduce(u256_from(start));
+  if (h->flags & ECL_ORIGIN) {  // twelve limbs: the scalar, then x and y of the origin point
+    if (!origin_from_limbs(h->origin_w, start + 4)) {
+      h->err = "the origin is not a point of the curve";
+      return ECL_E_ARG;
+    }
+  }
+  // the walks of `bsgs` never take part in the look-ahead
+  if (h->flags & (ECL_ORIGIN | ECL_INSERT)) return count_call(h, nkeys, add_core(h, k0, nkeys, out, cap, nout));
+  return count_call(h, nkeys, la_dispatch(h, k0, nkeys, out, cap, nout));
 }
 
 #include "abi_mul.h"

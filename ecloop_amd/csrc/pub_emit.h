@@ -8,6 +8,7 @@
 // 3.5 M + 1 S + hash160.  What is probed: the LEADING 20 BYTES of x as five big-endian words (the word order k_tr_check uses for an
 // output key), 160 bits like every other type; the host re-derives a hit and compares all 32.
 #pragma once
+#include "bloom.h"
 #include "fe256.h"
 
 // +-Gy - Y, magnitude 3 (which = 0: C + G_i, 1: C - G_i).  gy: the table's y (normalised), Y: magnitude 1.  `which` is wave-uniform
@@ -41,4 +42,14 @@ FE_FN void pub_words20(u32 h[5], fe x) {
   fe_to_words(w, x);
 #pragma unroll
   for (int j = 0; j < 5; ++j) h[j] = w[7 - j];
+}
+// the baby table of `bsgs` (ECL_INSERT): the 20 bit positions blf_add (bloom.h: bloom_index, lib/utils.c:290-306) gives the 160 probed bits of
+// x, before the reduction to the filter's size - what k_add_pub_ins sets and pub_check later probes.  x: magnitude <= 6.
+FE_FN void pub_insert_idx(u64 idx[20], const fe& x) {
+  u32 h[5];
+  u64 a[5];
+  pub_words20(h, x);
+  bloom_words_of(a, h);
+#pragma unroll
+  for (int p = 0; p < 20; ++p) idx[p] = bloom_index(a, p);
 }

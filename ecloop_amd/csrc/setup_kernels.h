@@ -31,6 +31,23 @@ __global__ void k_tab_to_limbs(const u32* __restrict__ words, u32* __restrict__ 
   tab[(size_t)i * ECL_TAB_STRIDE + 18] = 0, tab[(size_t)i * ECL_TAB_STRIDE + 19] = 0;
 }
 
+// ECL_ORIGIN: the walk's base point (E or C_0, which k_mul_window_one has just put at `e`) shifted by the caller's origin O, in place, by the
+// complete formulas (ec.h: ec_add_origin), so that everything after it - the lane centres, the search kernel - walks O + k G unchanged.
+// One thread.  *inf = 1 if the sum is the point at infinity (the base point is then left as it was and the host fails the call), else 0.
+struct origin_arg { u32 w[16]; };
+__global__ void __launch_bounds__(64) k_origin_add(u32* __restrict__ e, origin_arg o, u32* __restrict__ inf) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  u32 ew[16], ow[16], out[16];
+#pragma unroll
+  for (int w = 0; w < 16; ++w) ew[w] = e[w], ow[w] = o.w[w], out[w] = 0;
+  const int fin = ec_add_origin(out, ew, ow);
+  if (fin) {
+#pragma unroll
+    for (int w = 0; w < 16; ++w) e[w] = out[w];
+  }
+  *inf = fin ? 0u : 1u;
+}
+
 // lane centres C_g = C_0 + g*D from the ladder {2^j * D}: at most 32 mixed additions + one inversion per lane
 __global__ void __launch_bounds__(256) k_init_centres(const u32* __restrict__ c0, const u32* __restrict__ ladder,
                                                        uint4* __restrict__ cxy, u32 T) {

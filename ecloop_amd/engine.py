@@ -393,3 +393,124 @@ def blf_gen(hashes, n, existing=None, device=0):
         return d.get_bloom(size)
     finally:
         d.close()
+
+
+# ----------------------------------------------------------------------------------------------- bsgs: the key of a known public key
+
+
+def bsgs_plan(a, b, beta):
+    """the arithmetic of host/bsgs_plan.h in Python integers (the method is written there): h = 2^beta baby steps, s = 2h keys per giant
+    step, N = ceil((b - a + 1) / s) steps W_i = (2a + s - 1 + 2s i) G - 2Q; ranges with 2 (b + s) + 1 >= n are refused"""
+    if not (0 <= beta <= 62) or a < 1 or a > b or b >= N:
+        raise ValueError("bsgs: the range must satisfy 1 <= a <= b < n")
+    h, s = 1 << beta, 2 << beta
+    if 2 * (b + s) + 1 >= N:
+        raise ValueError("bsgs: the range reaches n / 2 (2 (b + s) + 1 >= n): a giant step could be the point at infinity")
+    return {"beta": beta, "h": h, "s": s, "steps": (b - a + s) // s, "baby_start": 1, "baby_offs": 1, "baby_keys": h,
+            "giant_start": 2 * a + s - 1, "giant_offs": beta + 2, "filter_words": max(h, 1024)}
+
+
+def bsgs_default_beta(a, b):
+    return min(30, max(10, (b - a + 1).bit_length() // 2))  # ceil((bits - 1) / 2), clamped (unmeasured: tools/bench_bsgs.py)
+
+
+def bsgs_point(pub):
+    """a public key as 66 hex digits (02 / 03) or 130 (04, checked on the curve), or an (x, y) pair -> (x, y); a bare x names two keys
+    and is refused"""
+    if isinstance(pub, (tuple, list)):
+        x, y = int(pub[0]), int(pub[1])
+    else:
+        t = pub.strip().lower()
+        if len(t) == 66 and t[:2] in ("02", "03"):
+            x = int(t[2:], 16)
+            y = pow((x ** 3 + 7) % P, (P + 1) // 4, P) if x < P else 0
+            if (y & 1) != (t[1] == "3"):
+                y = P - y
+        elif len(t) == 130 and t[:2] == "04":
+            x, y = int(t[2:66], 16), int(t[66:], 16)
+        else:
+            raise ValueError("bsgs: a public key is 66 hex digits (02.. / 03..) or 130 (04..); a bare x names two keys")
+    if not (x < P and 0 < y < P and (y * y - x ** 3 - 7) % P == 0):
+        raise ValueError("bsgs: the public key is not a point of the curve")
+    return x, y
+
+
+def bsgs_origin(q):
+    """O = -2Q"""
+    x, y = q
+    lam = 3 * x * x * pow(2 * y, P - 2, P) % P
+    x2 = (lam * lam - 2 * x) % P
+    return x2, (-(lam * (x - x2) - y)) % P
+
+
+def _words5_of_x(x):
+    return [(x >> (32 * (7 - j))) & 0xFFFFFFFF for j in range(5)]
+
+
+def bsgs_search(pub, range_s, range_e, baby_log2=None, filter_words=None, device=0, device_cls=None, cap=4096):
+    """baby-step giant-step search for the key of `pub` in [range_s, range_e] on one GPU -> (key or None, stats); stats: baby_keys,
+    giant_steps (walked), false_positives (giant steps whose window held no key), windows_rescanned.  The baby filter is built once by an
+    insert context, copied into the origin context that walks the giant steps; a record names a window, which an ordinary public-key
+    context rescans, and a key is accepted only if all of x and the parity of y of its point are the target's."""
+    Dev = device_cls or Device
+    q = bsgs_point(pub)
+    beta = bsgs_default_beta(range_s, range_e) if baby_log2 is None else int(baby_log2)
+    while True:
+        plan = bsgs_plan(range_s, range_e, beta)
+        nwords = int(filter_words) if filter_words else plan["filter_words"]
+        ins = Dev(device, a33=False, pub=True, insert=True, ord_offs=plan["baby_offs"])
+        try:
+            try:
+                ins.set_bloom(np.zeros(nwords, np.uint64))
+            except (EclError, MemoryError):
+                if baby_log2 is None and not filter_words and beta > 10:
+                    beta -= 1  # the filter does not fit: fewer baby steps
+                    continue
+                raise
+            _, total = ins.add_range(plan["baby_start"], plan["baby_keys"], cap=1)
+            if total:
+                raise EclError("bsgs: the insert walk reported records")
+            words = ins.get_bloom(nwords)
+        finally:
+            ins.close()
+        break
+    stats = {"baby_keys": plan["baby_keys"], "giant_steps": 0, "false_positives": 0, "windows_rescanned": 0}
+    h5 = _words5_of_x(q[0])
+    giant = Dev(device, a33=False, pub=True, origin=True, ord_offs=plan["giant_offs"])
+    scan = None
+    try:
+        giant.set_bloom(words)
+        origin, done = bsgs_origin(q), 0
+        while done < plan["steps"]:
+            n = min(plan["steps"] - done, 1 << 32)
+            start = plan["giant_start"] + (done << plan["giant_offs"])
+            raw, total = giant.add_range(start, n, cap=cap, origin=origin)
+            if total > len(raw):
+                raw = np.concatenate([raw, giant.fetch_found(len(raw), total - len(raw))])
+                if len(raw) != total:
+                    raise EclError("bsgs: more records in one call than the device keeps; use a larger filter")
+            stats["giant_steps"] += n
+            for off in sorted(int(r["key_offset"]) for r in raw):
+                first = range_s + (done + off) * plan["s"]
+                nk = min(plan["s"], range_e - first + 1)
+                if scan is None:
+                    scan = Dev(device, a33=False, pub=True)
+                    one = np.zeros(1024, np.uint64)
+                    blf_add_host(one, np.array([h5], np.uint32))
+                    scan.set_bloom(one)
+                    scan.set_list(np.array([h5], np.uint32))
+                    scan.set_lookahead(0)
+                recs, _ = scan.add_range(first, nk, cap=64)
+                stats["windows_rescanned"] += 1
+                for r in sorted(int(r["key_offset"]) for r in recs):
+                    key = first + r
+                    x, par, ok = scan.verify_pub([key])
+                    if ok[0] and sum(int(w) << (32 * (7 - j)) for j, w in enumerate(x[0])) == q[0] and int(par[0]) == (q[1] & 1):
+                        return key, stats
+                stats["false_positives"] += 1
+            done += n
+        return None, stats
+    finally:
+        giant.close()
+        if scan is not None:
+            scan.close()

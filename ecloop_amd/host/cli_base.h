@@ -184,6 +184,7 @@ static bool have_ssse3, have_avx2, have_avx512; /* set once in main */
    commands (plan: -rnd -mul -visible). */
 typedef struct {
   const char *filter, *outfile, *range, *window, *seed, *addr, *gpus, *count, *visible;
+  const char *pubkey, *baby, *words; /* bsgs: -k, -b, -m */
   bool quiet, endo, raw, bin, version, host_only, rnd_jobs, as_mul;
 } opts_t;
 typedef struct { const char *flag; size_t at; bool takes_value; } optdef_t;
@@ -194,6 +195,7 @@ static const optdef_t OPTDEFS[] = {
     {"-q", offsetof(opts_t, quiet), false},       {"-endo", offsetof(opts_t, endo), false}, {"-raw", offsetof(opts_t, raw), false},
     {"-bin", offsetof(opts_t, bin), false},       {"-v", offsetof(opts_t, version), false}, {"-host", offsetof(opts_t, host_only), false},
     {"-rnd", offsetof(opts_t, rnd_jobs), false},  {"-mul", offsetof(opts_t, as_mul), false},
+    {"-k", offsetof(opts_t, pubkey), true},       {"-b", offsetof(opts_t, baby), true},     {"-m", offsetof(opts_t, words), true},
 };
 static void opts_parse(opts_t *o, int argc, const char **argv) {
   memset(o, 0, sizeof *o);

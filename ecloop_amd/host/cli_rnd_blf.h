@@ -243,6 +243,7 @@ static void usage(const char *prog) { /* the reference's help text (main.c:750-7
       "  add             - search in given range with batch addition\n",
       "  mul             - search hex encoded private keys (from stdin)\n",
       "  rnd             - search random range of bits in given range\n",
+      "  bsgs            - find the private key of a known public key in given range (baby-step giant-step, one GPU)\n",
       "\nCompute options:\n",
       "  -f <file>       - filter file to search (list of hashes or bloom fitler)\n",
       "  -o <file>       - output file to write found keys (default: stdout)\n",
@@ -259,6 +260,12 @@ static void usage(const char *prog) { /* the reference's help text (main.c:750-7
       "  -endo           - use endomorphism (default: false)\n",
       "  -raw            - mul: the private key is the SHA-256 of the line (hashed on the GPU)\n",
       "  -bin            - mul: stdin carries 32-byte little-endian scalars instead of hex lines\n",
+      "\nbsgs options:\n",
+      "  -k <pubkey>     - the public key (66 hex digits 02.. / 03.., or 130 digits 04..), or a file of them, one per line\n",
+      "  -r <range>      - the range a:b that holds the key, in hex, both ends included (example: 8000:ffffff)\n",
+      "  -b <bits>       - 2^bits baby steps (default: half the bits of the range's size, 10 ... 30)\n",
+      "  -m <words>      - 64-bit words of the baby filter (default: one per baby step, 1024 at least)\n",
+      "  -o <file>, -q   - as above; a key is printed as 'pub: <compressed key> <- <private key>'\n",
       "\nOther commands:\n",
       "  blf-gen         - create bloom filter from list of hex-encoded hash160\n",
       "  blf-check       - check bloom filter for given hex-encoded hash160\n\n"};

@@ -77,7 +77,20 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
    record or a list entry holds - and has the whole key from it (all 32 bytes of x, and y for the prefix byte).  With ECL_ENDO a key gives
    three records (x, beta x, beta^2 x: endo = 0, 2, 4), which stand for six keys.  Public keys are searched alone: ECL_PUB is valid by
    itself or with ECL_ENDO; together with any of ECL_ADDR33, ECL_ADDR65, ECL_P2SH, ECL_ETH, ECL_TR (or the refused bits 8 and 32) it is
-   ECL_E_ARG. */
+   ECL_E_ARG.
+   ECL_ORIGIN and ECL_INSERT (no reference counterpart): the two walks of a baby-step giant-step search for the key of a KNOWN public key
+   (the `bsgs` command; ecloop_amd/host/bsgs_plan.h has the method).  Each is valid in exactly one combination - ECL_PUB | ECL_ORIGIN,
+   ECL_PUB | ECL_INSERT - and ECL_E_ARG with ECL_ENDO, with any other type, with each other or without ECL_PUB.  Neither takes part in
+   the look-ahead, and ecl_hip_mul_batch(_raw) on them is ECL_E_ARG.
+   ECL_PUB | ECL_ORIGIN: a public-key walk that starts from a point nobody knows the scalar of.  The `start` argument of ecl_hip_add_range
+   points to TWELVE limbs: the scalar, then the affine x and y of an origin point O (little-endian u64 limbs, both below p, y^2 = x^3 + 7:
+   checked on the host, ECL_E_ARG otherwise), and the call walks the points O + (start + j 2^ord_offs) G, j < nkeys - records, key_offset
+   and coverage as for ECL_PUB, the ECL_E_RANGE check on the scalar part as it is (so the caller keeps O + k G finite: a base point that is
+   -O makes the call ECL_E_RANGE, any other meeting of the two leaves x values of one group that are no point's - nothing else).  A call
+   continues the resident walk only if its origin is the one before's, too.
+   ECL_PUB | ECL_INSERT: a public-key walk that SETS the 20 filter bits (blf_add) of the leading 20 bytes of x of every key of the call
+   - and of no other point the walk computes - in the resident filter instead of probing them: *nout = 0, keys are counted and the
+   coverage check applies; ecl_hip_get_bloom reads the filter back. */
 #define ECL_ADDR33 1u
 #define ECL_ADDR65 2u
 #define ECL_ENDO 4u
@@ -85,6 +98,8 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
 #define ECL_ETH 64u
 #define ECL_TR 128u
 #define ECL_PUB 256u
+#define ECL_ORIGIN 512u
+#define ECL_INSERT 1024u
 
 /* return codes */
 #define ECL_OK 0
@@ -137,7 +152,8 @@ void ecl_hip_close(ecl_hip *h);
 int ecl_hip_set_bloom(ecl_hip *h, const uint64_t *bits, uint64_t nwords);
 
 /* Hash the nkeys keys  start, start+s, ..., start+(nkeys-1)*s  (s = 2^ord_offs; every encoding / endo variant
-   selected at open) and report every bloom hit.  start: 256-bit scalar, 4 little-endian u64 limbs, as `fe`.
+   selected at open) and report every bloom hit.  start: 256-bit scalar, 4 little-endian u64 limbs, as `fe` (a context opened with
+   ECL_ORIGIN: twelve limbs - the scalar, then x and y of the origin point, see the flags).
    Exactly these keys are tested - the caller reproduces the reference's job rounding (main.c:442,368).
    Consecutive calls whose `start` continues the previous range reuse the on-device walk state; small ones are answered from a
    look-ahead sweep (ecl_hip_set_lookahead) - same records either way.

@@ -22,7 +22,8 @@ What the numbers are used for:
 usage: tools/isa_mix.py [file.s] [mangled kernel name] [--json]     |     tools/isa_mix.py --all   (every instantiation: profiles/rNN_static_mix.json)
        tools/isa_mix.py --eth   (the three Ethereum kernels)
        tools/isa_mix.py --tr    (the Taproot kernels: registers, loops, the static VALU counts of the tagged hash and the window loop)
-       tools/isa_mix.py --pub   (the public-key kernels: registers, loops, the static per-key VALU count beside -a c's from the same assembly)"""
+       tools/isa_mix.py --pub   (the public-key kernels: registers, loops, the static per-key VALU count beside -a c's from the same assembly)
+       tools/isa_mix.py --bsgs  (the kernels `bsgs` adds: the insert walk beside -a x's from the same assembly, the origin set-up kernel)"""
 import json
 import os
 import re
@@ -318,6 +319,26 @@ def analyse_pub(path=ASM):
     return out
 
 
+# the kernels `bsgs` adds: the insert walk of the baby table (the giant walk runs k_add_pub<false> itself) and the one-thread origin shift
+BSGS_KERNELS = {"bsgs insert": "_Z13k_add_pub_ins8add_args", "bsgs origin": "_Z12k_origin_addPj10origin_argS_"}
+
+
+def analyse_bsgs(path=ASM):
+    """the insert walk in analyse_pub's form - registers / spills, loops, `scratch_below_top`, the static per-key VALU count (the 20 atomic
+    ORs of a key are VMEM, counted in `which_loop_vmem`) beside -a x's from the same assembly - and the registers of the origin kernel"""
+    k = BSGS_KERNELS["bsgs insert"]
+    a = analyse(path, k)
+    loops = a["loops"]
+    r = {"kernel": k, "registers": spills(path, k).get(k), "total": a["total"],
+         "loops": [{x: l[x] for x in ("header", "depth", "parent", "valu", "mad64", "vmem", "scratch", "scratch_at_calls")} for l in loops],
+         "scratch_below_top": sum(l["scratch"] for l in loops if l["depth"] >= 2),
+         "which_loop_valu": a["which_loop"]["valu"], "which_loop_vmem": a["which_loop"]["vmem"], "table_loop_valu": a["table_loop"]["valu"],
+         "prefix_loop_valu": a["prefix_loop"]["valu"], "per_key_valu": a["per_key_static"]["valu"],
+         "pub_per_key_valu": analyse(path, PUB_KERNELS["-a x"])["per_key_static"]["valu"]}
+    o = BSGS_KERNELS["bsgs origin"]
+    return {"bsgs insert": r, "bsgs origin": {"kernel": o, "registers": spills(path, o).get(o)}}
+
+
 def analyse_all(path=ASM):
     """every shipped instantiation of the two search kernels: fingerprint, registers / spills, and the scratch instructions inside the
     per-key loops (k_add: prefix-product, table and `which` loops; k_mul_check: window loop) - tests/test_profiles_fresh.py wants 0 there"""
@@ -350,6 +371,10 @@ def main():
     if "--pub" in sys.argv:
         rest = [a for a in sys.argv[1:] if not a.startswith("--")]
         print(json.dumps(analyse_pub(rest[0] if rest else ASM), indent=1))
+        return
+    if "--bsgs" in sys.argv:
+        rest = [a for a in sys.argv[1:] if not a.startswith("--")]
+        print(json.dumps(analyse_bsgs(rest[0] if rest else ASM), indent=1))
         return
     if "--all" in sys.argv:
         rest = [a for a in sys.argv[1:] if not a.startswith("--")]
