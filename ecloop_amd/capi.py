@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("ECLOOP_HIP_LIB") or os.path.join(PKG, "libecloop_hip.
 
 ADDR33, ADDR65, ENDO, P2SH, ETH, TR, PUB = 1, 2, 4, 16, 64, 128, 256
 ORIGIN, INSERT = 512, 1024  # the two walks of `bsgs`, each valid only beside PUB alone (include/ecloop_hip.h)
+HERD = 2048  # the herd of `kangaroo`, valid only beside PUB alone; ord_offs is then the number of distinguished-point bits
 E_ARG = -1
 E_RANGE = -6
 E_OVERFLOW = -4
@@ -28,7 +29,7 @@ FOUND_DTYPE = np.dtype([("key_offset", "<u8"), ("h160", "<u4", (5,)), ("endo", "
                         ("pad", "u1", (2,))])
 assert FOUND_DTYPE.itemsize == C.sizeof(Found) == 32
 
-LABELS = {1: "addr33", 0: "addr65", 2: "p2sh", 3: "eth", 4: "p2tr", 5: "pub"}  # ecl_found.compressed (the address type) -> label of the found line
+LABELS = {1: "addr33", 0: "addr65", 2: "p2sh", 3: "eth", 4: "p2tr", 5: "pub", 6: "dp"}  # ecl_found.compressed (the address type) -> label of the found line
 
 
 def label_of(compressed):
@@ -134,12 +135,14 @@ class Device:
     """One GPU context (ecl_hip handle)."""
 
     def __init__(self, device=0, a33=True, a65=False, endo=False, ord_offs=0, p2sh=False, eth=False, tr=False, pub=False, origin=False,
-                 insert=False):
+                 insert=False, herd=False):
         if pub and (a33 or a65 or p2sh or eth or tr):  # (before the library is asked)
             raise ValueError("public keys are searched alone: Device(a33=False, pub=True), with or without endo")
         if (origin or insert) and (not pub or endo or (origin and insert)):
             raise ValueError("origin and insert are the walks of bsgs: Device(a33=False, pub=True, origin=True) or (..., insert=True), no endo")
-        self.origin, self.insert = bool(origin), bool(insert)
+        if herd and (not pub or endo or origin or insert or not 0 <= ord_offs <= 32):
+            raise ValueError("herd is the walk of kangaroo: Device(a33=False, pub=True, herd=True, ord_offs=dp), dp = 0 ... 32, no endo, origin or insert")
+        self.origin, self.insert, self.herd = bool(origin), bool(insert), bool(herd)
         self.lib = load()
         self.h = C.c_void_p()
         self.a33, self.a65, self.endo, self.p2sh, self.eth, self.tr = bool(a33), bool(a65), bool(endo), bool(p2sh), bool(eth), bool(tr)
@@ -149,7 +152,7 @@ class Device:
         if tr and (a33 or a65 or p2sh or eth or endo):
             raise ValueError("Taproot is searched alone and without the endomorphism: Device(a33=False, tr=True)")
         flags = (ADDR33 if a33 else 0) | (ADDR65 if a65 else 0) | (P2SH if p2sh else 0) | (ETH if eth else 0) | (TR if tr else 0) | (PUB if pub else 0) | (ENDO if endo else 0) | \
-                (ORIGIN if origin else 0) | (INSERT if insert else 0)
+                (ORIGIN if origin else 0) | (INSERT if insert else 0) | (HERD if herd else 0)
         rc = self.lib.ecl_hip_open(C.byref(self.h), device, flags, ord_offs)
         if rc != 0:
             msg = self.lib.ecl_hip_last_error(self.h).decode() if self.h else ""
@@ -214,15 +217,22 @@ class Device:
         self._chk(self.lib.ecl_hip_plan_geometry(self.h, nkeys, C.byref(b), C.byref(t), C.byref(nb)))
         return b.value, t.value, nb.value
 
-    def add_range(self, start, nkeys, cap=4096, origin=None):
+    def add_range(self, start, nkeys, cap=4096, origin=None, herd=None):
         """-> (records as numpy structured array, total hit count). Raises on overflow unless total <= cap.
         A context opened with origin=True takes origin=(x, y), the affine origin point O: the call walks O + (start + j * stride) G.  One
-        opened with insert=True sets the keys' filter bits and reports nothing (total 0)."""
+        opened with insert=True sets the keys' filter bits and reports nothing (total 0).  One opened with herd=True takes start=None and herd=(B, Q, seed, herd_log2, jump_bits, spread_bits), Q = (x, y),
+        and nkeys is the number of jumps, a multiple of 2^herd_log2 (include/ecloop_hip.h: ECL_HERD); the records are distinguished points."""
         out = np.zeros(cap, dtype=FOUND_DTYPE)
         n = C.c_uint32()
         if self.origin != (origin is not None):
             raise ValueError("add_range(origin=(x, y)) goes with Device(origin=True), and only with it")
-        s = limbs(start) if origin is None else np.concatenate([limbs(start), limbs(origin[0]), limbs(origin[1])])
+        if self.herd != (herd is not None):
+            raise ValueError("add_range(herd=(B, Q, seed, herd_log2, jb, sb)) goes with Device(herd=True), and only with it")
+        if herd is not None:
+            B, Q, seed, herd_log2, jb, sb = herd
+            s = np.concatenate([limbs(B), limbs(Q[0]), limbs(Q[1]), np.array([seed & 0xFFFFFFFFFFFFFFFF, herd_log2, jb, sb], dtype=np.uint64)])
+        else:
+            s = limbs(start) if origin is None else np.concatenate([limbs(start), limbs(origin[0]), limbs(origin[1])])
         rc = self.lib.ecl_hip_add_range(self.h, s.ctypes.data, nkeys, out.ctypes.data, cap, C.byref(n))
         self._chk(rc, allow=(E_OVERFLOW,))
         return out[: min(n.value, cap)], n.value

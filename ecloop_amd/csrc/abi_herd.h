@@ -1,0 +1,171 @@
+// abi_herd.h - host side of ECL_PUB | ECL_HERD: the herd of `kangaroo` behind ecl_hip_add_range (herd_kernel.h has the kernels,
+// host/kangaroo_plan.h the method).  (one translation unit: included by ecloop_hip.hip)
+#pragma once
+#include "../host/kangaroo_plan.h"
+
+#define HERD_INIT_CHUNK (1u << 18)     /* kangaroos whose starts are multiplied per set-up launch */
+#define HERD_LAUNCH_STEPS_MAX 4096u    /* steps of one launch: a lone wave makes a step of 32 jumps in a fraction of a millisecond ... */
+#define HERD_LAUNCH_JUMPS_LOG2 34u     /* ... and a full chip is given at most 2^34 jumps per launch (static estimates) */
+
+struct herd_params {
+  u256 base;
+  u32 q[16];  // canonical words x[8], y[8]
+  u64 seed;
+  u32 herd_log2, jb, sb;
+};
+// the sixteen limbs of `start`, checked: ECL_E_ARG with the reason in h->err
+static int herd_parse(ecl_hip* h, const uint64_t blk[16], herd_params& p) {
+  p.base = sc_reduce(u256_from(blk));
+  if (!origin_from_limbs(p.q, blk + 4)) {
+    h->err = "the target is not a point of the curve";
+    return ECL_E_ARG;
+  }
+  p.seed = blk[12];
+  if (blk[13] < 1 || blk[13] > KG_HERD_LOG2_MAX || blk[14] < KG_JB_MIN || blk[14] > KG_JB_MAX || blk[15] < 1 || blk[15] > KG_SB_MAX) {
+    h->err = "herd block: herd_log2 1 ... 24, jump_bits 4 ... 120, spread_bits 1 ... 124";
+    return ECL_E_ARG;
+  }
+  p.herd_log2 = (u32)blk[13], p.jb = (u32)blk[14], p.sb = (u32)blk[15];
+  return ECL_OK;
+}
+
+// table and starts of a new herd, queued on h->stream and waited for; the flag word d_counter[6] (zeroed by the caller) comes home in *flags
+static int herd_build(ecl_hip* h, const herd_params& p, u32* flags) {
+  const u32 H = 1u << p.herd_log2;
+  if (h->herd_cap < H) {
+    if (h->d_herd) HIPCHK(h, hipFree(h->d_herd));
+    h->d_herd = nullptr, h->herd_cap = 0;
+    HIPCHK(h, hipMalloc(&h->d_herd, (size_t)H * 22 * sizeof(u32)));
+    h->herd_cap = H;
+  }
+  if (!h->d_herdtab) HIPCHK(h, hipMalloc(&h->d_herdtab, 32 * HERD_TAB_IN * sizeof(u32)));
+  kg_stream st = {p.seed};
+  kg_u128 s[KG_TABLE];
+  kg_table(&st, p.jb, s);
+  const u32 chunk = H < HERD_INIT_CHUNK ? H : HERD_INIT_CHUNK, nk = chunk > 32 ? chunk : 32;
+  dbuf<u32> d_k, d_pts, d_r;
+  dbuf<u8> d_ok;
+  HIPCHK(h, hipMalloc(&d_k.p, (size_t)nk * 8 * sizeof(u32)));
+  HIPCHK(h, hipMalloc(&d_pts.p, (size_t)nk * 16 * sizeof(u32)));
+  HIPCHK(h, hipMalloc(&d_r.p, (size_t)chunk * 4 * sizeof(u32)));
+  HIPCHK(h, hipMalloc(&d_ok.p, nk));
+  std::vector<u32> ks((size_t)nk * 8), rs((size_t)chunk * 4), tab(32 * HERD_TAB_IN);
+  // T_j = s_j G by the double-and-add kernel
+  for (u32 j = 0; j < 32; ++j) {
+    const uint64_t w[4] = {s[j].lo, s[j].hi, 0, 0};
+    words_of(&ks[(size_t)j * 8], u256_from(w));
+  }
+  HIPCHK(h, hipMemcpyAsync(d_k.p, ks.data(), 32 * 8 * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_mul_g, dim3(1), dim3(64), 0, h->stream, d_k.p, d_pts.p, d_ok.p, 32u);
+  HIPCHK(h, hipGetLastError());
+  std::vector<u32> tpts(32 * 16);
+  HIPCHK(h, hipMemcpyAsync(tpts.data(), d_pts.p, tpts.size() * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (u32 j = 0; j < 32; ++j) {
+    memcpy(&tab[(size_t)j * HERD_TAB_IN], &tpts[(size_t)j * 16], 64);
+    tab[(size_t)j * HERD_TAB_IN + 16] = (u32)s[j].lo, tab[(size_t)j * HERD_TAB_IN + 17] = (u32)(s[j].lo >> 32);
+    tab[(size_t)j * HERD_TAB_IN + 18] = (u32)s[j].hi, tab[(size_t)j * HERD_TAB_IN + 19] = (u32)(s[j].hi >> 32);
+  }
+  HIPCHK(h, hipMemcpyAsync(h->d_herdtab, tab.data(), tab.size() * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+  // the starts, a chunk of kangaroos at a time: (B + r_i) G and r_i G by the double-and-add kernel, then Q added to the wild ones
+  herd_q q;
+  memcpy(q.w, p.q, sizeof q.w);
+  for (u32 first = 0; first < H; first += chunk) {
+    const u32 n = H - first < chunk ? H - first : chunk;
+    for (u32 t = 0; t < n; ++t) {
+      const kg_u128 r = kg_offset(&st, p.sb);
+      const uint64_t w[4] = {r.lo, r.hi, 0, 0};
+      const u256 rv = u256_from(w);
+      words_of(&ks[(size_t)t * 8], ((first + t) & 1u) ? rv : sc_add(p.base, rv));
+      rs[(size_t)t * 4] = (u32)r.lo, rs[(size_t)t * 4 + 1] = (u32)(r.lo >> 32), rs[(size_t)t * 4 + 2] = (u32)r.hi, rs[(size_t)t * 4 + 3] = (u32)(r.hi >> 32);
+    }
+    HIPCHK(h, hipMemcpyAsync(d_k.p, ks.data(), (size_t)n * 8 * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_r.p, rs.data(), (size_t)n * 4 * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_mul_g, dim3((n + 63) / 64), dim3(64), 0, h->stream, d_k.p, d_pts.p, d_ok.p, n);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(k_herd_init, dim3((n + 63) / 64), dim3(64), 0, h->stream, d_pts.p, d_ok.p, d_r.p, q, h->d_herd, H, first, n, h->d_counter);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipStreamSynchronize(h->stream));  // the host buffers are filled again
+  }
+  HIPCHK(h, hipMemcpy(flags, h->d_counter + 6, sizeof(u32), hipMemcpyDeviceToHost));
+  return ECL_OK;
+}
+
+// ecl_hip_add_range of a herd context: nkeys jumps, nkeys / H per kangaroo
+static int herd_add_core(ecl_hip* h, const uint64_t blk[16], uint64_t nkeys, ecl_found* out, uint32_t cap, uint32_t* nout) {
+  *nout = 0;
+  herd_params p;
+  int rc;
+  if ((rc = herd_parse(h, blk, p)) != ECL_OK) return rc;
+  const u32 H = 1u << p.herd_log2;
+  if (nkeys % H) {
+    h->err = "nkeys is not a multiple of the herd";
+    return ECL_E_ARG;
+  }
+  h->last_held = h->last_total = 0, h->last_from_host = false;
+  const u32 rcap = raw_cap_of(h, cap ? cap : 1);
+  if ((rc = ensure_found(h, rcap)) != ECL_OK) return rc;
+  const u32 L = (H + HERD_M - 1) / HERD_M, grid = (L + HERD_BLOCK - 1) / HERD_BLOCK, T = grid * HERD_BLOCK;
+  const size_t need = (size_t)T * HERD_M * 2;
+  if (h->scr_elems < need) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (h->d_scr) HIPCHK(h, hipFree(h->d_scr));
+    if (h->d_scr2) HIPCHK(h, hipFree(h->d_scr2));
+    h->d_scr = nullptr, h->d_scr2 = nullptr, h->scr_elems = 0;
+    HIPCHK(h, hipMalloc(&h->d_scr, need * sizeof(uint4)));
+    HIPCHK(h, hipMalloc(&h->d_scr2, (need / 2) * sizeof(u32)));
+    h->scr_elems = need;
+  }
+  HIPCHK(h, hipMemsetAsync(h->d_counter, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
+  const bool cont = h->herd_valid && memcmp(h->herd_blk, blk, sizeof h->herd_blk) == 0;
+  if (!cont) {
+    h->herd_valid = false;
+    u32 flags = 0;
+    HIPCHK(h, hipEventRecord(h->ev_s0, h->stream));
+    if ((rc = herd_build(h, p, &flags)) != ECL_OK) return rc;
+    HIPCHK(h, hipEventRecord(h->ev_s1, h->stream));
+    if (flags & 2u) {
+      h->err = "a kangaroo's start is the point at infinity";
+      return ECL_E_RANGE;
+    }
+  }
+  herd_args a;
+  a.tab = h->d_herdtab, a.state = h->d_herd, a.scratch = h->d_scr, a.scratch2 = h->d_scr2;
+  a.found = (uint4*)h->d_found, a.counter = h->d_counter, a.jumps = (unsigned long long*)(h->d_counter + 4), a.cap = rcap;
+  a.H = H, a.L = L, a.T = T, a.dpmask = h->offs >= 32 ? ~0u : (1u << h->offs) - 1u;
+  u64 per = (1ull << HERD_LAUNCH_JUMPS_LOG2) >> p.herd_log2;
+  if (per > HERD_LAUNCH_STEPS_MAX) per = HERD_LAUNCH_STEPS_MAX;
+  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  for (u64 left = nkeys / H; left;) {
+    const u64 n = left < per ? left : per;
+    a.steps = (u32)n;
+    if (h->diag_drop) h->diag_drop = false, a.steps -= 1;  // (test hook: every kangaroo makes one jump fewer, so the count falls short)
+    hipLaunchKernelGGL(k_herd_walk, dim3(grid), dim3(HERD_BLOCK), 0, h->stream, a);
+    HIPCHK(h, hipGetLastError());
+    left -= n;
+  }
+  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+  u32 cnt = 0;
+  rc = collect_found(h, cap, rcap, out, &cnt, true);
+  if (rc != ECL_OK && rc != ECL_E_OVERFLOW) return rc;
+  float ms = 0;
+  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  h->kernel_ms += ms, h->launches += 1, h->keys += nkeys;
+  if (!cont) {
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev_s0, h->ev_s1));
+    h->setup_ms += ms, h->setups += 1;
+  }
+  if (check_coverage(h, "add_range", nkeys, rc, nout) == ECL_E_COVERAGE) {  // the herd is not where the caller thinks it is: built anew next time
+    h->herd_valid = false;
+    return ECL_E_COVERAGE;
+  }
+  if (h->pin_counter[6] & 1u) {
+    h->err = "a kangaroo's distance passed 2^128";
+    h->herd_valid = false, h->last_held = h->last_total = 0;
+    return ECL_E_RANGE;
+  }
+  h->herd_valid = true;
+  memcpy(h->herd_blk, blk, sizeof h->herd_blk);
+  *nout = cnt;
+  return rc;
+}

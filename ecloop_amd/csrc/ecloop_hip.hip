@@ -26,6 +26,7 @@
 #include "mul_kernels.h"
 #include "tr_kernels.h"
 #include "aux_kernels.h"
+#include "herd_kernel.h"
 
 // ------------------------------------------------------------------------------------------------ context
 
@@ -88,6 +89,10 @@ struct ecl_hip {
   // ECL_ORIGIN: the origin point of the call in hand (canonical words x[8], y[8]; set by ecl_hip_add_range) and the one the resident
   // walk was positioned with: a call continues the walk only if they are equal
   u32 origin_w[16] = {}, walk_origin[16] = {};
+  // ECL_HERD: the resident herd (22 words per kangaroo), its jump table, and the sixteen limbs it was built from: a call continues the
+  // herd only if its block equals them
+  u32* d_herd = nullptr; u32 herd_cap = 0; u32* d_herdtab = nullptr;
+  uint64_t herd_blk[16] = {}; bool herd_valid = false;
   LA_CONTEXT_MEMBERS
   // timing
   double kernel_ms = 0, setup_ms = 0, mul_ms = 0;
@@ -147,14 +152,16 @@ const char* ecl_hip_last_error(const ecl_hip* h) { return h ? h->err.c_str() : "
 int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   const u32 types = ECL_ADDR33 | ECL_ADDR65 | ECL_P2SH;
   if (!out || ord_offs > 255 || !(flags & (types | ECL_ETH | ECL_TR | ECL_PUB)) ||
-      (flags & ~(types | ECL_ETH | ECL_TR | ECL_PUB | ECL_ENDO | ECL_ORIGIN | ECL_INSERT)))
+      (flags & ~(types | ECL_ETH | ECL_TR | ECL_PUB | ECL_ENDO | ECL_ORIGIN | ECL_INSERT | ECL_HERD)))
     return ECL_E_ARG;
   // the two walks of `bsgs`: each valid only as ECL_PUB | ECL_ORIGIN / ECL_PUB | ECL_INSERT (no endomorphism, no other type, not both)
   if ((flags & ECL_ORIGIN) && flags != (ECL_PUB | ECL_ORIGIN)) return ECL_E_ARG;
   if ((flags & ECL_INSERT) && flags != (ECL_PUB | ECL_INSERT)) return ECL_E_ARG;
+  // the herd of `kangaroo`: valid only as ECL_PUB | ECL_HERD; ord_offs is the number of distinguished-point bits
+  if ((flags & ECL_HERD) && (flags != (ECL_PUB | ECL_HERD) || ord_offs > 32)) return ECL_E_ARG;
   if ((flags & ECL_ETH) && (flags & types)) return ECL_E_ARG;  // eth is searched alone
   if ((flags & ECL_TR) && flags != ECL_TR) return ECL_E_ARG;   // Taproot is searched alone and without the endomorphism
-  if ((flags & ECL_PUB) && (flags & ~(ECL_PUB | ECL_ENDO | ECL_ORIGIN | ECL_INSERT))) return ECL_E_ARG;  // public keys are searched alone
+  if ((flags & ECL_PUB) && (flags & ~(ECL_PUB | ECL_ENDO | ECL_ORIGIN | ECL_INSERT | ECL_HERD))) return ECL_E_ARG;  // public keys are searched alone
   int n = ecl_hip_device_count();
   if (device < 0 || device >= n) return ECL_E_NODEV;
   ecl_hip* h = new ecl_hip();
@@ -178,7 +185,7 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   static std::mutex mu;
   static std::set<u32> passed;
   const char* skip = getenv("ECL_HIP_SKIP_SELFTEST");
-  const u32 key = (u32)device * 2048u + flags;  // flags < 2048
+  const u32 key = (u32)device * 4096u + flags;  // flags < 4096
   {
     std::lock_guard<std::mutex> lk(mu);
     if ((skip && skip[0] == '1') || passed.count(key)) return ECL_OK;
@@ -200,6 +207,7 @@ void ecl_hip_close(ecl_hip* h) {
   if (h->prep_stream) (void)hipStreamSynchronize(h->prep_stream);
   (void)hipFree(h->d_tab), (void)hipFree(h->d_gtab), (void)hipFree(h->d_aux), (void)hipFree(h->d_auxk), (void)hipFree(h->d_cxy), (void)hipFree(h->d_ctab);
   (void)hipFree(h->d_scr), (void)hipFree(h->d_scr2), (void)hipFree(h->d_bloom), (void)hipFree(h->d_list), (void)hipFree(h->d_found), (void)hipFree(h->d_counter);
+  (void)hipFree(h->d_herd), (void)hipFree(h->d_herdtab);
   if (h->pin_counter) (void)hipHostFree(h->pin_counter);
   for (int i = 0; i < MUL_NBUF; ++i) {
     (void)hipFree(h->d_kbuf[i]);
@@ -886,6 +894,7 @@ static bool origin_from_limbs(u32 w[16], const uint64_t xy[8]) {
   return fe_is_zero(fe_sub(fe_sqr(y), rhs));
 }
 
+#include "abi_herd.h"
 #include "abi_lookahead.h"
 
 // fingerprint of what a filter / a list holds, computed over ALL of its words where they are resident (k_fingerprint, aux_kernels.h: a 6 GB
@@ -919,6 +928,11 @@ extern "C" int ecl_hip_add_range(ecl_hip* h, const uint64_t start[4], uint64_t n
                                  uint32_t* nout) {
   if (!h || !start || (!out && cap) || !nout || cap > ECL_CAP_MAX) return ECL_E_ARG;
   *nout = 0;
+  if (h->flags & ECL_HERD) {  // sixteen limbs, nkeys jumps, no filter (abi_herd.h)
+    if (nkeys == 0) return ECL_OK;
+    HIPCHK(h, hipSetDevice(h->dev));
+    return count_call(h, nkeys, herd_add_core(h, start, nkeys, out, cap, nout));
+  }
   if (!h->d_bloom) return ECL_E_NOBLOOM;
   if (nkeys == 0) return ECL_OK;
   HIPCHK(h, hipSetDevice(h->dev));

@@ -514,3 +514,92 @@ def bsgs_search(pub, range_s, range_e, baby_log2=None, filter_words=None, device
         giant.close()
         if scan is not None:
             scan.close()
+
+
+# ----------------------------------------------------------------------------------------------- kangaroo: the same for wide ranges
+
+
+def _clamp(v, lo, hi):
+    return lo if v < lo else hi if v > hi else v
+
+
+def kangaroo_plan(a, b, herd_log2=None, dp_bits=None, seed=0):
+    """the defaults of host/kangaroo_plan.h (kg_plan_make) in Python integers: from the range [a, b] the herd, the distinguished-point bits,
+    the jump and spread bits, the base scalar of the tame herd and the steps of a round; the refusals as ValueError"""
+    if a < 1 or a > b or b >= N:
+        raise ValueError("kangaroo: the range must satisfy 1 <= a <= b < n")
+    wbits = (b - a).bit_length()
+    if wbits > 124:
+        raise ValueError("kangaroo: the range holds more than 2^124 keys")
+    if herd_log2 is not None and not 1 <= herd_log2 <= 24:
+        raise ValueError("kangaroo: herd_log2 is 1 ... 24")
+    if dp_bits is not None and not 0 <= dp_bits <= 32:
+        raise ValueError("kangaroo: dp_bits is 0 ... 32")
+    half = wbits // 2
+    hl = herd_log2 if herd_log2 is not None else _clamp(half - 4, 1, 22)
+    dp = dp_bits if dp_bits is not None else _clamp(max(half - hl - 1, half + 2 - 26), 0, 32)
+    return {"wbits": wbits, "herd_log2": hl, "dp": dp, "jb": _clamp(half + hl - 2, 4, 120), "sb": _clamp(wbits, 1, 124),
+            "round_steps": 1 << _clamp(min(half - 1 - hl, 34 - hl), 0, 33), "base": a, "seed": seed}
+
+
+def kangaroo_give_up(plan, max_factor):
+    """the give-up limit in jumps: max_factor * 2 sqrt(W) + H 2^dp, sqrt(W) taken as 2^ceil(wbits / 2)"""
+    return (max_factor << (1 + (plan["wbits"] + 1) // 2)) + (1 << (plan["herd_log2"] + plan["dp"]))
+
+
+def kangaroo_candidates(base, d_tame, d_wild):
+    """the two keys a tame / wild pair with equal identity stands for"""
+    return (base + d_tame - d_wild) % N, (-(base + d_tame) - d_wild) % N
+
+
+def _dp_identity(r):
+    return int(r["h160"][2]) << 64 | int(r["h160"][3]) << 32 | int(r["h160"][4])
+
+
+def _dp_distance(r):
+    return int(r["key_offset"]) | int(r["h160"][1]) << 64 | int(r["h160"][0]) << 96
+
+
+def kangaroo_search(pub, a, b, herd_log2=None, dp_bits=None, seed=0, max_factor=64, device=0, device_cls=None, round_steps=None):
+    """Pollard's lambda search for the key of `pub` in [a, b] on one GPU -> (key or None, stats); stats: jumps, rounds, dps (distinguished
+    points stored), same_herd (collisions inside a herd: counted, not acted on), candidates_checked.  A round is one add_range of
+    round_steps jumps per kangaroo on an ECL_PUB | ECL_HERD context; its records, sorted by (identity, distance, herd), go into a table
+    keyed on the identity; a tame / wild pair gives two candidates, each re-derived by the double-and-add kernel and accepted only if all
+    of x and the parity of y are the target's.  None once the jumps reach the give-up limit (host/kangaroo_plan.h has the method)."""
+    Dev = device_cls or Device
+    q = bsgs_point(pub)
+    plan = kangaroo_plan(a, b, herd_log2, dp_bits, seed)
+    H, steps = 1 << plan["herd_log2"], int(round_steps or plan["round_steps"])
+    limit = kangaroo_give_up(plan, max_factor)
+    block = (plan["base"], q, seed, plan["herd_log2"], plan["jb"], plan["sb"])
+    stats = {"jumps": 0, "rounds": 0, "dps": 0, "same_herd": 0, "candidates_checked": 0}
+    store = {}
+    cap = max(4096, 2 * ((steps * H) >> plan["dp"]) + 4096)
+    d = Dev(device, a33=False, pub=True, herd=True, ord_offs=plan["dp"])
+    try:
+        while True:
+            raw, total = d.add_range(None, steps * H, cap=cap, herd=block)
+            if total > len(raw):
+                raw = np.concatenate([raw, d.fetch_found(len(raw), total - len(raw))])
+                if len(raw) != total:
+                    raise EclError("kangaroo: more records in one round than the device keeps; use more dp bits")
+            stats["jumps"] += steps * H
+            stats["rounds"] += 1
+            for ident, dist, herd in sorted((_dp_identity(r), _dp_distance(r), int(r["endo"])) for r in raw):
+                have = store.get(ident)
+                if have is None:
+                    store[ident] = (dist, herd)
+                    stats["dps"] += 1
+                elif have[1] == herd:
+                    stats["same_herd"] += 1
+                else:
+                    tame, wild = (have[0], dist) if herd else (dist, have[0])
+                    for k in kangaroo_candidates(plan["base"], tame, wild):
+                        stats["candidates_checked"] += 1
+                        x, par, ok = d.verify_pub([k])
+                        if ok[0] and sum(int(w) << (32 * (7 - j)) for j, w in enumerate(x[0])) == q[0] and int(par[0]) == (q[1] & 1):
+                            return k, stats
+            if stats["jumps"] >= limit:
+                return None, stats
+    finally:
+        d.close()

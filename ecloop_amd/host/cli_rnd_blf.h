@@ -244,6 +244,7 @@ static void usage(const char *prog) { /* the reference's help text (main.c:750-7
       "  mul             - search hex encoded private keys (from stdin)\n",
       "  rnd             - search random range of bits in given range\n",
       "  bsgs            - find the private key of a known public key in given range (baby-step giant-step, one GPU)\n",
+      "  kangaroo        - the same for ranges too wide for bsgs (Pollard's lambda method, one GPU)\n",
       "\nCompute options:\n",
       "  -f <file>       - filter file to search (list of hashes or bloom fitler)\n",
       "  -o <file>       - output file to write found keys (default: stdout)\n",
@@ -266,6 +267,12 @@ static void usage(const char *prog) { /* the reference's help text (main.c:750-7
       "  -b <bits>       - 2^bits baby steps (default: half the bits of the range's size, 10 ... 30)\n",
       "  -m <words>      - 64-bit words of the baby filter (default: one per baby step, 1024 at least)\n",
       "  -o <file>, -q   - as above; a key is printed as 'pub: <compressed key> <- <private key>'\n",
+      "\nkangaroo options:\n",
+      "  -k, -r, -o, -q  - as for bsgs; the range holds at most 2^124 keys\n",
+      "  -herd <log2>    - 2^log2 kangaroos, half of them tame (default: from the range, 1 ... 24)\n",
+      "  -dp <bits>      - a point is distinguished if the low bits of x are zero (default: from the range, 0 ... 32)\n",
+      "  -seed <s>       - seed of the jump table and the start offsets (default: 0)\n",
+      "  -max <factor>   - give up after factor * 2 sqrt(range) jumps (default: 64)\n",
       "\nOther commands:\n",
       "  blf-gen         - create bloom filter from list of hex-encoded hash160\n",
       "  blf-check       - check bloom filter for given hex-encoded hash160\n\n"};

@@ -59,6 +59,7 @@ typedef struct { u64 w[4]; } sc; /* 256-bit scalar, little-endian limbs (the ref
 #include "cli_rnd_blf.h"
 #include "cli_keys.h"
 #include "cli_bsgs.h"
+#include "cli_kangaroo.h"
 
 /* ------------------------------------------------------------------------------------------- device bring-up */
 /* Device contexts of a run: context g works on GPU (g mod shown) mod real, where `shown` is the -t count clamped to
@@ -186,6 +187,7 @@ int main(int argc, const char **argv) {
   if (!strcmp(verb, "blf-gen")) return cmd_blf_gen(o, argv[0]), 0;
   if (!strcmp(verb, "blf-check")) return cmd_blf_check(o, argc, argv), 0;
   if (!strcmp(verb, "bsgs")) return cmd_bsgs(o); /* its own contexts and filter: no -f, no -a */
+  if (!strcmp(verb, "kangaroo")) return cmd_kangaroo(o); /* its own context, no filter: no -f, no -a */
   if (!strcmp(verb, "parse")) { /* hidden: `mul`'s text front end alone (no GPU), for the parser tests */
     run.cmd = CMD_MUL, run.parse_only = true, run.ngpus = 1, run.bin = o->bin;
     report_init(&run.rep, NULL, true);

@@ -90,7 +90,32 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
    continues the resident walk only if its origin is the one before's, too.
    ECL_PUB | ECL_INSERT: a public-key walk that SETS the 20 filter bits (blf_add) of the leading 20 bytes of x of every key of the call
    - and of no other point the walk computes - in the resident filter instead of probing them: *nout = 0, keys are counted and the
-   coverage check applies; ecl_hip_get_bloom reads the filter back. */
+   coverage check applies; ecl_hip_get_bloom reads the filter back.
+   ECL_HERD (no reference counterpart): the herd of a Pollard lambda (kangaroo) search for the key of a KNOWN public key (the `kangaroo`
+   command; ecloop_amd/host/kangaroo_plan.h is the definition of the method).  Valid only as ECL_PUB | ECL_HERD: with ECL_ENDO, ECL_ORIGIN,
+   ECL_INSERT, any address type or without ECL_PUB it is ECL_E_ARG.  For such a context ord_offs of ecl_hip_open is the number of
+   distinguished-point bits dp, 0 ... 32 (more: ECL_E_ARG); no filter is needed (ecl_hip_add_range before ecl_hip_set_bloom is not
+   ECL_E_NOBLOOM); it does not take part in the look-ahead, ecl_hip_set_geometry has no effect on it and ecl_hip_mul_batch(_raw) is
+   ECL_E_ARG.  The `start` argument of ecl_hip_add_range points to SIXTEEN limbs, the herd's parameter block:
+     limbs 0..3    the base scalar B
+     limbs 4..11   the affine x and y of the target Q (both below p, y^2 = x^3 + 7: checked on the host, ECL_E_ARG otherwise)
+     limb 12       seed
+     limb 13       herd_log2, 1 ... 24: H = 2^herd_log2 kangaroos, an even index is tame, an odd one wild
+     limb 14       jump_bits jb, 4 ... 120 (32 different distances need 2^(jb + 1) >= 32)
+     limb 15       spread_bits sb, 1 ... 124   (any of the three out of its range: ECL_E_ARG)
+   and nkeys is the number of JUMPS of the call, a multiple of H (else ECL_E_ARG): every kangaroo makes nkeys / H of them.  A call whose
+   sixteen limbs equal the previous call's continues the resident herd; anything else builds the herd anew, which counts as one set-up in
+   ecl_hip_get_setup_timing.  The kernel counts the jumps it makes: a call whose count differs from nkeys returns ECL_E_COVERAGE (and
+   ecl_hip_diag_drop_round makes that happen), and the next call builds the herd anew.
+   The method: the 32 jump distances s_j are drawn from a SplitMix64 stream of seed, 128 bits from two outputs each, s_j = 1 + (v mod
+   2^(jb + 1)), a draw equal to an earlier one drawn again; table point T_j = s_j G.  The start offsets r_i = v mod 2^sb follow from the same
+   stream.  Tame i starts at (B + r_i) G, wild i at Q + r_i G (the complete addition), both with distance r_i; a start that is the point at
+   infinity is ECL_E_RANGE.  A jump: with x canonical, j = bits 32..36 of x, P <- P + T_j, d <- d + s_j; where x(P) = x(T_j) - the sum would be
+   a doubling or the point at infinity - the kangaroo takes j + 1 mod 32 for this jump, so the shared inversion never sees a zero.  After
+   the jump the point is distinguished if the low dp bits of x are zero, and is reported as one ecl_found record with compressed = 6
+   (label dp): endo = 0 tame / 1 wild, key_offset = distance bits 0..63, h160[0], h160[1] = distance bits 96..127 and 64..95, h160[2..4] =
+   the leading 12 bytes of x in the h160_t word convention.  Distances are 128-bit: one that would pass 2^128 fails the call with
+   ECL_E_RANGE.  ECL_E_OVERFLOW and ecl_hip_fetch_found as for every other context; the order of a call's records is not defined. */
 #define ECL_ADDR33 1u
 #define ECL_ADDR65 2u
 #define ECL_ENDO 4u
@@ -100,6 +125,7 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
 #define ECL_PUB 256u
 #define ECL_ORIGIN 512u
 #define ECL_INSERT 1024u
+#define ECL_HERD 2048u
 
 /* return codes */
 #define ECL_OK 0
@@ -123,7 +149,8 @@ typedef struct ecl_found {
   uint8_t endo;
   uint8_t compressed; /* the address type: 1 = addr33, 0 = addr65, 2 = P2SH-P2WPKH (only for a context opened with ECL_P2SH),
                          3 = Ethereum (ECL_ETH; h160 holds the address), 4 = Taproot (ECL_TR, label p2tr; h160 holds the leading
-                         20 bytes of the output key), 5 = public key (ECL_PUB, label pub; h160 holds the leading 20 bytes of x) */
+                         20 bytes of the output key), 5 = public key (ECL_PUB, label pub; h160 holds the leading 20 bytes of x),
+                         6 = distinguished point (ECL_HERD, label dp; the fields as the flags' comment gives them) */
   uint8_t pad[2];
 } ecl_found; /* 32 bytes */
 
@@ -153,7 +180,7 @@ int ecl_hip_set_bloom(ecl_hip *h, const uint64_t *bits, uint64_t nwords);
 
 /* Hash the nkeys keys  start, start+s, ..., start+(nkeys-1)*s  (s = 2^ord_offs; every encoding / endo variant
    selected at open) and report every bloom hit.  start: 256-bit scalar, 4 little-endian u64 limbs, as `fe` (a context opened with
-   ECL_ORIGIN: twelve limbs - the scalar, then x and y of the origin point, see the flags).
+   ECL_ORIGIN: twelve limbs - the scalar, then x and y of the origin point; with ECL_HERD: sixteen limbs and nkeys jumps; see the flags).
    Exactly these keys are tested - the caller reproduces the reference's job rounding (main.c:442,368).
    Consecutive calls whose `start` continues the previous range reuse the on-device walk state; small ones are answered from a
    look-ahead sweep (ecl_hip_set_lookahead) - same records either way.

@@ -23,7 +23,8 @@ usage: tools/isa_mix.py [file.s] [mangled kernel name] [--json]     |     tools/
        tools/isa_mix.py --eth   (the three Ethereum kernels)
        tools/isa_mix.py --tr    (the Taproot kernels: registers, loops, the static VALU counts of the tagged hash and the window loop)
        tools/isa_mix.py --pub   (the public-key kernels: registers, loops, the static per-key VALU count beside -a c's from the same assembly)
-       tools/isa_mix.py --bsgs  (the kernels `bsgs` adds: the insert walk beside -a x's from the same assembly, the origin set-up kernel)"""
+       tools/isa_mix.py --bsgs  (the kernels `bsgs` adds: the insert walk beside -a x's from the same assembly, the origin set-up kernel)
+       tools/isa_mix.py --kangaroo  (the herd walk of `kangaroo`: registers, the two per-kangaroo loops, a jump's static count and the inversion's share by M)"""
 import json
 import os
 import re
@@ -339,6 +340,38 @@ def analyse_bsgs(path=ASM):
     return {"bsgs insert": r, "bsgs origin": {"kernel": o, "registers": spills(path, o).get(o)}}
 
 
+# the kernels `kangaroo` adds: the herd walk and the set-up of its starts
+HERD_KERNELS = {"herd walk": "_Z11k_herd_walk9herd_args", "herd init": "_Z11k_herd_initPKjPKhS0_6herd_qPjjjjS4_"}
+INV_VALU_DYNAMIC = 16400  # fe_inv's executed VALU instructions (the figure ecloop_hip.hip's inv_keys_worth uses)
+
+
+def analyse_herd(path=ASM):
+    """the herd walk: registers / spills, its loop nest (step loop > pass 1, pass 2), the scratch instructions inside the two per-kangaroo
+    loops, the static VALU count of a jump (both passes' bodies, rare paths included) and, for M = 16, 32, 64 kangaroos per lane, the
+    inversion's share of a jump"""
+    k = HERD_KERNELS["herd walk"]
+    bl, _ = blocks(path, k)
+    parent, depth = loop_tree(path, k)
+    excl = {h: zero() for h in parent}
+    for b in bl:
+        if b["header"] in excl:
+            for key in KEYS:
+                excl[b["header"]][key] += b["c"][key]
+    inner = sorted((h for h in parent if depth[h] == 2), key=lambda h: excl[h]["valu"])
+    r = {"kernel": k, "registers": spills(path, k).get(k),
+         "loops": [{"header": h, "depth": depth[h], "parent": parent[h], **{x: excl[h][x] for x in ("valu", "mad64", "vmem", "lds", "scratch")}}
+                   for h in sorted(parent, key=lambda h: (depth[h], h))]}
+    if len(inner) >= 2:
+        p1, p2 = excl[inner[0]], excl[inner[-1]]
+        jump = p1["valu"] + p2["valu"]
+        r.update({"pass1_valu": p1["valu"], "pass2_valu": p2["valu"], "jump_valu": jump, "scratch_in_passes": p1["scratch"] + p2["scratch"],
+                  "lds_in_passes": p1["lds"] + p2["lds"], "vmem_in_passes": p1["vmem"] + p2["vmem"],
+                  "per_jump_with_inversion": {m: round(jump + INV_VALU_DYNAMIC / m) for m in (16, 32, 64)},
+                  "inversion_share": {m: round(INV_VALU_DYNAMIC / m / (jump + INV_VALU_DYNAMIC / m), 3) for m in (16, 32, 64)}})
+    o = HERD_KERNELS["herd init"]
+    return {"herd walk": r, "herd init": {"kernel": o, "registers": spills(path, o).get(o)}}
+
+
 def analyse_all(path=ASM):
     """every shipped instantiation of the two search kernels: fingerprint, registers / spills, and the scratch instructions inside the
     per-key loops (k_add: prefix-product, table and `which` loops; k_mul_check: window loop) - tests/test_profiles_fresh.py wants 0 there"""
@@ -375,6 +408,10 @@ def main():
     if "--bsgs" in sys.argv:
         rest = [a for a in sys.argv[1:] if not a.startswith("--")]
         print(json.dumps(analyse_bsgs(rest[0] if rest else ASM), indent=1))
+        return
+    if "--kangaroo" in sys.argv:
+        rest = [a for a in sys.argv[1:] if not a.startswith("--")]
+        print(json.dumps(analyse_herd(rest[0] if rest else ASM), indent=1))
         return
     if "--all" in sys.argv:
         rest = [a for a in sys.argv[1:] if not a.startswith("--")]
