@@ -12,7 +12,9 @@ LIB_PATH = os.environ.get("ECLOOP_HIP_LIB") or os.path.join(PKG, "libecloop_hip.
 ADDR33, ADDR65, ENDO, P2SH, ETH, TR, PUB = 1, 2, 4, 16, 64, 128, 256
 ORIGIN, INSERT = 512, 1024  # the two walks of `bsgs`, each valid only beside PUB alone (include/ecloop_hip.h)
 HERD = 2048  # the herd of `kangaroo`, valid only beside PUB alone; ord_offs is then the number of distinguished-point bits
+PREFIX = 4096  # the prefix filter in place of the bloom: beside ADDR33 / ADDR65 or ETH, with or without ENDO (include/ecloop_hip.h)
 E_ARG = -1
+E_NOBLOOM = -5
 E_RANGE = -6
 E_OVERFLOW = -4
 E_COVERAGE = -8  # the device did not hash every key of the call (include/ecloop_hip.h, section 1)
@@ -135,7 +137,10 @@ class Device:
     """One GPU context (ecl_hip handle)."""
 
     def __init__(self, device=0, a33=True, a65=False, endo=False, ord_offs=0, p2sh=False, eth=False, tr=False, pub=False, origin=False,
-                 insert=False, herd=False):
+                 insert=False, herd=False, prefix=False):
+        if prefix and (p2sh or tr or pub or origin or insert or herd or not (a33 or a65 or eth)):
+            raise ValueError("the prefix filter goes with a33 / a65 or with eth: Device(prefix=True), Device(a33=False, eth=True, prefix=True)")
+        self.prefix = bool(prefix)
         if pub and (a33 or a65 or p2sh or eth or tr):  # (before the library is asked)
             raise ValueError("public keys are searched alone: Device(a33=False, pub=True), with or without endo")
         if (origin or insert) and (not pub or endo or (origin and insert)):
@@ -152,7 +157,7 @@ class Device:
         if tr and (a33 or a65 or p2sh or eth or endo):
             raise ValueError("Taproot is searched alone and without the endomorphism: Device(a33=False, tr=True)")
         flags = (ADDR33 if a33 else 0) | (ADDR65 if a65 else 0) | (P2SH if p2sh else 0) | (ETH if eth else 0) | (TR if tr else 0) | (PUB if pub else 0) | (ENDO if endo else 0) | \
-                (ORIGIN if origin else 0) | (INSERT if insert else 0) | (HERD if herd else 0)
+                (ORIGIN if origin else 0) | (INSERT if insert else 0) | (HERD if herd else 0) | (PREFIX if prefix else 0)
         rc = self.lib.ecl_hip_open(C.byref(self.h), device, flags, ord_offs)
         if rc != 0:
             msg = self.lib.ecl_hip_last_error(self.h).decode() if self.h else ""
@@ -176,6 +181,14 @@ class Device:
     def set_bloom(self, words):
         w = np.ascontiguousarray(words, dtype=np.uint64)
         self._chk(self.lib.ecl_hip_set_bloom(self.h, w.ctypes.data, len(w)))
+
+    def set_prefixes(self, ranges):
+        """the range table of a Device(prefix=True): (n, 10) uint32, lo[5] then hi[5] per range, most significant word first, sorted by
+        lo and disjoint (engine.prefix_ranges plans one from patterns)"""
+        R = np.ascontiguousarray(ranges, dtype=np.uint32)
+        if not self.prefix or R.ndim != 2 or R.shape[1] != 10:
+            raise ValueError("set_prefixes takes an (n, 10) uint32 table on a Device(prefix=True)")
+        self._chk(self.lib.ecl_hip_set_bloom(self.h, R.ctypes.data, 5 * len(R)))
 
     def set_list(self, hashes):
         """sorted unique (n x 5) uint32 hash list for the on-device exact confirm; None / empty removes it"""

@@ -84,7 +84,7 @@ extern "C" int ecl_hip_diag_hash160(ecl_hip* h, const uint64_t (*x)[4], const ui
 }
 
 extern "C" int ecl_hip_bloom_insert(ecl_hip* h, const uint32_t (*h160)[5], uint64_t n) {
-  if (!h || (!h160 && n)) return ECL_E_ARG;
+  if (!h || (!h160 && n) || (h->flags & ECL_PREFIX)) return ECL_E_ARG;
   if (!h->d_bloom) return ECL_E_NOBLOOM;
   if (n == 0) return ECL_OK;
   la_leave(h), h->la_key_valid = false;  // the resident filter is no longer the one that was uploaded: no shared look-ahead on it
@@ -104,7 +104,7 @@ extern "C" int ecl_hip_bloom_insert(ecl_hip* h, const uint32_t (*h160)[5], uint6
 }
 
 extern "C" int ecl_hip_bloom_insert_count(ecl_hip* h, const uint32_t (*h160)[5], uint64_t n, uint64_t* added) {
-  if (!h || (!h160 && n) || !added) return ECL_E_ARG;
+  if (!h || (!h160 && n) || !added || (h->flags & ECL_PREFIX)) return ECL_E_ARG;
   *added = 0;
   if (!h->d_bloom) return ECL_E_NOBLOOM;
   if (n == 0) return ECL_OK;
@@ -139,7 +139,7 @@ extern "C" int ecl_hip_bloom_insert_count(ecl_hip* h, const uint32_t (*h160)[5],
 }
 
 extern "C" int ecl_hip_get_bloom(ecl_hip* h, uint64_t* bits, uint64_t nwords) {
-  if (!h || !bits) return ECL_E_ARG;
+  if (!h || !bits || (h->flags & ECL_PREFIX)) return ECL_E_ARG;
   if (!h->d_bloom) return ECL_E_NOBLOOM;
   if (nwords != h->bloom_words) return ECL_E_ARG;
   HIPCHK(h, hipSetDevice(h->dev));
@@ -157,8 +157,11 @@ extern "C" int ecl_hip_diag_bloom(ecl_hip* h, const uint32_t (*h160)[5], uint8_t
   HIPCHK(h, hipMalloc(&dh.p, (size_t)n * 20));
   HIPCHK(h, hipMalloc(&dhit.p, n));
   HIPCHK(h, hipMemcpy(dh.p, h160, (size_t)n * 20, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_diag_bloom, dim3((n + 63) / 64), dim3(64), 0, h->stream, bloom_make(h->d_bloom, h->bloom_words),
-                     dh.p, dhit.p, n);
+  if (h->flags & ECL_PREFIX)  // the device's two-stage prefix test on the given values
+    hipLaunchKernelGGL(k_diag_prefix, dim3((n + 63) / 64), dim3(64), 0, h->stream, prefix_of(h), dh.p, dhit.p, n);
+  else
+    hipLaunchKernelGGL(k_diag_bloom, dim3((n + 63) / 64), dim3(64), 0, h->stream, bloom_make(h->d_bloom, h->bloom_words),
+                       dh.p, dhit.p, n);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(hit, dhit.p, n, hipMemcpyDeviceToHost));
@@ -238,6 +241,7 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   const bool saveAuto = h->B_auto;
   u64* save_bloom = h->d_bloom;
   const u64 save_words = h->bloom_words, save_list_n = h->list_n;
+  const u32 save_prefix_n = h->prefix_n;
   u32* save_list = h->d_list;
   h->d_list = nullptr, h->list_n = 0;
   // ECL_ORIGIN: the same walk from the origin O = 0xdc2a04 G (its x, y from (1)), against the double-and-add kernel's (start + j s + 0xdc2a04) G;
@@ -253,7 +257,14 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   const u32 cap = insert ? 0 : N * per_key * ((h->flags & ECL_ENDO) ? ((h->flags & ECL_PUB) ? 3 : 6) : 1);  // (a public key and its negative share x: three images)
   std::vector<ecl_found> recs(cap);
   u32 n = 0;
-  rc = ecl_hip_set_bloom(h, ones.data(), ones.size());
+  // ECL_PREFIX: the one range [0, 2^160 - 1] stands for the all-ones filter (ten 32-bit words in five 64-bit ones)
+  if (h->flags & ECL_PREFIX) {
+    ones.assign(5, 0ull);
+    ones[2] = ~0ull << 32, ones[3] = ones[4] = ~0ull;
+    rc = ecl_hip_set_bloom(h, ones.data(), 5);
+  } else {
+    rc = ecl_hip_set_bloom(h, ones.data(), ones.size());
+  }
   if (rc == ECL_OK) rc = ecl_hip_add_range(h, start, N, cap ? recs.data() : nullptr, cap, &n);
   if (rc == ECL_OK && insert) rc = ecl_hip_get_bloom(h, got_bits.data(), got_bits.size());
   std::vector<uint64_t> ks((size_t)N * 4), xs((size_t)N * 4), ys((size_t)N * 4);
@@ -282,7 +293,7 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
       for (u32 j = 0; j < 5; ++j) rpub[(size_t)i * 5 + j] = (uint32_t)(xs[(size_t)i * 4 + (7 - j) / 2] >> (32 * ((7 - j) & 1)));
   // restore the caller's state whatever happened
   if (h->d_bloom) (void)hipFree(h->d_bloom);
-  h->d_bloom = save_bloom, h->bloom_words = save_words;
+  h->d_bloom = save_bloom, h->bloom_words = save_words, h->prefix_n = save_prefix_n;
   h->d_list = save_list, h->list_n = save_list_n;
   h->B = saveB, h->Tmax = saveT, h->B_auto = saveAuto;
   if (h->d_tab) (void)hipFree(h->d_tab);

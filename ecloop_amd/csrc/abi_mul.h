@@ -335,7 +335,7 @@ extern "C" int ecl_hip_reserve_mul(ecl_hip* h, uint32_t n, uint32_t cap) {
 extern "C" int ecl_hip_mul_batch(ecl_hip* h, const uint64_t (*scalars)[4], uint32_t n, ecl_found* out, uint32_t cap,
                                  uint32_t* nout) {
   if (!h || (!scalars && n) || (!out && cap) || !nout || cap > ECL_CAP_MAX) return ECL_E_ARG;
-  if (h->flags & (ECL_ORIGIN | ECL_INSERT | ECL_HERD)) return ECL_E_ARG;  // the walks of `bsgs` have no `mul`
+  if (h->flags & (ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX)) return ECL_E_ARG;  // the walks of `bsgs` and prefix contexts have no `mul`
   *nout = 0;
   if (!h->d_bloom) return ECL_E_NOBLOOM;
   if (n == 0) return ECL_OK;
@@ -417,7 +417,7 @@ extern "C" int ecl_hip_mul_batch(ecl_hip* h, const uint64_t (*scalars)[4], uint3
 extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t text_bytes, const uint64_t* lines, uint32_t n, ecl_found* out,
                                      uint32_t cap, uint32_t* nout) {
   if (!h || (!text && text_bytes) || (!lines && n) || (!out && cap) || !nout || n > MUL_RAW_MAX || text_bytes > 0xFFFFFFF0u || cap > ECL_CAP_MAX) return ECL_E_ARG;
-  if (h->flags & (ECL_ORIGIN | ECL_INSERT | ECL_HERD)) return ECL_E_ARG;
+  if (h->flags & (ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX)) return ECL_E_ARG;
   *nout = 0;
   if (!h->d_bloom) return ECL_E_NOBLOOM;
   if (n == 0) return ECL_OK;

@@ -24,6 +24,7 @@
 #include "hash160.h"
 #include "keccak.h"
 #include "pub_emit.h"
+#include "prefix.h"
 
 struct ecl_found_dev {
   u64 key_offset;
@@ -37,7 +38,10 @@ struct add_args {
   uint4* __restrict__ cxy;      // lane centres as canonical words, planes {x.lo, x.hi, y.lo, y.hi} x T
   uint4* __restrict__ scratch;  // prefix products (9x29 limbs 0..7), [(k*2 + half) * T + lane]
   u32* __restrict__ scratch2;   // prefix products (limb 8), [k * T + lane]
-  bloom_t bloom;
+  union {
+    bloom_t bloom;
+    prefix_t prefix;  // the prefix kernels (k_add_pfx, k_add_pfx_eth): bitmap, range table, n, bucket shift in the same 24 bytes
+  };
   union {
     ecl_found_dev* found;
     u32* slab;  // the Taproot emit kernels (no filter, no records): where the points and tweaks go, TR_SLAB_WORDS words per key (tr_emit)
@@ -214,9 +218,23 @@ __device__ __forceinline__ void cand_flush(const add_args& a, cand_queues& q) { 
 // be reached by ALL lanes of the wave together: lanes whose key is outside the range come along with live = false.
 // (Deferring the stage-1 test by one hash - loads in flight under the next hash160 - was measured: no gain, the
 // other waves of the SIMD already cover the probe latency.)
-template <bool P2SH>
+// ---- the prefix kernels' filter (prefix.h): stage 1 is one bitmap load; its survivors wait in ring A alone and take the exact test 64 at
+// a time (one ring is enough: there is no middle stage to thin them out, the exact test either pushes the record or drops it).  The type
+// field keeps two bits (ETH is type 3).
+__device__ __forceinline__ void prefix_finish(const add_args& a, cand_queue& qa) {
+  bool valid;
+  const cand_rec r = cand_take(qa, valid);
+  if (valid && prefix_exact(a.prefix, r.h)) found_push(a, r.off, r.h, r.tag & 0xff, (r.tag >> 8) & 3);
+}
+__device__ __forceinline__ void prefix_flush(const add_args& a, cand_queues& q) { prefix_finish(a, q.a); }  // A holds < 64
+template <bool P2SH, bool PREFIX = false>
 __device__ __forceinline__ void filter_check(const add_args& a, cand_queues* q, bool live, u64 off, const u32 h[5], u32 endo,
                                              u32 compressed) {
+  if (PREFIX) {
+    const bool in = live && prefix_stage1(a.prefix, h);
+    if (cand_append(q->a, in, off, h, endo | (compressed << 8))) prefix_finish(a, q->a);
+    return;
+  }
   const bool pass = live && bloom_stage1(a.bloom, h);
   if (!q) {
     if (pass && bloom_stage2(a.bloom, h)) found_push(a, off, h, endo, compressed);
@@ -232,7 +250,7 @@ __device__ __forceinline__ void filter_check(const add_args& a, cand_queues* q, 
 // ETH (no reference counterpart, searched alone: A33 = A65 = P2SH = false): the Ethereum address of the point, Keccak-256 over x || y
 // (keccak.h), type 3; x and y are normalised and the endomorphism images formed as for addr65.
 // x: magnitude <= 4, y: magnitude <= 3.
-template <bool A33, bool A65, bool P2SH, bool ENDO, bool ETH = false>
+template <bool A33, bool A65, bool P2SH, bool ENDO, bool ETH = false, bool PREFIX = false>
 __device__ __forceinline__ void check_point(const add_args& a, cand_queues* q, bool live, fe x, fe y, u64 off) {
   u32 xw[3][8], yw[2][8], par = 0;
   if (ENDO) {
@@ -266,7 +284,7 @@ __device__ __forceinline__ void check_point(const add_args& a, cand_queues* q, b
     for (int i = 0; i < 8; ++i) xs[i] = ENDO ? (e < 2 ? xw[0][i] : (e < 4 ? xw[1][i] : xw[2][i])) : xw[0][i];
     if (A33 || P2SH) {
       hash160_33(h, xs, (par ^ (u32)e) & 1u);  // parity(-y) = !parity(y): p is odd, y != 0
-      if (A33) filter_check<P2SH>(a, q, live, off, h, e, 1);
+      if (A33) filter_check<P2SH, PREFIX>(a, q, live, off, h, e, 1);
       if (P2SH) {
         u32 hs[5];
         hash160_p2sh(hs, h);
@@ -278,7 +296,7 @@ __device__ __forceinline__ void check_point(const add_args& a, cand_queues* q, b
 #pragma unroll
       for (int i = 0; i < 8; ++i) ys[i] = (ENDO && (e & 1)) ? yw[1][i] : yw[0][i];
       hash160_65(h, xs, ys);
-      filter_check<P2SH>(a, q, live, off, h, e, 0);
+      filter_check<P2SH, PREFIX>(a, q, live, off, h, e, 0);
     }
     if (ETH) {
       u32 ys[8];
@@ -300,7 +318,7 @@ __device__ __forceinline__ void check_point(const add_args& a, cand_queues* q, b
         for (int i = 0; i < 8; ++i) ys[i] = yw[0][i];
       }
       eth_address(h, xs, ys);
-      filter_check<true>(a, q, live, off, h, e, 3);
+      filter_check<true, PREFIX>(a, q, live, off, h, e, 3);
     }
   }
 }
@@ -479,5 +497,25 @@ __device__ __forceinline__ void pub_insert(const add_args& a, bool live, const f
 #undef ECL_WALK_KERNEL
 #undef ECL_WALK_PUB
 #undef ECL_WALK_INSERT
+#undef ECL_WALK_P2SH
+#undef ECL_WALK_WAVES
+// Prefix instantiations (-p, ECL_PREFIX): k_add_pfx<A33, A65, ENDO> and k_add_pfx_eth<ENDO>, the walk and the hashes of k_add / k_add_eth
+// with the prefix filter (prefix.h) in place of the bloom and one ring in place of two; at the waves per SIMD of the kernel they mirror.
+#define ECL_WALK_KERNEL k_add_pfx
+#define ECL_WALK_PREFIX
+#define ECL_WALK_P2SH false
+#define ECL_WALK_WAVES ((A65 && ENDO) ? 3 : ECL_ADD_WAVES)
+#include "add_walk.inc"
+#undef ECL_WALK_KERNEL
+#undef ECL_WALK_P2SH
+#undef ECL_WALK_WAVES
+#define ECL_WALK_KERNEL k_add_pfx_eth
+#define ECL_WALK_ETH
+#define ECL_WALK_P2SH false
+#define ECL_WALK_WAVES ECL_ETH_WAVES
+#include "add_walk.inc"
+#undef ECL_WALK_KERNEL
+#undef ECL_WALK_ETH
+#undef ECL_WALK_PREFIX
 #undef ECL_WALK_P2SH
 #undef ECL_WALK_WAVES

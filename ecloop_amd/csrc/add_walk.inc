@@ -4,6 +4,8 @@
 // With ECL_WALK_ETH defined as well the kernel is k_add_eth<ENDO>: the Ethereum address alone (ECL_WALK_WAVES an expression of ENDO).
 // With ECL_WALK_TR defined the kernel is k_add_tr (no template): the Taproot emit kernel, tr_emit in place of check_point, no rings.
 // With ECL_WALK_PUB defined the kernel is k_add_pub<ENDO>: public keys by x - no y of a walked point, pub_check in place of check_point.
+// With ECL_WALK_PREFIX defined (alone or beside ECL_WALK_ETH) the kernel is k_add_pfx<A33, A65, ENDO> / k_add_pfx_eth<ENDO>: the prefix
+// filter (prefix.h) in place of the bloom, one candidate ring.
 // With ECL_WALK_INSERT defined beside ECL_WALK_PUB the kernel is k_add_pub_ins (no template): pub_insert in place of pub_check, no rings.
 #if defined(ECL_WALK_TR) || defined(ECL_WALK_INSERT)
 #elif defined(ECL_WALK_ETH) || defined(ECL_WALK_PUB)
@@ -22,10 +24,17 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
   q.keys = 0;
 #else
   constexpr bool P2SH = ECL_WALK_P2SH || ETH;  // (for the rings: the record's type field keeps two bits)
+#if defined(ECL_WALK_PREFIX)
+  __shared__ u32 q_mem[ECL_ADD_BLOCK / 64][1][8 * ECL_Q_SLOTS];  // one candidate ring per wave
+  cand_queues q;
+  q.a.mem = q_mem[threadIdx.x >> 6][0], q.a.head = 0, q.a.count = 0;
+  q.b.mem = nullptr, q.b.head = 0, q.b.count = 0;
+#else
   __shared__ u32 q_mem[ECL_ADD_BLOCK / 64][2][8 * ECL_Q_SLOTS];  // two candidate rings per wave
   cand_queues q;
   q.a.mem = q_mem[threadIdx.x >> 6][0], q.a.head = 0, q.a.count = 0;
   q.b.mem = q_mem[threadIdx.x >> 6][1], q.b.head = 0, q.b.count = 0;
+#endif
   q.keys = 0;
 #endif
   const u32 g = blockIdx.x * (u32)ECL_ADD_BLOCK + threadIdx.x;
@@ -121,6 +130,8 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
           pub_insert(a, live, px);
 #elif defined(ECL_WALK_PUB)
           pub_check<ENDO>(a, q, live, px, off);
+#elif defined(ECL_WALK_PREFIX)
+          check_point<A33, A65, false, ENDO, ETH, true>(a, &q, live, px, py, off);
 #else
           check_point<A33, A65, ECL_WALK_P2SH, ENDO, ETH>(a, &q, live, px, py, off);
 #endif
@@ -144,6 +155,8 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
 #if defined(ECL_WALK_INSERT)
 #elif defined(ECL_WALK_PUB)
   cand1_flush<5u, true>(a, q);
+#elif defined(ECL_WALK_PREFIX)
+  prefix_flush(a, q);
 #elif !defined(ECL_WALK_TR)
   cand_flush<P2SH>(a, q);
 #endif

@@ -71,6 +71,15 @@ __global__ void k_diag_bloom(bloom_t b, const u32* h160, u8* hit, u32 n) {
   for (int w = 0; w < 5; ++w) h[w] = h160[(size_t)i * 5 + w];
   hit[i] = bloom_has(b, h) ? 1 : 0;
 }
+// the same for a prefix context: the two stages of the prefix filter (prefix.h) on given values
+__global__ void k_diag_prefix(prefix_t p, const u32* h160, u8* hit, u32 n) {
+  u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u32 h[5];
+#pragma unroll
+  for (int w = 0; w < 5; ++w) h[w] = h160[(size_t)i * 5 + w];
+  hit[i] = prefix_has(p, h) ? 1 : 0;
+}
 
 // bloom_mod alone, for any filter size (no bit array needed): pins the reciprocal modulo of both width classes
 __global__ void k_diag_bloom_mod(bloom_t b, const u64* x, u64* r, u32 n) {

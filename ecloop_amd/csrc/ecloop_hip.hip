@@ -51,6 +51,7 @@ struct ecl_hip {
   bool ctab_valid = false;
   uint4* d_scr = nullptr; u32* d_scr2 = nullptr; size_t scr_elems = 0;  // prefix-product chains
   u64* d_bloom = nullptr; u64 bloom_words = 0;
+  u32 prefix_n = 0;  // ECL_PREFIX: d_bloom holds the stage-1 bitmap (PREFIX_BITMAP_WORDS64 words) and behind it the table of prefix_n ranges
   // `mul`: scalars travel in pieces through MUL_NBUF device buffers (and as many pinned staging buffers for pageable callers), the copy
   // engine running up to MUL_NBUF - 1 pieces ahead of the kernel
   u32* d_kbuf[MUL_NBUF] = {}; u32* pin_k[MUL_NBUF] = {}; u32 kbuf_cap = 0, pin_cap = 0;
@@ -152,8 +153,10 @@ const char* ecl_hip_last_error(const ecl_hip* h) { return h ? h->err.c_str() : "
 int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   const u32 types = ECL_ADDR33 | ECL_ADDR65 | ECL_P2SH;
   if (!out || ord_offs > 255 || !(flags & (types | ECL_ETH | ECL_TR | ECL_PUB)) ||
-      (flags & ~(types | ECL_ETH | ECL_TR | ECL_PUB | ECL_ENDO | ECL_ORIGIN | ECL_INSERT | ECL_HERD)))
+      (flags & ~(types | ECL_ETH | ECL_TR | ECL_PUB | ECL_ENDO | ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX)))
     return ECL_E_ARG;
+  // the prefix filter: beside addr33 / addr65 or beside eth, with or without the endomorphism
+  if ((flags & ECL_PREFIX) && (flags & ~(ECL_PREFIX | ECL_ADDR33 | ECL_ADDR65 | ECL_ETH | ECL_ENDO))) return ECL_E_ARG;
   // the two walks of `bsgs`: each valid only as ECL_PUB | ECL_ORIGIN / ECL_PUB | ECL_INSERT (no endomorphism, no other type, not both)
   if ((flags & ECL_ORIGIN) && flags != (ECL_PUB | ECL_ORIGIN)) return ECL_E_ARG;
   if ((flags & ECL_INSERT) && flags != (ECL_PUB | ECL_INSERT)) return ECL_E_ARG;
@@ -185,7 +188,7 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   static std::mutex mu;
   static std::set<u32> passed;
   const char* skip = getenv("ECL_HIP_SKIP_SELFTEST");
-  const u32 key = (u32)device * 4096u + flags;  // flags < 4096
+  const u32 key = (u32)device * 8192u + flags;  // flags < 8192
   {
     std::lock_guard<std::mutex> lk(mu);
     if ((skip && skip[0] == '1') || passed.count(key)) return ECL_OK;
@@ -232,8 +235,39 @@ void ecl_hip_close(ecl_hip* h) {
   delete h;
 }
 
+}  // extern "C"
+// ECL_PREFIX: the filter words are the range table (ten 32-bit words per range); the stage-1 bitmap is built here and goes to the device
+// in front of it, in one allocation
+#define PREFIX_BITMAP_WORDS64 ((((u64)1 << PREFIX_BUCKET_BITS) / 64u))
+static prefix_t prefix_of(const ecl_hip* h) {
+  prefix_t p;
+  p.bitmap = (const u32*)h->d_bloom, p.table = (const u32*)(h->d_bloom + PREFIX_BITMAP_WORDS64);
+  p.n = h->prefix_n, p.shift = 32u - PREFIX_BUCKET_BITS;
+  return p;
+}
+static int prefix_set_table(ecl_hip* h, const u32* table, uint64_t nwords) {
+  if (nwords % 5 != 0 || !prefix_table_ok(table, nwords / 5)) {
+    h->err = "ecl_hip_set_bloom: a prefix table is 1 ... 65536 ranges lo[5], hi[5] with lo <= hi, sorted and disjoint";
+    return ECL_E_ARG;
+  }
+  const u32 n = (u32)(nwords / 5);
+  HIPCHK(h, hipSetDevice(h->dev));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (h->d_bloom) HIPCHK(h, hipFree(h->d_bloom));
+  h->d_bloom = nullptr, h->bloom_words = 0, h->prefix_n = 0;
+  std::vector<u64> img(PREFIX_BITMAP_WORDS64 + nwords);
+  prefix_build_bitmap((u32*)img.data(), table, n, 32u - PREFIX_BUCKET_BITS);
+  memcpy(img.data() + PREFIX_BITMAP_WORDS64, table, (size_t)nwords * sizeof(u64));
+  HIPCHK(h, hipMalloc(&h->d_bloom, img.size() * sizeof(u64)));
+  HIPCHK(h, hipMemcpyAsync(h->d_bloom, img.data(), img.size() * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->bloom_words = img.size(), h->prefix_n = n;
+  return ECL_OK;
+}
+extern "C" {
 int ecl_hip_set_bloom(ecl_hip* h, const uint64_t* bits, uint64_t nwords) {
   if (!h || !bits || nwords == 0 || nwords >= (1ull << 58)) return ECL_E_ARG;
+  if (h->flags & ECL_PREFIX) return prefix_set_table(h, (const u32*)bits, nwords);
   HIPCHK(h, hipSetDevice(h->dev));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   la_leave(h), h->la_key_valid = false;
@@ -265,7 +299,7 @@ void ecl_hip_free_host(void* p) {
 }
 
 int ecl_hip_set_list(ecl_hip* h, const uint32_t (*h160)[5], uint64_t n) {
-  if (!h || (n && !h160)) return ECL_E_ARG;
+  if (!h || (n && !h160) || (h->flags & ECL_PREFIX)) return ECL_E_ARG;
   for (uint64_t i = 1; i < n; ++i) {  // strictly increasing in compare_160 order (addr.c:18-26)
     int c = 0;
     for (int k = 0; k < 5 && c == 0; ++k) c = h160[i - 1][k] < h160[i][k] ? -1 : (h160[i - 1][k] > h160[i][k] ? 1 : 0);
@@ -428,6 +462,14 @@ typedef void (*add_kernel_t)(const add_args);
 // every non-empty set of address types (ecl_hip_open refuses the empty one) x endo
 static add_kernel_t pick_add_kernel(u32 flags) {
   const bool endo = flags & ECL_ENDO;
+  if (flags & ECL_PREFIX) {  // beside addr33 / addr65 or eth (ecl_hip_open): the prefix filter in place of the bloom
+    if (flags & ECL_ETH) return endo ? k_add_pfx_eth<true> : k_add_pfx_eth<false>;
+    switch (flags & (ECL_ADDR33 | ECL_ADDR65)) {
+    case ECL_ADDR33: return endo ? k_add_pfx<true, false, true> : k_add_pfx<true, false, false>;
+    case ECL_ADDR65: return endo ? k_add_pfx<false, true, true> : k_add_pfx<false, true, false>;
+    default: return endo ? k_add_pfx<true, true, true> : k_add_pfx<true, true, false>;
+    }
+  }
   if (flags & ECL_INSERT) return k_add_pub_ins;  // ECL_PUB | ECL_INSERT alone (ecl_hip_open): sets filter bits, no records
   if (flags & ECL_PUB) return endo ? k_add_pub<true> : k_add_pub<false>;  // alone (ecl_hip_open)
   if (flags & ECL_TR) return k_add_tr;  // alone, no endomorphism (ecl_hip_open): the emit kernel
@@ -829,6 +871,7 @@ static int add_launch(ecl_hip* h, const u256& k0, uint64_t nkeys, u32 rcap, bool
   memcpy(a.jump, h->jump_host, sizeof a.jump);
   a.cxy = h->d_cxy, a.scratch = h->d_scr, a.scratch2 = h->d_scr2;
   a.bloom = bloom_make(h->d_bloom, h->bloom_words);
+  if (h->flags & ECL_PREFIX) a.prefix = prefix_of(h);
   a.found = h->d_found, a.counter = h->d_counter, a.cap = rcap, a.keys = (unsigned long long*)(h->d_counter + 4);
   if (slab) a.slab = slab, a.epoch = epoch;
   a.B = B, a.T = T, a.nb = nb, a.nkeys = nkeys;
@@ -943,8 +986,8 @@ extern "C" int ecl_hip_add_range(ecl_hip* h, const uint64_t start[4], uint64_t n
       return ECL_E_ARG;
     }
   }
-  // the walks of `bsgs` never take part in the look-ahead
-  if (h->flags & (ECL_ORIGIN | ECL_INSERT)) return count_call(h, nkeys, add_core(h, k0, nkeys, out, cap, nout));
+  // the walks of `bsgs` and prefix contexts never take part in the look-ahead
+  if (h->flags & (ECL_ORIGIN | ECL_INSERT | ECL_PREFIX)) return count_call(h, nkeys, add_core(h, k0, nkeys, out, cap, nout));
   return count_call(h, nkeys, la_dispatch(h, k0, nkeys, out, cap, nout));
 }
 

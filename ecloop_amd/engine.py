@@ -216,26 +216,27 @@ def max_over_ranks(seconds, dist=None):
 
 
 class FoundRecord:
-    __slots__ = ("label", "h160", "pk", "prefix")
+    __slots__ = ("label", "h160", "pk", "prefix", "address")
 
     def __init__(self, label, h160, pk):
         self.label, self.h160, self.pk = label, h160, pk
+        self.address = ""  # a record of prefix_search: the address text, appended to its lines
         self.prefix = ""  # a verified pub record: "02" / "03", the first byte of the compressed key its line prints
 
     def line(self):
         """outfile format of ctx_write_found (main.c:193-195)"""
-        return "%s\t%s\t%064x" % (self.label, self.prefix + "".join("%08x" % int(w) for w in self.h160), self.pk)
+        return "%s\t%s\t%064x" % (self.label, self.prefix + "".join("%08x" % int(w) for w in self.h160), self.pk) + ("\t" + self.address if self.address else "")
 
     def stdout_line(self):
         """stdout format (main.c:187-189)"""
-        return "%s: %s <- %064x" % (self.label, self.prefix + "".join("%08x" % int(w) for w in self.h160), self.pk)
+        return "%s: %s <- %064x" % (self.label, self.prefix + "".join("%08x" % int(w) for w in self.h160), self.pk) + (" " + self.address if self.address else "")
 
 
 class KeySearch:
     """ctx_t + cmd_add / cmd_mul for one GPU."""
 
     def __init__(self, flt, device=0, a33=True, a65=False, endo=False, ord_offs=0, verify=True, launch_keys=1 << 32,
-                 half_group=0, max_lanes=0, device_cls=None, p2sh=False, eth=False, tr=False, pub=False):
+                 half_group=0, max_lanes=0, device_cls=None, p2sh=False, eth=False, tr=False, pub=False, prefix=False):
         if pub:
             a33 = False  # public keys are searched alone (with or without the endomorphism)
         elif tr:
@@ -258,10 +259,15 @@ class KeySearch:
             kw["tr"] = True
         if pub:
             kw["pub"] = True
+        if prefix:  # flt: a PrefixFilter - the range table stands where the bloom words stand (prefix_search)
+            kw["prefix"] = True
         self.dev = (device_cls or Device)(device, a33=a33, a65=a65, endo=endo, ord_offs=ord_offs, **kw)
         if half_group or max_lanes:
             self.dev.set_geometry(half_group, max_lanes)
-        self.dev.set_bloom(flt.words)
+        if prefix:
+            self.dev.set_prefixes(flt.table)
+        else:
+            self.dev.set_bloom(flt.words)
         if flt.hashes is not None:
             self.dev.set_list(flt.hashes)  # exact confirm on the device too (main.c:212-216); the host check stays
         self.launch_keys = launch_keys
@@ -378,6 +384,221 @@ class KeySearch:
             self.found.extend(new)
             self.k_checked += len(ks)
         return self.found
+
+
+# ----------------------------------------------------------------------------------------------- prefix search (-p)
+# The mirror of ecloop_amd/host/prefix_plan.h (the method is described there): patterns -> inclusive ranges over the 160-bit value, merged,
+# with the patterns each range serves; and the address text of a hit.
+
+B58_ALPHABET = "123456789ABCDEFGHJKLMNPQRSTUVWXYZabcdefghijkmnopqrstuvwxyz"
+BECH32_ALPHABET = "qpzry9x8gf2tvdw0s3jn54khce6mua7l"
+PREFIX_MAX_FRACTION_LOG2 = -16  # patterns that together cover more of the 160-bit space are refused
+PREFIX_MAX_RANGES = 1 << 16
+
+
+class PrefixError(ValueError):
+    """a refused pattern; the text names the pattern and the reason"""
+
+
+def _prefix_form(s):
+    if s[:2] in ("0x", "0X"):
+        return "hex"
+    if s[:4] in ("bc1q", "BC1Q"):
+        return "bech32"
+    if s[:1] == "1":
+        return "b58"
+    return None
+
+
+def _pattern_ranges(s, a33, a65, eth):
+    def fail(reason):
+        raise PrefixError("pattern '%s': %s" % (s, reason))
+
+    def bits_range(v, bits):
+        lo = v << (160 - bits)
+        return [(lo, lo + (1 << (160 - bits)) - 1)]
+
+    if not s or len(s) > 44:
+        fail("no address can start with it (empty or too long)")
+    form = _prefix_form(s)
+    if form is None:
+        if s[0] == "3":
+            fail("P2SH patterns (3...) are not supported yet")
+        if s[:4] in ("bc1p", "BC1P"):
+            fail("Taproot patterns (bc1p...) are not supported yet")
+        if all(c in "0123456789abcdefABCDEF" for c in s):
+            fail("bare hex patterns are not supported yet (an Ethereum pattern starts with 0x)")
+        fail("no address can start with it (patterns start with 1, bc1q or 0x)")
+    if form == "hex":
+        if not eth:
+            fail("a 0x pattern needs -a e")
+        d = s[2:]
+        if not 1 <= len(d) <= 40:
+            fail("no address can start with it (1 ... 40 hex digits after 0x)")
+        if any(c not in "0123456789abcdefABCDEF" for c in d):
+            fail("a character that is no hex digit")
+        return bits_range(int(d, 16), 4 * len(d))
+    if form == "bech32":
+        if eth or not a33 or a65:
+            fail("a bc1q pattern needs -a c (P2WPKH is the compressed key's hash alone)")
+        d = s[4:]
+        if not 1 <= len(d) <= 32:
+            fail("no address can start with it (1 ... 32 characters after bc1q)")
+        upper = s[0] == "B"
+        if any(c.islower() if upper else c.isupper() for c in d):
+            fail("mixed case (bech32 is lower case, or all upper case)")
+        v = 0
+        for c in d.lower():
+            if c not in BECH32_ALPHABET:
+                fail("a character outside the bech32 alphabet (it has no 1, b, i, o)")
+            v = v * 32 + BECH32_ALPHABET.index(c)
+        return bits_range(v, 5 * len(d))
+    if eth or not (a33 or a65):
+        fail("a 1... pattern needs -a c, u or cu")
+    if any(c not in B58_ALPHABET for c in s):
+        fail("a character outside the base58 alphabet (it has no 0, O, I, l)")
+    k = len(s) - len(s.lstrip("1"))
+    z, m = k - 1, len(s) - k
+    if z > 20:
+        fail("no address can start with it (more leading 1s than a hash has zero bytes)")
+    if m == 0:
+        return [(0, 0)] if z == 20 else bits_range(0, 8 * z)
+    if m > 33:
+        fail("no address can start with it (too long)")
+    v = 0
+    for c in s[k:]:
+        v = v * 58 + B58_ALPHABET.index(c)
+    L = 24 - z
+    bmin, bmax = 1 << (8 * (L - 1)), (1 << (8 * L)) - 1
+    out = []
+    lo, hi1 = v, v + 1
+    for _ in range(m, 34):
+        if lo > bmax:
+            break
+        a, b = lo, hi1 - 1
+        if b >= bmin:
+            out.append((max(a, bmin) >> 32, min(b, bmax) >> 32))
+        lo, hi1 = lo * 58, hi1 * 58
+    if not out:
+        fail("no address can start with it (no hash gives these leading digits)")
+    return out
+
+
+prefix_pattern_ranges = _pattern_ranges  # one pattern -> its (lo, hi) ranges before merging and before the 2^-16 bound (the tests' view)
+
+
+def _words5(v):
+    return [(v >> (32 * (4 - i))) & 0xFFFFFFFF for i in range(5)]
+
+
+def prefix_ranges(patterns, a33=True, a65=False, eth=False):
+    """-> (table, serves): the (n, 10) uint32 range table of Device.set_prefixes - lo[5], hi[5], most significant word first, sorted,
+    disjoint - and per range the ascending list of the indices of the patterns it serves.  Raises PrefixError for a refused pattern."""
+    patterns = list(patterns)
+    if not patterns:
+        raise PrefixError("no patterns given")
+    items = sorted((lo, i, hi) for i, p in enumerate(patterns) for lo, hi in _pattern_ranges(p, a33, a65, eth))
+    merged = []
+    for lo, i, hi in items:
+        if merged and lo <= merged[-1][1] + 1:
+            merged[-1][1] = max(merged[-1][1], hi)
+            merged[-1][2].add(i)
+        else:
+            merged.append([lo, hi, {i}])
+    if sum(hi - lo + 1 for lo, hi, _ in merged) > 1 << (160 + PREFIX_MAX_FRACTION_LOG2):
+        raise PrefixError("the patterns ('%s'%s) cover more than 2^-16 of all addresses: one launch would report more records than the device keeps; lengthen the pattern"
+                          % (patterns[0], ", ..." if len(patterns) > 1 else ""))
+    if len(merged) > PREFIX_MAX_RANGES:
+        raise PrefixError("the patterns need more than 65536 ranges")
+    table = np.array([_words5(lo) + _words5(hi) for lo, hi, _ in merged], dtype=np.uint32).reshape(-1, 10)
+    return table, [sorted(s) for _, _, s in merged]
+
+
+def _h160_bytes(h160):
+    return b"".join(int(w).to_bytes(4, "big") for w in h160)
+
+
+def address_b58(h160):
+    """base58check(00 || hash160): the P2PKH address"""
+    import hashlib
+    raw = b"\0" + _h160_bytes(h160)
+    raw += hashlib.sha256(hashlib.sha256(raw).digest()).digest()[:4]
+    v, s = int.from_bytes(raw, "big"), ""
+    while v:
+        v, r = divmod(v, 58)
+        s = B58_ALPHABET[r] + s
+    return "1" * (len(raw) - len(raw.lstrip(b"\0"))) + s
+
+
+def address_bech32(h160):
+    """BIP173: hrp bc, witness version 0, the 20-byte program (P2WPKH)"""
+    v = int.from_bytes(_h160_bytes(h160), "big")
+    data = [0] + [(v >> (5 * (31 - i))) & 31 for i in range(32)]
+    chk = 1
+    for x in [3, 3, 0, 2, 3] + data + [0] * 6:
+        b = chk >> 25
+        chk = (chk & 0x1FFFFFF) << 5 ^ x
+        for j, g in enumerate((0x3B6A57B2, 0x26508E6D, 0x1EA119FA, 0x3D4233DD, 0x2A1462B3)):
+            if (b >> j) & 1:
+                chk ^= g
+    chk ^= 1
+    return "bc1" + "".join(BECH32_ALPHABET[d] for d in data + [(chk >> (5 * (5 - i))) & 31 for i in range(6)])
+
+
+def address_eth(h160):
+    return "0x" + _h160_bytes(h160).hex()
+
+
+def prefix_match(patterns, h160, label):
+    """the address text of a record in the form of the first pattern, in list order, that it starts with; None if there is none (a range's
+    end value whose checksum does not fit).  label: the record's (addr33, addr65, eth)"""
+    for p in patterns:
+        form = _prefix_form(p)
+        if form == "hex" and label == "eth":
+            a = address_eth(h160)
+            if a.startswith(p.lower()):
+                return a
+        elif form == "bech32" and label == "addr33":
+            a = address_bech32(h160)
+            a = a.upper() if p[0] == "B" else a
+            if a.startswith(p):
+                return a
+        elif form == "b58" and label in ("addr33", "addr65"):
+            a = address_b58(h160)
+            if a.startswith(p):
+                return a
+    return None
+
+
+class PrefixFilter:
+    """what KeySearch takes in place of a Filter for a prefix search: the range table; every record the device reports counts"""
+
+    def __init__(self, table):
+        self.table, self.words, self.hashes = table, None, None
+
+    def confirm(self, h160):
+        return True
+
+
+def prefix_search(patterns, range_s, range_e, a33=True, a65=False, eth=False, endo=False, device=0, device_cls=None, verify=True, **kw):
+    """`add -p` for one GPU: the keys of [range_s, range_e) (cmd_add's job arithmetic) whose address starts with one of the patterns.
+    -> (records, edge): FoundRecord objects with .address set, and the number of records dropped because their text matched no pattern"""
+    patterns = list(patterns)
+    if eth:
+        a33 = a65 = False
+    table, _ = prefix_ranges(patterns, a33, a65, eth)
+    ks = KeySearch(PrefixFilter(table), device=device, a33=a33, a65=a65, endo=endo, eth=eth, verify=verify, device_cls=device_cls, prefix=True, **kw)
+    try:
+        out, edge = [], 0
+        for r in ks.cmd_add(range_s, range_e):
+            r.address = prefix_match(patterns, r.h160, r.label)
+            if r.address is None:
+                edge += 1
+            else:
+                out.append(r)
+        return out, edge
+    finally:
+        ks.close()
 
 
 def blf_gen(hashes, n, existing=None, device=0):

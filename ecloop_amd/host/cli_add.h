@@ -19,6 +19,7 @@ typedef struct {
   pthread_mutex_t mu;
 } scan_t;
 typedef struct { scan_t *scan; int g; } scan_worker_t;
+static void prefix_report(run_t *run, const ecl_found *hits, const sc *keys, u32 n);
 
 static sc sc_add_u64_raw(sc a, u64 v) {
   sc b = sc_u64(v), r;
@@ -91,6 +92,7 @@ static void *scan_worker(void *arg) {
     }
     u32 (*qx)[FULL_WORDS] = (run->tr || run->pub) && kept ? malloc((size_t)kept * sizeof *qx) : NULL; /* Taproot / pub: the whole keys, from the verification */
     verify_hits(run, w->g, pks, buf, kept, qx);
+    if (run->pfx) prefix_report(run, buf, pks, kept), kept = 0; /* -p: the address text decides, and goes on the found line */
     for (u32 i = 0; i < kept; ++i) report_hit(&run->rep, buf[i].compressed, qx ? qx[i] : buf[i].h160, &pks[i]);
     free(pks), free(qx);
     report_progress(&run->rep, st);

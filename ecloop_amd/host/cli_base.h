@@ -186,6 +186,7 @@ typedef struct {
   const char *filter, *outfile, *range, *window, *seed, *addr, *gpus, *count, *visible;
   const char *pubkey, *baby, *words; /* bsgs: -k, -b, -m */
   const char *herd, *dp, *maxf;      /* kangaroo: -herd, -dp, -max (and -k, -seed) */
+  const char *prefix;                /* add / rnd: -p */
   bool quiet, endo, raw, bin, version, host_only, rnd_jobs, as_mul;
 } opts_t;
 typedef struct { const char *flag; size_t at; bool takes_value; } optdef_t;
@@ -197,6 +198,7 @@ static const optdef_t OPTDEFS[] = {
     {"-bin", offsetof(opts_t, bin), false},       {"-v", offsetof(opts_t, version), false}, {"-host", offsetof(opts_t, host_only), false},
     {"-rnd", offsetof(opts_t, rnd_jobs), false},  {"-mul", offsetof(opts_t, as_mul), false},
     {"-k", offsetof(opts_t, pubkey), true},       {"-b", offsetof(opts_t, baby), true},     {"-m", offsetof(opts_t, words), true},
+    {"-p", offsetof(opts_t, prefix), true},
     {"-herd", offsetof(opts_t, herd), true},      {"-dp", offsetof(opts_t, dp), true},      {"-max", offsetof(opts_t, maxf), true},
 };
 static void opts_parse(opts_t *o, int argc, const char **argv) {

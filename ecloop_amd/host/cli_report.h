@@ -10,6 +10,8 @@ typedef struct {
   FILE *file;      /* -o (appended to), or NULL */
   bool quiet;      /* -q: nothing on stdout */
   u64 found, checked;
+  bool prefix;     /* -p: the status line shows `edge` as well */
+  u64 edge;        /* -p: records dropped because their address text matched no pattern (a range's end values) */
   u64 t_start, t_progress, t_shown; /* ms: clock start, last progress report, last status print */
   u64 paused_ms, paused_since;
   volatile bool paused; /* read by the device threads without the mutex, like the reference's flag (main.c:153) */
@@ -37,8 +39,10 @@ static void status_show_locked(report_t *r) {
   double secs = (run_ms < 1 ? 1 : run_ms) / 1000.0;
   const char *hint = r->closed ? "" : r->paused ? " ('r' \xe2\x80\x93 resume)" : " ('p' \xe2\x80\x93 pause)";
   erase_status_line();
-  fprintf(stderr, "%.2fs ~ %.2f Mkeys/s ~ %'llu / %'llu%s%c", secs, r->checked / secs / 1000000, (unsigned long long)r->found,
-          (unsigned long long)r->checked, hint, r->closed ? '\n' : '\r');
+  char edge[48] = "";
+  if (r->prefix) snprintf(edge, sizeof edge, " ~ edge: %llu", (unsigned long long)r->edge);
+  fprintf(stderr, "%.2fs ~ %.2f Mkeys/s ~ %'llu / %'llu%s%s%c", secs, r->checked / secs / 1000000, (unsigned long long)r->found,
+          (unsigned long long)r->checked, edge, hint, r->closed ? '\n' : '\r');
   fflush(stderr);
 }
 /* one found key: "addr33: <hash160> <- <key>" on stdout, "addr33\t<hash160>\t<key>" in the file; counts it.  type: the address type of
@@ -109,6 +113,7 @@ typedef struct run_t {
   bool a33, a65, p2sh, eth, tr, pub, endo, colour, bin, parse_only, seeded;
   sc range_s, range_e, stride_k;
   u32 ord_offs, ord_size;
+  pfx_plan *pfx; /* -p: the plan of the patterns (cli_prefix.h), NULL otherwise */
 } run_t;
 
 /* A failed library call ends the run.  Device threads can fail at the same time (`mul`'s two contexts of a GPU): the first one reports and

@@ -247,6 +247,10 @@ static void usage(const char *prog) { /* the reference's help text (main.c:750-7
       "  kangaroo        - the same for ranges too wide for bsgs (Pollard's lambda method, one GPU)\n",
       "\nCompute options:\n",
       "  -f <file>       - filter file to search (list of hashes or bloom fitler)\n",
+      "  -p <pattern>    - add, rnd: search addresses that START with the pattern, or with any pattern of a file (one per line), in\n",
+      "                    place of -f: 1... (base58 P2PKH; -a c, u or cu), bc1q... (bech32 P2WPKH; -a c) or 0x... (Ethereum; -a e, case is\n",
+      "                    ignored: EIP-55 case is not matched).  Patterns that cover more than 2^-16 of all addresses are refused:\n",
+      "                    lengthen them.  A found line ends with the address\n",
       "  -o <file>       - output file to write found keys (default: stdout)\n",
       "  -t <gpus>       - number of GPUs to use (default: all)\n",
       "  -a <addr_type>  - address type to search: c - addr33, u - addr65, s - p2sh (nested SegWit, 3...), e - eth (Ethereum), t - p2tr (Taproot, bc1p...), x - pubkey (public key, by its x coordinate) (default: c)\n",

@@ -51,12 +51,14 @@ typedef uint32_t u32;
 typedef uint8_t u8;
 typedef struct { u64 w[4]; } sc; /* 256-bit scalar, little-endian limbs (the reference's fe) */
 
+#include "prefix_plan.h"
 #include "cli_base.h"
 #include "cli_filter.h"
 #include "cli_report.h"
 #include "cli_add.h"
 #include "cli_mul.h"
 #include "cli_rnd_blf.h"
+#include "cli_prefix.h"
 #include "cli_keys.h"
 #include "cli_bsgs.h"
 #include "cli_kangaroo.h"
@@ -117,7 +119,7 @@ static double bring_up(run_t *run, int shown, int real) {
     if (!(keys.w[1] | keys.w[2] | keys.w[3]) && keys.w[0] < largest_call) largest_call = keys.w[0];
   }
   const u32 flags = (run->a33 ? ECL_ADDR33 : 0) | (run->a65 ? ECL_ADDR65 : 0) | (run->p2sh ? ECL_P2SH : 0) | (run->eth ? ECL_ETH : 0) |
-                    (run->tr ? ECL_TR : 0) | (run->pub ? ECL_PUB : 0) | (run->endo ? ECL_ENDO : 0);
+                    (run->tr ? ECL_TR : 0) | (run->pub ? ECL_PUB : 0) | (run->endo ? ECL_ENDO : 0) | (run->pfx ? ECL_PREFIX : 0);
   pthread_t th[MAX_GPUS];
   bringup_t job[MAX_GPUS];
   for (int g = 0; g < run->ngpus; ++g) {
@@ -183,6 +185,8 @@ int main(int argc, const char **argv) {
     exit(1);
   }
   list_skip_0x = run.eth;
+  /* -p (no reference counterpart): addresses that START with given characters, add / rnd only, no filter file (cli_prefix.h) */
+  if (o->prefix) prefix_check_options(o, verb);
   /* commands that need no search context */
   if (!strcmp(verb, "blf-gen")) return cmd_blf_gen(o, argv[0]), 0;
   if (!strcmp(verb, "blf-check")) return cmd_blf_check(o, argc, argv), 0;
@@ -205,14 +209,16 @@ int main(int argc, const char **argv) {
   run.colour = isatty(fileno(stdout));
   if (o->seed) /* a seeded run draws from rand()'s stream (the reference free()s an argv pointer here and aborts, main.c:800-805) */
     run.seeded = true, seeded_start(o->seed);
-  if (!plan_only) filter_open(&run.flt, o->filter);
+  if (!plan_only && !o->prefix) filter_open(&run.flt, o->filter);
   if (o->quiet && !o->outfile && !plan_only) { fprintf(stderr, "quiet mode chosen without output file\n"); exit(1); }
   run.a33 = o->addr ? strchr(o->addr, 'c') != NULL : true, run.a65 = o->addr && strchr(o->addr, 'u');
   if (run.eth || run.tr || run.pub) run.a33 = run.a65 = false;
   run.p2sh = o->addr && strchr(o->addr, 's'); /* no reference counterpart: P2SH-P2WPKH */
   if (!run.a33 && !run.a65 && !run.p2sh && !run.eth && !run.tr && !run.pub) run.a33 = true; /* main.c:825-827 */
   run.endo = o->endo && run.cmd != CMD_MUL, run.bin = o->bin && run.cmd == CMD_MUL;
+  if (o->prefix && !plan_only) prefix_open(&run, o->prefix); /* needs the address types: refuses a pattern form that does not fit -a */
   report_init(&run.rep, o->outfile, o->quiet);
+  run.rep.prefix = run.pfx != NULL;
   range_from_option(o->range, &run.range_s, &run.range_e);
   window_from_option(&run);
   run.stride_k = sc_pow2(run.cmd == CMD_MUL ? 0 : run.ord_offs);
@@ -257,7 +263,8 @@ int main(int argc, const char **argv) {
 
   printf("gpus: %d ~ addr33: %d ~ addr65: %d ~ endo: %d%s | filter: ", shown, run.a33, run.a65, run.endo,
          run.p2sh ? " ~ p2sh: 1" : run.eth ? " ~ eth: 1" : run.tr ? " ~ p2tr: 1" : run.pub ? " ~ pub: 1" : "");
-  if (run.flt.list) printf("list (%'llu)\n", (unsigned long long)run.flt.nlist);
+  if (run.pfx) printf("prefix (%u pattern%s, %u range%s)\n", run.pfx->npat, run.pfx->npat == 1 ? "" : "s", run.pfx->nrange, run.pfx->nrange == 1 ? "" : "s");
+  else if (run.flt.list) printf("list (%'llu)\n", (unsigned long long)run.flt.nlist);
   else printf("bloom\n");
   if (run.cmd == CMD_ADD) print_scalar_row("range_s", &run.range_s), print_scalar_row("range_e", &run.range_e);
   printf("setup: %.2fs (%d device context%s opened in parallel, %.0f MB filter uploaded, walk buffers reserved)\n", setup_s, run.ngpus,

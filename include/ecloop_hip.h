@@ -115,7 +115,20 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
    the jump the point is distinguished if the low dp bits of x are zero, and is reported as one ecl_found record with compressed = 6
    (label dp): endo = 0 tame / 1 wild, key_offset = distance bits 0..63, h160[0], h160[1] = distance bits 96..127 and 64..95, h160[2..4] =
    the leading 12 bytes of x in the h160_t word convention.  Distances are 128-bit: one that would pass 2^128 fails the call with
-   ECL_E_RANGE.  ECL_E_OVERFLOW and ecl_hip_fetch_found as for every other context; the order of a call's records is not defined. */
+   ECL_E_RANGE.  ECL_E_OVERFLOW and ecl_hip_fetch_found as for every other context; the order of a call's records is not defined.
+   ECL_PREFIX (no reference counterpart): the prefix filter, for addresses that START with given characters (the `-p` option;
+   ecloop_amd/host/prefix_plan.h turns patterns into ranges).  In place of a bloom filter the context holds a table of n inclusive ranges
+   [lo, hi] over the 160-bit value, words in the record's order (h160[0] most significant), and reports a key iff a hash of it lies inside
+   a range: no false positives, no duplicates.  Valid beside ECL_ADDR33 / ECL_ADDR65 with or without ECL_ENDO, or beside ECL_ETH with or
+   without ECL_ENDO; with ECL_P2SH, ECL_TR, ECL_PUB, ECL_ORIGIN, ECL_INSERT or ECL_HERD it is ECL_E_ARG.  On such a context
+     ecl_hip_set_bloom(h, words, nwords) takes the TABLE: nwords = 5 n, each range ten uint32 - lo[5], hi[5] - with 1 <= n <= 65536, lo <= hi,
+       the ranges sorted by lo and disjoint; nwords no multiple of 5, n out of range, lo > hi, an unsorted table or overlapping ranges are
+       ECL_E_ARG.  The library builds the stage-1 bitmap (one bit per 2^-24 of the space) itself;
+     ecl_hip_add_range is ECL_E_NOBLOOM before a table is set and otherwise behaves as always (cap, ECL_E_OVERFLOW, ecl_hip_fetch_found,
+       the coverage check); the context never takes part in the look-ahead;
+     ecl_hip_set_list, ecl_hip_bloom_insert, ecl_hip_bloom_insert_count, ecl_hip_get_bloom, ecl_hip_mul_batch and ecl_hip_mul_batch_raw are
+       ECL_E_ARG;
+     ecl_hip_diag_bloom runs the device's two-stage prefix test on the given values (hit = the value lies inside a range). */
 #define ECL_ADDR33 1u
 #define ECL_ADDR65 2u
 #define ECL_ENDO 4u
@@ -126,6 +139,7 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
 #define ECL_ORIGIN 512u
 #define ECL_INSERT 1024u
 #define ECL_HERD 2048u
+#define ECL_PREFIX 4096u
 
 /* return codes */
 #define ECL_OK 0

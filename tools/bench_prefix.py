@@ -1,0 +1,68 @@
+#!/usr/bin/env python3
+"""Prefix-search (`-p`) rate on one GPU, in one process, profiler off:
+  p   ecl_hip_add_range with ECL_ADDR33 | ECL_PREFIX over 2^32 keys, the table of one long pattern (default 1BgGZ9tcN4);
+  c   the same range with ECL_ADDR33 against a small `.blf` - the filter blf-gen sizes for 1000 entries (5392 bytes), with those many
+      random hashes in it: the unchanged addr33 kernel of this build, its stage 1 one cached probe like the prefix kernel's bitmap load;
+warm, `runs` alternating rounds, medians and their ratio reported.  Look-ahead off, 2^20 lanes per context (the half group stays automatic).
+
+usage: bench_prefix.py rates [runs = 3] [log2 keys = 32] [pattern = 1BgGZ9tcN4]"""
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from ecloop_amd import capi, engine  # noqa: E402
+
+START = 0x4000_0000_0000
+
+
+def timed_add(d, start, n):
+    ms0 = d.timing()[0]
+    t0 = time.perf_counter()
+    recs, total = d.add_range(start, n, cap=1 << 16)
+    wall = time.perf_counter() - t0
+    return (d.timing()[0] - ms0) * 1e-3, wall, total
+
+
+def rates(runs, log2, pattern):
+    n = 1 << log2
+    table, _ = engine.prefix_ranges([pattern], True, False, False)
+    words = np.zeros(engine.blf_size_words(1000), dtype=np.uint64)
+    engine.blf_add_host(words, np.random.RandomState(1).randint(0, 1 << 32, size=(1000, 5), dtype=np.int64).astype(np.uint32))
+    p = capi.Device(0, a33=True, prefix=True)
+    p.set_prefixes(table)
+    c = capi.Device(0, a33=True)
+    c.set_bloom(words)
+    c.set_lookahead(0)
+    ctx = {"p": p, "c": c}
+    for d in ctx.values():
+        d.set_geometry(0, 1 << 20)
+        timed_add(d, START - (1 << 28), 1 << 28)  # warm: tables, buffers, code objects
+    rows = {"p": [], "c": []}
+    for r in range(runs):
+        for leg in ("p", "c"):
+            rows[leg].append(timed_add(ctx[leg], START + r * n, n))
+    res = {"runs": runs, "keys": n, "pattern": pattern, "ranges": len(table), "blf_bytes": len(words) * 8,
+           "geometry": {k: ctx[k].plan_geometry(n) for k in ctx}}
+    for leg in ("p", "c"):
+        res[leg] = {"event_M_per_s": [round(n / e / 1e6, 1) for e, _, _ in rows[leg]], "wall_M_per_s": [round(n / w / 1e6, 1) for _, w, _ in rows[leg]],
+                    "event_median_M_per_s": round(statistics.median(n / e / 1e6 for e, _, _ in rows[leg]), 1),
+                    "wall_median_M_per_s": round(statistics.median(n / w / 1e6 for _, w, _ in rows[leg]), 1), "hits": [h for _, _, h in rows[leg]]}
+    res["p_over_c_event"] = round(res["p"]["event_median_M_per_s"] / res["c"]["event_median_M_per_s"], 3)
+    res["coverage_p"] = p.coverage()
+    for d in ctx.values():
+        d.close()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "rates":
+        a = sys.argv[2:] + [None] * 3
+        rates(int(a[0] or 3), int(a[1] or 32), a[2] or "1BgGZ9tcN4")
+    else:
+        sys.exit(__doc__)

@@ -250,6 +250,25 @@ def analyse_eth(path=ASM):
     return out
 
 
+# the prefix kernels (-p): the walk and the hashes of k_add / k_add_eth with the prefix filter (csrc/prefix.h) and one ring
+PREFIX_KERNELS = {"-p -a c": "_Z9k_add_pfxILb1ELb0ELb0EEv8add_args", "-p -a u": "_Z9k_add_pfxILb0ELb1ELb0EEv8add_args", "-p -a cu": "_Z9k_add_pfxILb1ELb1ELb0EEv8add_args",
+                  "-p -a c -endo": "_Z9k_add_pfxILb1ELb0ELb1EEv8add_args", "-p -a u -endo": "_Z9k_add_pfxILb0ELb1ELb1EEv8add_args",
+                  "-p -a cu -endo": "_Z9k_add_pfxILb1ELb1ELb1EEv8add_args", "-p -a e": "_Z13k_add_pfx_ethILb0EEv8add_args", "-p -a e -endo": "_Z13k_add_pfx_ethILb1EEv8add_args"}
+
+
+def analyse_prefix(path=ASM):
+    """the eight prefix kernels in analyse_all's form"""
+    sp = {**spills(path, "_Z9k_add_pfx"), **spills(path, "_Z13k_add_pfx_eth")}
+    out = {}
+    for label, k in PREFIX_KERNELS.items():
+        a = analyse(path, k)
+        out[label] = {"kernel": k, "fingerprint": a["fingerprint"], "registers": sp.get(k),
+                      "scratch_in_loops": {"which": a["which_loop"]["scratch"], "table": a["table_loop"]["scratch"], "prefix": a["prefix_loop"]["scratch"],
+                                           "launch": a["launch_loop"]["scratch"]},
+                      "per_key_static": {x: round(v, 1) for x, v in a["per_key_static"].items()}}
+    return out
+
+
 # the Taproot kernels (-a t, searched alone): stage A (the emit kernels from the walk and from `mul`'s window sums) and stage B (k_tr_check;
 # <true>: ecl_hip_diag_tr's instantiation, which writes whole output keys instead of probing)
 TR_KERNELS = {"-a t emit": "_Z8k_add_tr8add_args", "mul -a t emit": "_Z15k_mul_points_trPKjjj4wtab8add_argsPjjj",
@@ -396,6 +415,10 @@ def main():
     if "--eth" in sys.argv:
         rest = [a for a in sys.argv[1:] if not a.startswith("--")]
         print(json.dumps(analyse_eth(rest[0] if rest else ASM), indent=1))
+        return
+    if "--prefix" in sys.argv:
+        rest = [a for a in sys.argv[1:] if not a.startswith("--")]
+        print(json.dumps(analyse_prefix(rest[0] if rest else ASM), indent=1))
         return
     if "--tr" in sys.argv:
         rest = [a for a in sys.argv[1:] if not a.startswith("--")]
