@@ -138,12 +138,13 @@ class Device:
 
     def __init__(self, device=0, a33=True, a65=False, endo=False, ord_offs=0, p2sh=False, eth=False, tr=False, pub=False, origin=False,
                  insert=False, herd=False, prefix=False):
-        if prefix and (p2sh or tr or pub or origin or insert or herd or not (a33 or a65 or eth)):
+        if prefix and (p2sh or tr or pub or insert or herd or not (a33 or a65 or eth)):
             raise ValueError("the prefix filter goes with a33 / a65 or with eth: Device(prefix=True), Device(a33=False, eth=True, prefix=True)")
         self.prefix = bool(prefix)
+        self.splitkey = bool(prefix and origin)  # the split-key search: the prefix walk from an origin (twelve limbs per start and per verify entry)
         if pub and (a33 or a65 or p2sh or eth or tr):  # (before the library is asked)
             raise ValueError("public keys are searched alone: Device(a33=False, pub=True), with or without endo")
-        if (origin or insert) and (not pub or endo or (origin and insert)):
+        if (origin or insert) and not self.splitkey and (not pub or endo or (origin and insert)):
             raise ValueError("origin and insert are the walks of bsgs: Device(a33=False, pub=True, origin=True) or (..., insert=True), no endo")
         if herd and (not pub or endo or origin or insert or not 0 <= ord_offs <= 32):
             raise ValueError("herd is the walk of kangaroo: Device(a33=False, pub=True, herd=True, ord_offs=dp), dp = 0 ... 32, no endo, origin or insert")
@@ -315,9 +316,24 @@ class Device:
         self._chk(self.lib.ecl_hip_get_mul_window(self.h, C.byref(bits)))
         return bits.value
 
-    def verify(self, ks):
-        """pk_verify_hash for a batch: -> (h33, h65, ok) of the scalars' public keys (window-table path)"""
+    def _verify_entries(self, ks, origin):
+        """four limbs per scalar - or, on a Device(prefix=True, origin=True), twelve: the scalar, then x and y of its origin (one point (x, y)
+        for all, or one per scalar; None in a list stands for the point at infinity)"""
         K = limbs_array(ks)
+        if self.splitkey != (origin is not None):
+            raise ValueError("verify(origin=...) goes with Device(prefix=True, origin=True), and only with it")
+        if origin is None:
+            return K
+        pts = list(origin) if isinstance(origin, list) else [origin] * len(K)
+        if len(pts) != len(K):
+            raise ValueError("verify(origin=[...]): one origin per key")
+        O = np.array([[0] * 8 if p is None else list(limbs(p[0])) + list(limbs(p[1])) for p in pts], dtype=np.uint64).reshape(-1, 8)
+        return np.ascontiguousarray(np.concatenate([K, O], axis=1))
+
+    def verify(self, ks, origin=None):
+        """pk_verify_hash for a batch: -> (h33, h65, ok) of the scalars' public keys (window-table path); with origin= (a split-key
+        device): of the points O + k G"""
+        K = self._verify_entries(ks, origin)
         h33 = np.zeros((len(K), 5), dtype=np.uint32)
         h65 = np.zeros((len(K), 5), dtype=np.uint32)
         ok = np.zeros(len(K), dtype=np.uint8)
@@ -331,9 +347,10 @@ class Device:
         self._chk(self.lib.ecl_hip_p2sh_hash(self.h, H.ctypes.data, out.ctypes.data, len(H)))
         return out
 
-    def verify_eth(self, ks):
-        """-> (addr, ok): the Ethereum address of each scalar's public key by verify's path (window-table sum, not the walk kernel)"""
-        K = limbs_array(ks)
+    def verify_eth(self, ks, origin=None):
+        """-> (addr, ok): the Ethereum address of each scalar's public key by verify's path (window-table sum, not the walk kernel); with
+        origin= (a split-key device): of the points O + k G"""
+        K = self._verify_entries(ks, origin)
         addr = np.zeros((len(K), 5), dtype=np.uint32)
         ok = np.zeros(len(K), dtype=np.uint8)
         self._chk(self.lib.ecl_hip_verify_eth(self.h, K.ctypes.data, len(K), addr.ctypes.data, ok.ctypes.data))

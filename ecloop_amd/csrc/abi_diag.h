@@ -227,7 +227,7 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   int rc = ecl_hip_diag_mulg(h, KS, x, y, ok, 3);
   if (rc == ECL_OK) rc = ecl_hip_diag_hash160(h, x, y, h33, h65, 3);
   if (rc == ECL_OK) rc = ecl_hip_p2sh_hash(h, h33, hsh, 1);
-  if (rc == ECL_OK) rc = ecl_hip_verify_eth(h, KS, 1, heth, oketh);
+  if (rc == ECL_OK) rc = verify_eth_plain(h, KS, 1, heth, oketh);
   if (rc == ECL_OK) rc = ecl_hip_verify_tr(h, KS, 3, qtr, oktr);
   if (rc != ECL_OK) return rc;
   if (memcmp(h33, KAT33, sizeof KAT33) != 0 || memcmp(h65, KAT65, sizeof KAT65) != 0 || memcmp(hsh[0], KATP2SH, sizeof KATP2SH) != 0 ||
@@ -283,7 +283,7 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
                                               (uint32_t(*)[5])r33.data(), (uint32_t(*)[5])r65.data(), N);
   if (rc == ECL_OK && (h->flags & ECL_P2SH)) rc = ecl_hip_p2sh_hash(h, (const uint32_t(*)[5])r33.data(), (uint32_t(*)[5])rsh.data(), N);
   // an ECL_ETH context: the walk's addresses against the window-table sum's (ecl_hip_verify_eth; (3) checks that sum against the double-and-add kernel)
-  if (rc == ECL_OK && (h->flags & ECL_ETH)) rc = ecl_hip_verify_eth(h, (const uint64_t(*)[4])ks.data(), N, (uint32_t(*)[5])reth.data(), eok.data());
+  if (rc == ECL_OK && (h->flags & ECL_ETH)) rc = verify_eth_plain(h, (const uint64_t(*)[4])ks.data(), N, (uint32_t(*)[5])reth.data(), eok.data());
   // an ECL_TR context: the walk's and k_tr_check's output keys against the window-table path's (ecl_hip_verify_tr)
   if (rc == ECL_OK && (h->flags & ECL_TR)) rc = ecl_hip_verify_tr(h, (const uint64_t(*)[4])ks.data(), N, (uint32_t(*)[8])rtr.data(), eok.data());
   // an ECL_PUB context: the walk's x against the double-and-add kernel's, its leading 20 bytes as five big-endian words
@@ -347,7 +347,7 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
     }
     for (int w = 0; w < 4; ++w) vk[w] = ~0ull;                 // all digits 0x3fff (the sum is (2^256 - 1) mod n times G)
     vk[4] = 0, vk[5] = 0, vk[6] = 0, vk[7] = 1ull << 60;       // window 18 only
-    rc = ecl_hip_verify(h, (const uint64_t(*)[4])vk.data(), M, (uint32_t(*)[5])g33.data(), (uint32_t(*)[5])g65.data(), gok.data());
+    rc = verify_plain(h, (const uint64_t(*)[4])vk.data(), M, (uint32_t(*)[5])g33.data(), (uint32_t(*)[5])g65.data(), gok.data());
     if (rc == ECL_OK) rc = ecl_hip_diag_mulg(h, (const uint64_t(*)[4])vk.data(), (uint64_t(*)[4])vx.data(), (uint64_t(*)[4])vy.data(), vok.data(), M);
     if (rc == ECL_OK) rc = ecl_hip_diag_hash160(h, (const uint64_t(*)[4])vx.data(), (const uint64_t(*)[4])vy.data(),
                                                 (uint32_t(*)[5])w33.data(), (uint32_t(*)[5])w65.data(), M);

@@ -534,7 +534,50 @@ extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t t
   return count_call(h, n, rc);
 }
 
-extern "C" int ecl_hip_verify(ecl_hip* h, const uint64_t (*k)[4], uint32_t n, uint32_t (*h33)[5], uint32_t (*h65)[5], uint8_t* ok) {
+// Split-key contexts (ECL_PREFIX | ECL_ORIGIN): an entry of ecl_hip_verify / ecl_hip_verify_eth is twelve limbs - the scalar, then x and y of
+// its origin (k_verify_origin, k_verify_origin_eth).  Every origin is checked on the host like the origin of a walk (a point of the curve;
+// all eight limbs zero: the point at infinity, the sum is k G alone), ECL_E_ARG otherwise and nothing is launched.  h65 = nullptr: the eth half.
+static bool verify_takes_origins(const ecl_hip* h) { return (h->flags & (ECL_PREFIX | ECL_ORIGIN)) == (ECL_PREFIX | ECL_ORIGIN); }
+static int verify_origin(ecl_hip* h, const uint64_t* k, uint32_t n, uint32_t (*h33)[5], uint32_t (*h65)[5], uint8_t* ok) {
+  if (n > (1u << 24)) return ECL_E_ARG;  // (hits of one call; 96 bytes each on the host first)
+  std::vector<u32> ent((size_t)n * VERIFY_ORIGIN_WORDS);
+  for (u32 i = 0; i < n; ++i) {
+    const uint64_t* e = k + (size_t)i * 12;
+    u32* w = &ent[(size_t)i * VERIFY_ORIGIN_WORDS];
+    words_of(w, u256_from(e));
+    uint64_t any = 0;
+    for (int l = 4; l < 12; ++l) any |= e[l];
+    if (!any) continue;  // the origin at infinity (the words stay zero)
+    if (!origin_from_limbs(w + 8, e + 4)) {
+      h->err = "verify: an origin is not a point of the curve";
+      return ECL_E_ARG;
+    }
+  }
+  HIPCHK(h, hipSetDevice(h->dev));
+  int rc;
+  if ((rc = ensure_gtable(h)) != ECL_OK) return rc;
+  const size_t in_bytes = (size_t)n * VERIFY_ORIGIN_WORDS * sizeof(u32);
+  dbuf<u8> d;  // entries 96 B, two hashes (eth: one address) 20 B each, flag
+  HIPCHK(h, hipMalloc(&d.p, in_bytes + (size_t)n * 41));
+  u32* dk = (u32*)d.p;
+  u32* d33 = (u32*)(d.p + in_bytes);
+  u32* d65 = (u32*)(d.p + in_bytes + (size_t)n * 20);
+  u8* dok = d.p + in_bytes + (size_t)n * 40;
+  HIPCHK(h, hipMemcpyAsync(dk, ent.data(), in_bytes, hipMemcpyHostToDevice, h->stream));
+  if (h65)
+    hipLaunchKernelGGL(k_verify_origin, dim3((n + 63) / 64), dim3(64), 0, h->stream, dk, n, h->d_gtab, d33, d65, dok);
+  else
+    hipLaunchKernelGGL(k_verify_origin_eth, dim3((n + 63) / 64), dim3(64), 0, h->stream, dk, n, h->d_gtab, d33, dok);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(h33, d33, (size_t)n * 20, hipMemcpyDeviceToHost, h->stream));
+  if (h65) HIPCHK(h, hipMemcpyAsync(h65, d65, (size_t)n * 20, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));  // (ent lives until here)
+  return ECL_OK;
+}
+
+// the four-limb form of ecl_hip_verify whatever the context's flags (the self-test of a split-key context asks for it)
+static int verify_plain(ecl_hip* h, const uint64_t (*k)[4], uint32_t n, uint32_t (*h33)[5], uint32_t (*h65)[5], uint8_t* ok) {
   if (!h || !k || !h33 || !h65 || !ok || n == 0 || n > (1u << 31)) return ECL_E_ARG;
   HIPCHK(h, hipSetDevice(h->dev));
   int rc;
@@ -563,7 +606,13 @@ extern "C" int ecl_hip_verify(ecl_hip* h, const uint64_t (*k)[4], uint32_t n, ui
   return ECL_OK;
 }
 
-extern "C" int ecl_hip_verify_eth(ecl_hip* h, const uint64_t (*k)[4], uint32_t n, uint32_t (*addr)[5], uint8_t* ok) {
+extern "C" int ecl_hip_verify(ecl_hip* h, const uint64_t (*k)[4], uint32_t n, uint32_t (*h33)[5], uint32_t (*h65)[5], uint8_t* ok) {
+  if (!h || !k || !h33 || !h65 || !ok || n == 0 || n > (1u << 31)) return ECL_E_ARG;
+  if (verify_takes_origins(h)) return verify_origin(h, (const uint64_t*)k, n, h33, h65, ok);
+  return verify_plain(h, k, n, h33, h65, ok);
+}
+
+static int verify_eth_plain(ecl_hip* h, const uint64_t (*k)[4], uint32_t n, uint32_t (*addr)[5], uint8_t* ok) {
   if (!h || !k || !addr || !ok || n == 0 || n > (1u << 31)) return ECL_E_ARG;
   HIPCHK(h, hipSetDevice(h->dev));
   int rc;
@@ -580,6 +629,12 @@ extern "C" int ecl_hip_verify_eth(ecl_hip* h, const uint64_t (*k)[4], uint32_t n
   HIPCHK(h, hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return ECL_OK;
+}
+
+extern "C" int ecl_hip_verify_eth(ecl_hip* h, const uint64_t (*k)[4], uint32_t n, uint32_t (*addr)[5], uint8_t* ok) {
+  if (!h || !k || !addr || !ok || n == 0 || n > (1u << 31)) return ECL_E_ARG;
+  if (verify_takes_origins(h)) return verify_origin(h, (const uint64_t*)k, n, addr, nullptr, ok);
+  return verify_eth_plain(h, k, n, addr, ok);
 }
 
 extern "C" int ecl_hip_p2sh_hash(ecl_hip* h, const uint32_t (*h33)[5], uint32_t (*out)[5], uint32_t n) {

@@ -156,9 +156,11 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
       (flags & ~(types | ECL_ETH | ECL_TR | ECL_PUB | ECL_ENDO | ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX)))
     return ECL_E_ARG;
   // the prefix filter: beside addr33 / addr65 or beside eth, with or without the endomorphism
-  if ((flags & ECL_PREFIX) && (flags & ~(ECL_PREFIX | ECL_ADDR33 | ECL_ADDR65 | ECL_ETH | ECL_ENDO))) return ECL_E_ARG;
-  // the two walks of `bsgs`: each valid only as ECL_PUB | ECL_ORIGIN / ECL_PUB | ECL_INSERT (no endomorphism, no other type, not both)
-  if ((flags & ECL_ORIGIN) && flags != (ECL_PUB | ECL_ORIGIN)) return ECL_E_ARG;
+  // (and, for a split-key search, from an origin: ECL_PREFIX | ECL_ORIGIN beside the same types)
+  if ((flags & ECL_PREFIX) && (flags & ~(ECL_PREFIX | ECL_ORIGIN | ECL_ADDR33 | ECL_ADDR65 | ECL_ETH | ECL_ENDO))) return ECL_E_ARG;
+  // the two walks of `bsgs`: each valid only as ECL_PUB | ECL_ORIGIN / ECL_PUB | ECL_INSERT (no endomorphism, no other type, not both);
+  // the origin of a hashing walk only on a prefix context
+  if ((flags & ECL_ORIGIN) && !(flags & ECL_PREFIX) && flags != (ECL_PUB | ECL_ORIGIN)) return ECL_E_ARG;
   if ((flags & ECL_INSERT) && flags != (ECL_PUB | ECL_INSERT)) return ECL_E_ARG;
   // the herd of `kangaroo`: valid only as ECL_PUB | ECL_HERD; ord_offs is the number of distinguished-point bits
   if ((flags & ECL_HERD) && (flags != (ECL_PUB | ECL_HERD) || ord_offs > 32)) return ECL_E_ARG;
@@ -981,10 +983,12 @@ extern "C" int ecl_hip_add_range(ecl_hip* h, const uint64_t start[4], uint64_t n
   HIPCHK(h, hipSetDevice(h->dev));
   const u256 k0 = sc_reduce(u256_from(start));
   if (h->flags & ECL_ORIGIN) {  // twelve limbs: the scalar, then x and y of the origin point
-    if (!origin_from_limbs(h->origin_w, start + 4)) {
+    u32 ow[16];
+    if (!origin_from_limbs(ow, start + 4)) {  // (the context keeps the origin of the call before)
       h->err = "the origin is not a point of the curve";
       return ECL_E_ARG;
     }
+    memcpy(h->origin_w, ow, sizeof ow);
   }
   // the walks of `bsgs` and prefix contexts never take part in the look-ahead
   if (h->flags & (ECL_ORIGIN | ECL_INSERT | ECL_PREFIX)) return count_call(h, nkeys, add_core(h, k0, nkeys, out, cap, nout));

@@ -418,6 +418,54 @@ __global__ void __launch_bounds__(64) k_verify_eth(const u32* __restrict__ k, u3
   for (int w = 0; w < 5; ++w) addr[(size_t)i * 5 + w] = h[w];
   ok[i] = (u8)fin;
 }
+// Split-key contexts (ECL_PREFIX | ECL_ORIGIN): the hits of a walk over O + k G are re-derived as k_verify / k_verify_eth re-derive a key's -
+// the window-table sum of k, an inversion of the kernel's own - with one more mixed addition, + O, in between.  An entry is 24 words:
+// k[8], then the canonical words of O.x and O.y; the origin is per entry, so one launch verifies the endomorphism images of a walk as well
+// (image e of O + k G is O' + k' G with O' the same image of O: host/splitkey.h).  Every addition is the complete one (jac_madd), the
+// fallback tr_sum_complete takes for its degenerate sums: a zero digit adds nothing, k G = O doubles, k G = -O is the point at infinity.
+// O.x = O.y = 0 (no point of the curve) stands for an origin at infinity: the sum is k G alone.  Returns 0 where the sum is the point at
+// infinity - k G = -O, or k = 0 (mod n) with O at infinity - and nothing else is special.
+#define VERIFY_ORIGIN_WORDS 24u
+__device__ __forceinline__ int verify_origin_point(fe& x, fe& y, const u32* __restrict__ e, const u32* __restrict__ gtab) {
+  u32 kk[9], any = 0;
+#pragma unroll
+  for (int w = 0; w < 8; ++w) kk[w] = e[w];
+  kk[8] = 0;
+#pragma unroll
+  for (int w = 8; w < 24; ++w) any |= e[w];
+  jac acc = gtable_mul(kk, gtab);
+  if (any) acc = jac_madd(acc, fe_ldw(e + 8), fe_ldw(e + 16));
+  return jac_to_affine(x, y, acc);
+}
+__global__ void __launch_bounds__(64) k_verify_origin(const u32* __restrict__ k, u32 n, const u32* __restrict__ gtab, u32* __restrict__ h33,
+                                                      u32* __restrict__ h65, u8* __restrict__ ok) {
+  const u32 i = blockIdx.x * 64u + threadIdx.x;
+  if (i >= n) return;
+  fe x, y;
+  const int fin = verify_origin_point(x, y, k + (size_t)i * VERIFY_ORIGIN_WORDS, gtab);
+  u32 xw[8], yw[8], h[5];
+  fe_to_words(xw, x), fe_to_words(yw, y);
+  hash160_33(h, xw, yw[0] & 1u);
+#pragma unroll
+  for (int w = 0; w < 5; ++w) h33[(size_t)i * 5 + w] = h[w];
+  hash160_65(h, xw, yw);
+#pragma unroll
+  for (int w = 0; w < 5; ++w) h65[(size_t)i * 5 + w] = h[w];
+  ok[i] = (u8)fin;
+}
+__global__ void __launch_bounds__(64) k_verify_origin_eth(const u32* __restrict__ k, u32 n, const u32* __restrict__ gtab, u32* __restrict__ addr,
+                                                          u8* __restrict__ ok) {
+  const u32 i = blockIdx.x * 64u + threadIdx.x;
+  if (i >= n) return;
+  fe x, y;
+  const int fin = verify_origin_point(x, y, k + (size_t)i * VERIFY_ORIGIN_WORDS, gtab);
+  u32 xw[8], yw[8], h[5];
+  fe_to_words(xw, x), fe_to_words(yw, y);
+  eth_address(h, xw, yw);
+#pragma unroll
+  for (int w = 0; w < 5; ++w) addr[(size_t)i * 5 + w] = h[w];
+  ok[i] = (u8)fin;
+}
 // the P2SH half of pk_verify_hash (ecl_hip_p2sh_hash): the script hash of each given addr33 hash, one lane per hash
 __global__ void __launch_bounds__(64) k_p2sh_hash(const u32* __restrict__ h33, u32* __restrict__ out, u32 n) {
   const u32 i = blockIdx.x * 64u + threadIdx.x;

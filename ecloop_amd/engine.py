@@ -216,27 +216,30 @@ def max_over_ranks(seconds, dist=None):
 
 
 class FoundRecord:
-    __slots__ = ("label", "h160", "pk", "prefix", "address")
+    __slots__ = ("label", "h160", "pk", "prefix", "address", "split")
 
     def __init__(self, label, h160, pk):
         self.label, self.h160, self.pk = label, h160, pk
+        self.split = None  # a record of a split-key search: the image e; pk is then the PARTIAL key (splitkey_combine), its lines end with split:<e>
         self.address = ""  # a record of prefix_search: the address text, appended to its lines
         self.prefix = ""  # a verified pub record: "02" / "03", the first byte of the compressed key its line prints
 
     def line(self):
         """outfile format of ctx_write_found (main.c:193-195)"""
-        return "%s\t%s\t%064x" % (self.label, self.prefix + "".join("%08x" % int(w) for w in self.h160), self.pk) + ("\t" + self.address if self.address else "")
+        return "%s\t%s\t%064x" % (self.label, self.prefix + "".join("%08x" % int(w) for w in self.h160), self.pk) + ("\t" + self.address if self.address else "") + \
+            ("" if self.split is None else "\tsplit:%d" % self.split)
 
     def stdout_line(self):
         """stdout format (main.c:187-189)"""
-        return "%s: %s <- %064x" % (self.label, self.prefix + "".join("%08x" % int(w) for w in self.h160), self.pk) + (" " + self.address if self.address else "")
+        return "%s: %s <- %064x" % (self.label, self.prefix + "".join("%08x" % int(w) for w in self.h160), self.pk) + (" " + self.address if self.address else "") + \
+            ("" if self.split is None else " split:%d" % self.split)
 
 
 class KeySearch:
     """ctx_t + cmd_add / cmd_mul for one GPU."""
 
     def __init__(self, flt, device=0, a33=True, a65=False, endo=False, ord_offs=0, verify=True, launch_keys=1 << 32,
-                 half_group=0, max_lanes=0, device_cls=None, p2sh=False, eth=False, tr=False, pub=False, prefix=False):
+                 half_group=0, max_lanes=0, device_cls=None, p2sh=False, eth=False, tr=False, pub=False, prefix=False, origin=None):
         if pub:
             a33 = False  # public keys are searched alone (with or without the endomorphism)
         elif tr:
@@ -261,6 +264,12 @@ class KeySearch:
             kw["pub"] = True
         if prefix:  # flt: a PrefixFilter - the range table stands where the bloom words stand (prefix_search)
             kw["prefix"] = True
+        self.origin = None  # split-key search (prefix_search(origin=)): the walk is O + k G, the records' keys are partial keys
+        if origin is not None:
+            if not prefix:
+                raise ValueError("an origin goes with the prefix search only (prefix_search(origin=(x, y)))")
+            self.origin = (int(origin[0]), int(origin[1]))
+            kw["origin"] = True
         self.dev = (device_cls or Device)(device, a33=a33, a65=a65, endo=endo, ord_offs=ord_offs, **kw)
         if half_group or max_lanes:
             self.dev.set_geometry(half_group, max_lanes)
@@ -282,6 +291,18 @@ class KeySearch:
     # the self-test of the context pins that sum against the double-and-add kernel)
     def _verify(self, recs):
         if not recs:
+            return
+        if self.origin is not None:  # image e of O + k G is O' + k' G: k' = the record's partial key, O' the same image of O
+            orgs = [splitkey_image_origin(self.origin, r.split) for r in recs]
+            if self.eth:
+                h33, ok = self.dev.verify_eth([r.pk for r in recs], origin=orgs)
+                h65 = h33
+            else:
+                h33, h65, ok = self.dev.verify([r.pk for r in recs], origin=orgs)
+            for i, r in enumerate(recs):
+                h = h65[i] if r.label == "addr65" else h33[i]
+                if not ok[i] or [int(v) for v in h] != [int(v) for v in r.h160]:
+                    raise EclError("[!] error: hash mismatch (%s) pk: %064x" % (r.label, r.pk))
             return
         tr = [r for r in recs if r.label == "p2tr"]
         if tr:  # the first 20 bytes of the re-derived output key against the record, which then carries all 32
@@ -326,6 +347,8 @@ class KeySearch:
                 continue
             pk = calc_priv(start, self.stride, int(r["key_offset"]), int(r["endo"]))
             recs.append(FoundRecord(label_of(r["compressed"]), [int(v) for v in r["h160"]], pk))
+            if self.origin is not None:
+                recs[-1].split = int(r["endo"])
         if self.verify:
             self._verify(recs)
         self.found.extend(recs)
@@ -345,7 +368,7 @@ class KeySearch:
             s = (start + done * self.stride) % N
             c = cap
             while True:
-                raw, total = self.dev.add_range(s, n, cap=c)
+                raw, total = self.dev.add_range(s, n, cap=c) if self.origin is None else self.dev.add_range(s, n, cap=c, origin=self.origin)
                 if total <= c:
                     break
                 # overflow (dense filters only): the device kept up to max(cap, 2^20) records of the call - read the rest; only
@@ -580,14 +603,31 @@ class PrefixFilter:
         return True
 
 
-def prefix_search(patterns, range_s, range_e, a33=True, a65=False, eth=False, endo=False, device=0, device_cls=None, verify=True, **kw):
+SPLITKEY_BETA = 0x7AE96A2B657C07106E64479EAC3434E99CF0497512F58995C1396C28719501EE  # x -> beta x is the point map of k -> lambda k
+
+
+def splitkey_image_origin(origin, e):
+    """image e (0 ... 5, the `endo` byte of a record) of the point (x, y): x times beta^(e // 2), y negated for odd e (host/splitkey.h)"""
+    x, y = origin
+    return x * pow(SPLITKEY_BETA, e // 2, P) % P, (P - y) % P if e & 1 else y
+
+
+def splitkey_combine(kq, partial, e=0):
+    """the requester's final key of a split-key hit: calc_priv(k_Q, e) + partial (mod n); e = 0: k_Q + partial (host/splitkey.h: sk_combine)"""
+    return (calc_priv(kq % N, 1, 0, e) + partial) % N
+
+
+def prefix_search(patterns, range_s, range_e, a33=True, a65=False, eth=False, endo=False, device=0, device_cls=None, verify=True, origin=None, **kw):
     """`add -p` for one GPU: the keys of [range_s, range_e) (cmd_add's job arithmetic) whose address starts with one of the patterns.
-    -> (records, edge): FoundRecord objects with .address set, and the number of records dropped because their text matched no pattern"""
+    -> (records, edge): FoundRecord objects with .address set, and the number of records dropped because their text matched no pattern.
+    origin=(x, y), a point Q of the curve: the split-key search (`-p` with `-k`) - the walk is Q + k G, a record's pk is the PARTIAL key
+    k' and .split the image e it belongs to: the address is that of the key splitkey_combine(k_Q, k', e), which only Q's owner can form"""
     patterns = list(patterns)
     if eth:
         a33 = a65 = False
     table, _ = prefix_ranges(patterns, a33, a65, eth)
-    ks = KeySearch(PrefixFilter(table), device=device, a33=a33, a65=a65, endo=endo, eth=eth, verify=verify, device_cls=device_cls, prefix=True, **kw)
+    ks = KeySearch(PrefixFilter(table), device=device, a33=a33, a65=a65, endo=endo, eth=eth, verify=verify, device_cls=device_cls, prefix=True,
+                   **({"origin": bsgs_point(origin)} if origin is not None else {}), **kw)
     try:
         out, edge = [], 0
         for r in ks.cmd_add(range_s, range_e):

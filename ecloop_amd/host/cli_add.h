@@ -71,8 +71,10 @@ static void *scan_worker(void *arg) {
     sc s = scan_scalar(run, &sn->rs, &lo);
     u32 cnt = 0;
     int rc;
+    u64 start[12]; /* -p with -k: the scalar, then the origin - the same origin for every chunk and every shard */
+    memcpy(start, s.w, 32), memcpy(start + 4, run->origin, 64);
     for (;;) {
-      rc = ecl_hip_add_range(run->dev[w->g], s.w, n, buf, cap, &cnt);
+      rc = ecl_hip_add_range(run->dev[w->g], start, n, buf, cap, &cnt);
       if (rc != ECL_E_OVERFLOW) break;
       /* dense filter: the device kept the records that did not fit (up to max(cap, 2^20) per call) - read them; only a call with
          more hits than that is run again with a buffer that fits */

@@ -187,6 +187,7 @@ typedef struct {
   const char *pubkey, *baby, *words; /* bsgs: -k, -b, -m */
   const char *herd, *dp, *maxf;      /* kangaroo: -herd, -dp, -max (and -k, -seed) */
   const char *prefix;                /* add / rnd: -p */
+  const char *part, *split;          /* combine: -part, -split (and, with -p, -k: the split-key search) */
   bool quiet, endo, raw, bin, version, host_only, rnd_jobs, as_mul;
 } opts_t;
 typedef struct { const char *flag; size_t at; bool takes_value; } optdef_t;
@@ -198,7 +199,7 @@ static const optdef_t OPTDEFS[] = {
     {"-bin", offsetof(opts_t, bin), false},       {"-v", offsetof(opts_t, version), false}, {"-host", offsetof(opts_t, host_only), false},
     {"-rnd", offsetof(opts_t, rnd_jobs), false},  {"-mul", offsetof(opts_t, as_mul), false},
     {"-k", offsetof(opts_t, pubkey), true},       {"-b", offsetof(opts_t, baby), true},     {"-m", offsetof(opts_t, words), true},
-    {"-p", offsetof(opts_t, prefix), true},
+    {"-p", offsetof(opts_t, prefix), true},      {"-part", offsetof(opts_t, part), true},  {"-split", offsetof(opts_t, split), true},
     {"-herd", offsetof(opts_t, herd), true},      {"-dp", offsetof(opts_t, dp), true},      {"-max", offsetof(opts_t, maxf), true},
 };
 static void opts_parse(opts_t *o, int argc, const char **argv) {

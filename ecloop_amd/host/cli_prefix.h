@@ -49,11 +49,12 @@ static void prefix_check_options(const opts_t *o, const char *verb) {
 }
 /* the hits of one device call, verified already: each one's address text against the patterns.  A record that matches none is a range's
    end value whose checksum does not fit: dropped and counted (the status line shows the count).  The found line is the sink's with the
-   address appended: "addr33: <hash160> <- <key> <address>" on stdout, a fourth tab-separated field in the -o file */
+   address appended: "addr33: <hash160> <- <key> <address>" on stdout, a fourth tab-separated field in the -o file.  A split-key run
+   (-k) prints the partial key there and one more field, split:<e> - the image the requester's `combine` needs */
 static void prefix_report(run_t *run, const ecl_found *hits, const sc *keys, u32 n) {
   report_t *r = &run->rep;
   for (u32 i = 0; i < n; ++i) {
-    char addr[48], hh[41], kk[65];
+    char addr[48], hh[41], kk[65], sp[16] = "", spf[16] = "";
     if (pfx_match(run->pfx, hits[i].h160, hits[i].compressed, addr) < 0) {
       pthread_mutex_lock(&r->mu);
       r->edge++;
@@ -62,9 +63,10 @@ static void prefix_report(run_t *run, const ecl_found *hits, const sc *keys, u32
     }
     hex_of_words(hh, hits[i].h160, 5), hex_of_scalar(kk, &keys[i]);
     const char *label = hits[i].compressed == 3 ? "eth" : hits[i].compressed ? "addr33" : "addr65";
+    if (run->split) snprintf(sp, sizeof sp, " split:%u", hits[i].endo), snprintf(spf, sizeof spf, "\tsplit:%u", hits[i].endo);
     pthread_mutex_lock(&r->mu);
-    if (!r->quiet) erase_status_line(), printf("%s: %s <- %s %s\n", label, hh, kk, addr), fflush(stdout);
-    if (r->file) fprintf(r->file, "%s\t%s\t%s\t%s\n", label, hh, kk, addr), fflush(r->file);
+    if (!r->quiet) erase_status_line(), printf("%s: %s <- %s %s%s\n", label, hh, kk, addr, sp), fflush(stdout);
+    if (r->file) fprintf(r->file, "%s\t%s\t%s\t%s%s\n", label, hh, kk, addr, spf), fflush(r->file);
     r->found++;
     status_show_locked(r);
     pthread_mutex_unlock(&r->mu);

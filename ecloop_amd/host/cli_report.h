@@ -114,6 +114,9 @@ typedef struct run_t {
   sc range_s, range_e, stride_k;
   u32 ord_offs, ord_size;
   pfx_plan *pfx; /* -p: the plan of the patterns (cli_prefix.h), NULL otherwise */
+  bool split;    /* -p with -k: the walk starts from the requester's public key (cli_splitkey.h); the keys reported are partial keys */
+  u64 origin[8]; /* ... its x and y, the last eight of the twelve limbs of every add_range call */
+  char split_hex[67];
 } run_t;
 
 /* A failed library call ends the run.  Device threads can fail at the same time (`mul`'s two contexts of a GPU): the first one reports and
@@ -145,6 +148,25 @@ static void verify_fail(const sc *key, const ecl_found *hit, const u32 *want) {
 #define FULL_WORDS 9 /* a whole key for the found line: eight words (p2tr: the output key; pub: x) and the parity of y (pub) */
 static void verify_hits(run_t *run, int g, const sc *keys, const ecl_found *hits, u32 n, u32 (*full)[FULL_WORDS]) {
   if (!n) return;
+  if (run->split) { /* -p with -k: the point of a hit is Q + k G; its image `endo` is O' + k' G, k' = keys[i] (calc_priv's) and O' the same image
+                       of Q (splitkey.h) - twelve limbs per entry, re-derived by the window-table sum + O' (ecl_hip_verify on such a context) */
+    u64 (*ent)[12] = malloc((size_t)n * sizeof *ent);
+    u32 (*h33)[5] = malloc((size_t)n * 20), (*h65)[5] = malloc((size_t)n * 20);
+    u8 *fin = malloc(n);
+    for (u32 i = 0; i < n; ++i) {
+      memcpy(ent[i], keys[i].w, 32), memcpy(ent[i] + 4, run->origin, 64);
+      sk_image_origin(ent[i] + 4, ent[i] + 8, hits[i].endo);
+    }
+    int rc = run->eth ? ecl_hip_verify_eth(run->dev[g], (const uint64_t(*)[4])ent, n, h33, fin)
+                      : ecl_hip_verify(run->dev[g], (const uint64_t(*)[4])ent, n, h33, h65, fin);
+    if (rc != ECL_OK) die_ecl(run, g, rc, "verify");
+    for (u32 i = 0; i < n; ++i) {
+      const u32 *want = run->eth || hits[i].compressed ? h33[i] : h65[i];
+      if (hits[i].compressed != (run->eth ? 3 : hits[i].compressed ? 1 : 0) || !fin[i] || memcmp(want, hits[i].h160, 20)) verify_fail(&keys[i], &hits[i], want);
+    }
+    free(ent), free(h33), free(h65), free(fin);
+    return;
+  }
   if (run->pub) { /* the key's point by the double-and-add kernel (ecl_hip_diag_mulg: neither the walk nor the window sum), x and y */
     u64 (*x)[4] = malloc((size_t)n * 32), (*y)[4] = malloc((size_t)n * 32);
     u8 *fin = malloc(n);

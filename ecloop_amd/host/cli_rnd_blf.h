@@ -251,6 +251,9 @@ static void usage(const char *prog) { /* the reference's help text (main.c:750-7
       "                    place of -f: 1... (base58 P2PKH; -a c, u or cu), bc1q... (bech32 P2WPKH; -a c) or 0x... (Ethereum; -a e, case is\n",
       "                    ignored: EIP-55 case is not matched).  Patterns that cover more than 2^-16 of all addresses are refused:\n",
       "                    lengthen them.  A found line ends with the address\n",
+      "  -k <pubkey>     - add, rnd with -p: split-key search on another person's behalf.  The walk starts from their public key (66 hex digits\n",
+      "                    02.. / 03.., or 130 digits 04..; one key), the keys printed are PARTIAL keys, worthless without the owner's private\n",
+      "                    key, and a found line ends with split:<e>.  The owner runs combine\n",
       "  -o <file>       - output file to write found keys (default: stdout)\n",
       "  -t <gpus>       - number of GPUs to use (default: all)\n",
       "  -a <addr_type>  - address type to search: c - addr33, u - addr65, s - p2sh (nested SegWit, 3...), e - eth (Ethereum), t - p2tr (Taproot, bc1p...), x - pubkey (public key, by its x coordinate) (default: c)\n",
@@ -278,6 +281,9 @@ static void usage(const char *prog) { /* the reference's help text (main.c:750-7
       "  -seed <s>       - seed of the jump table and the start offsets (default: 0)\n",
       "  -max <factor>   - give up after factor * 2 sqrt(range) jumps (default: 64)\n",
       "\nOther commands:\n",
+      "  combine         - combine -part <partial key> [-split <e>]: the final key of a split-key hit.  Reads the OWNER's private key (hex)\n",
+      "                    from stdin - never type it on the searcher's machine - and prints it combined with the partial key; with a GPU\n",
+      "                    visible, the final key's addresses as well\n",
       "  blf-gen         - create bloom filter from list of hex-encoded hash160\n",
       "  blf-check       - check bloom filter for given hex-encoded hash160\n\n"};
   printf("Usage: %s <cmd> [-t <gpus>] [-f <file>] [-a <addr_type>] [-r <range>]\nv%s ~ MI355X build of the ecloop command set\n", prog, VERSION);

@@ -52,6 +52,7 @@ typedef uint8_t u8;
 typedef struct { u64 w[4]; } sc; /* 256-bit scalar, little-endian limbs (the reference's fe) */
 
 #include "prefix_plan.h"
+#include "splitkey.h"
 #include "cli_base.h"
 #include "cli_filter.h"
 #include "cli_report.h"
@@ -62,6 +63,7 @@ typedef struct { u64 w[4]; } sc; /* 256-bit scalar, little-endian limbs (the ref
 #include "cli_keys.h"
 #include "cli_bsgs.h"
 #include "cli_kangaroo.h"
+#include "cli_splitkey.h"
 
 /* ------------------------------------------------------------------------------------------- device bring-up */
 /* Device contexts of a run: context g works on GPU (g mod shown) mod real, where `shown` is the -t count clamped to
@@ -119,7 +121,8 @@ static double bring_up(run_t *run, int shown, int real) {
     if (!(keys.w[1] | keys.w[2] | keys.w[3]) && keys.w[0] < largest_call) largest_call = keys.w[0];
   }
   const u32 flags = (run->a33 ? ECL_ADDR33 : 0) | (run->a65 ? ECL_ADDR65 : 0) | (run->p2sh ? ECL_P2SH : 0) | (run->eth ? ECL_ETH : 0) |
-                    (run->tr ? ECL_TR : 0) | (run->pub ? ECL_PUB : 0) | (run->endo ? ECL_ENDO : 0) | (run->pfx ? ECL_PREFIX : 0);
+                    (run->tr ? ECL_TR : 0) | (run->pub ? ECL_PUB : 0) | (run->endo ? ECL_ENDO : 0) | (run->pfx ? ECL_PREFIX : 0) |
+                    (run->split ? ECL_ORIGIN : 0);
   pthread_t th[MAX_GPUS];
   bringup_t job[MAX_GPUS];
   for (int g = 0; g < run->ngpus; ++g) {
@@ -186,12 +189,15 @@ int main(int argc, const char **argv) {
   }
   list_skip_0x = run.eth;
   /* -p (no reference counterpart): addresses that START with given characters, add / rnd only, no filter file (cli_prefix.h) */
+  /* -k with add / rnd / mul (no reference counterpart): the split-key form of -p, nowhere else (cli_splitkey.h) */
+  if (o->pubkey) splitkey_check_options(o, verb);
   if (o->prefix) prefix_check_options(o, verb);
   /* commands that need no search context */
   if (!strcmp(verb, "blf-gen")) return cmd_blf_gen(o, argv[0]), 0;
   if (!strcmp(verb, "blf-check")) return cmd_blf_check(o, argc, argv), 0;
   if (!strcmp(verb, "bsgs")) return cmd_bsgs(o); /* its own contexts and filter: no -f, no -a */
   if (!strcmp(verb, "kangaroo")) return cmd_kangaroo(o); /* its own context, no filter: no -f, no -a */
+  if (!strcmp(verb, "combine")) return cmd_combine(o);   /* the requester's side of a split-key search: mod-n arithmetic, a GPU only for the addresses */
   if (!strcmp(verb, "parse")) { /* hidden: `mul`'s text front end alone (no GPU), for the parser tests */
     run.cmd = CMD_MUL, run.parse_only = true, run.ngpus = 1, run.bin = o->bin;
     report_init(&run.rep, NULL, true);
@@ -217,6 +223,7 @@ int main(int argc, const char **argv) {
   if (!run.a33 && !run.a65 && !run.p2sh && !run.eth && !run.tr && !run.pub) run.a33 = true; /* main.c:825-827 */
   run.endo = o->endo && run.cmd != CMD_MUL, run.bin = o->bin && run.cmd == CMD_MUL;
   if (o->prefix && !plan_only) prefix_open(&run, o->prefix); /* needs the address types: refuses a pattern form that does not fit -a */
+  if (o->prefix && o->pubkey && !plan_only) splitkey_open(&run, o->pubkey);
   report_init(&run.rep, o->outfile, o->quiet);
   run.rep.prefix = run.pfx != NULL;
   range_from_option(o->range, &run.range_s, &run.range_e);
@@ -266,6 +273,7 @@ int main(int argc, const char **argv) {
   if (run.pfx) printf("prefix (%u pattern%s, %u range%s)\n", run.pfx->npat, run.pfx->npat == 1 ? "" : "s", run.pfx->nrange, run.pfx->nrange == 1 ? "" : "s");
   else if (run.flt.list) printf("list (%'llu)\n", (unsigned long long)run.flt.nlist);
   else printf("bloom\n");
+  if (run.split) printf("split key: the keys printed are PARTIAL keys for %s (its owner adds their own: combine -part <key> -split <e>)\n", run.split_hex);
   if (run.cmd == CMD_ADD) print_scalar_row("range_s", &run.range_s), print_scalar_row("range_e", &run.range_e);
   printf("setup: %.2fs (%d device context%s opened in parallel, %.0f MB filter uploaded, walk buffers reserved)\n", setup_s, run.ngpus,
          run.ngpus == 1 ? "" : "s", run.flt.nwords * 8 / 1e6);

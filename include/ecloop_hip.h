@@ -80,7 +80,8 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
    ECL_E_ARG.
    ECL_ORIGIN and ECL_INSERT (no reference counterpart): the two walks of a baby-step giant-step search for the key of a KNOWN public key
    (the `bsgs` command; ecloop_amd/host/bsgs_plan.h has the method).  Each is valid in exactly one combination - ECL_PUB | ECL_ORIGIN,
-   ECL_PUB | ECL_INSERT - and ECL_E_ARG with ECL_ENDO, with any other type, with each other or without ECL_PUB.  Neither takes part in
+   ECL_PUB | ECL_INSERT - and ECL_E_ARG with ECL_ENDO, with any other type, with each other or without ECL_PUB (but for ECL_ORIGIN beside
+   ECL_PREFIX, the split-key search: see ECL_PREFIX).  Neither takes part in
    the look-ahead, and ecl_hip_mul_batch(_raw) on them is ECL_E_ARG.
    ECL_PUB | ECL_ORIGIN: a public-key walk that starts from a point nobody knows the scalar of.  The `start` argument of ecl_hip_add_range
    points to TWELVE limbs: the scalar, then the affine x and y of an origin point O (little-endian u64 limbs, both below p, y^2 = x^3 + 7:
@@ -120,7 +121,7 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
    ecloop_amd/host/prefix_plan.h turns patterns into ranges).  In place of a bloom filter the context holds a table of n inclusive ranges
    [lo, hi] over the 160-bit value, words in the record's order (h160[0] most significant), and reports a key iff a hash of it lies inside
    a range: no false positives, no duplicates.  Valid beside ECL_ADDR33 / ECL_ADDR65 with or without ECL_ENDO, or beside ECL_ETH with or
-   without ECL_ENDO; with ECL_P2SH, ECL_TR, ECL_PUB, ECL_ORIGIN, ECL_INSERT or ECL_HERD it is ECL_E_ARG.  On such a context
+   without ECL_ENDO; with ECL_P2SH, ECL_TR, ECL_PUB, ECL_INSERT or ECL_HERD it is ECL_E_ARG (ECL_ORIGIN: below).  On such a context
      ecl_hip_set_bloom(h, words, nwords) takes the TABLE: nwords = 5 n, each range ten uint32 - lo[5], hi[5] - with 1 <= n <= 65536, lo <= hi,
        the ranges sorted by lo and disjoint; nwords no multiple of 5, n out of range, lo > hi, an unsorted table or overlapping ranges are
        ECL_E_ARG.  The library builds the stage-1 bitmap (one bit per 2^-24 of the space) itself;
@@ -128,7 +129,16 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
        the coverage check); the context never takes part in the look-ahead;
      ecl_hip_set_list, ecl_hip_bloom_insert, ecl_hip_bloom_insert_count, ecl_hip_get_bloom, ecl_hip_mul_batch and ecl_hip_mul_batch_raw are
        ECL_E_ARG;
-     ecl_hip_diag_bloom runs the device's two-stage prefix test on the given values (hit = the value lies inside a range). */
+     ecl_hip_diag_bloom runs the device's two-stage prefix test on the given values (hit = the value lies inside a range).
+   ECL_PREFIX | ECL_ORIGIN (the split-key vanity search, `-p` with `-k`): the one hashing combination ECL_ORIGIN is valid in - beside
+   ECL_PREFIX and ECL_ADDR33, ECL_ADDR65, both, or ECL_ETH, with or without ECL_ENDO; ECL_ORIGIN on a hashing context without ECL_PREFIX,
+   and ECL_PREFIX | ECL_PUB | ECL_ORIGIN, stay ECL_E_ARG.  The context is the prefix context above whose walk starts from the caller's
+   point: `start` of ecl_hip_add_range points to TWELVE limbs, treated exactly as ECL_PUB | ECL_ORIGIN treats them (the origin checked on
+   the host, ECL_E_ARG; a base point that is -O: ECL_E_RANGE; a call continues the resident walk only if its origin is the one before's;
+   no look-ahead; ecl_hip_mul_batch(_raw) ECL_E_ARG), and the call reports the keys j whose point O + (start + j 2^ord_offs) G has a hash
+   inside a range - records, key_offset (from the call's scalar), endo (the six images of that point) and compressed as on the plain
+   prefix context.  The scalars say nothing about the points' keys: whoever knows the origin's key k_O adds it (host/splitkey.h).  On such
+   a context each entry of `k` of ecl_hip_verify / ecl_hip_verify_eth is TWELVE limbs, too - see there. */
 #define ECL_ADDR33 1u
 #define ECL_ADDR65 2u
 #define ECL_ENDO 4u
@@ -243,7 +253,14 @@ int ecl_hip_set_list(ecl_hip *h, const uint32_t (*h160)[5], uint64_t n);
    device by a path other than the walk kernel (fixed-base window sum + own inversion per key).  The window sum and its
    table also give the base centre of a non-contiguous walk, and a hit shares its high digits with that centre, so
    the context self-test checks the window sum against the double-and-add kernel on full-width scalars.  ok[i] = 0
-   for k = 0 (mod n).  The caller compares with the hit's h160 and treats a mismatch as fatal, like the reference. */
+   for k = 0 (mod n).  The caller compares with the hit's h160 and treats a mismatch as fatal, like the reference.
+   On a context opened with ECL_PREFIX | ECL_ORIGIN each entry of `k` is TWELVE limbs, like the `start` of its ecl_hip_add_range: the
+   scalar, then x and y of an origin O (a point of the curve, checked on the host: ECL_E_ARG otherwise; all eight limbs zero: the point at
+   infinity), one origin per entry, and the hashes are those of O + k G - the window-table sum, one more complete mixed addition, an
+   inversion of the kernel's own (k_verify_origin; ecl_hip_verify_eth: k_verify_origin_eth): not the walk.  ok[i] = 0 where O + k G is
+   the point at infinity (k G = -O, or k = 0 (mod n) with O at infinity), in no other case.  n <= 2^24 there.  The image `endo` of a
+   walked point O + k G is O' + k' G with k' = calc_priv(k, endo) and O' the same image of O, so a hit with endo != 0 is verified by
+   the entry (k', O').  Every other context takes four limbs per entry, as always. */
 int ecl_hip_verify(ecl_hip *h, const uint64_t (*k)[4], uint32_t n, uint32_t (*h33)[5], uint32_t (*h65)[5], uint8_t *ok);
 /* ... and its P2SH half: out[i] = hash160(0x00 0x14 || h33[i]), the P2SH-P2WPKH hash of a key whose addr33 hash is h33[i] (both in
    h160_t words), computed on the device by the hash function of the search kernels.  A caller verifies a type-2 hit by passing the h33 of

@@ -3,6 +3,8 @@
   p   ecl_hip_add_range with ECL_ADDR33 | ECL_PREFIX over 2^32 keys, the table of one long pattern (default 1BgGZ9tcN4);
   c   the same range with ECL_ADDR33 against a small `.blf` - the filter blf-gen sizes for 1000 entries (5392 bytes), with those many
       random hashes in it: the unchanged addr33 kernel of this build, its stage 1 one cached probe like the prefix kernel's bitmap load;
+  o   `p` from an origin (ECL_ADDR33 | ECL_PREFIX | ECL_ORIGIN, the split-key search of DESIGN.md §7 (f12)): the same kernel, the same table and
+      the same scalars, walked from the point Q = 0xdc2a04 G - the expected ratio o / p is 1 within the spread of the runs;
 warm, `runs` alternating rounds, medians and their ratio reported.  Look-ahead off, 2^20 lanes per context (the half group stays automatic).
 
 usage: bench_prefix.py rates [runs = 3] [log2 keys = 32] [pattern = 1BgGZ9tcN4]"""
@@ -21,10 +23,10 @@ from ecloop_amd import capi, engine  # noqa: E402
 START = 0x4000_0000_0000
 
 
-def timed_add(d, start, n):
+def timed_add(d, start, n, origin=None):
     ms0 = d.timing()[0]
     t0 = time.perf_counter()
-    recs, total = d.add_range(start, n, cap=1 << 16)
+    recs, total = d.add_range(start, n, cap=1 << 16) if origin is None else d.add_range(start, n, cap=1 << 16, origin=origin)
     wall = time.perf_counter() - t0
     return (d.timing()[0] - ms0) * 1e-3, wall, total
 
@@ -39,22 +41,30 @@ def rates(runs, log2, pattern):
     c = capi.Device(0, a33=True)
     c.set_bloom(words)
     c.set_lookahead(0)
-    ctx = {"p": p, "c": c}
-    for d in ctx.values():
+    o = capi.Device(0, a33=True, prefix=True, origin=True)
+    o.set_prefixes(table)
+    xs, ys, ok = c.diag_mulg([0xDC2A04])
+    origin = {"p": None, "c": None, "o": (xs[0], ys[0])}
+    ctx = {"p": p, "o": o, "c": c}
+    for leg, d in ctx.items():
         d.set_geometry(0, 1 << 20)
-        timed_add(d, START - (1 << 28), 1 << 28)  # warm: tables, buffers, code objects
-    rows = {"p": [], "c": []}
+        timed_add(d, START - (1 << 28), 1 << 28, origin[leg])  # warm: tables, buffers, code objects
+    rows = {"p": [], "o": [], "c": []}
     for r in range(runs):
-        for leg in ("p", "c"):
-            rows[leg].append(timed_add(ctx[leg], START + r * n, n))
+        for leg in ("p", "o", "c"):
+            rows[leg].append(timed_add(ctx[leg], START + r * n, n, origin[leg]))
     res = {"runs": runs, "keys": n, "pattern": pattern, "ranges": len(table), "blf_bytes": len(words) * 8,
            "geometry": {k: ctx[k].plan_geometry(n) for k in ctx}}
-    for leg in ("p", "c"):
+    for leg in ("p", "o", "c"):
         res[leg] = {"event_M_per_s": [round(n / e / 1e6, 1) for e, _, _ in rows[leg]], "wall_M_per_s": [round(n / w / 1e6, 1) for _, w, _ in rows[leg]],
                     "event_median_M_per_s": round(statistics.median(n / e / 1e6 for e, _, _ in rows[leg]), 1),
                     "wall_median_M_per_s": round(statistics.median(n / w / 1e6 for _, w, _ in rows[leg]), 1), "hits": [h for _, _, h in rows[leg]]}
     res["p_over_c_event"] = round(res["p"]["event_median_M_per_s"] / res["c"]["event_median_M_per_s"], 3)
+    res["o_over_p_event"] = round(res["o"]["event_median_M_per_s"] / res["p"]["event_median_M_per_s"], 3)
+    res["p_spread_event"] = round(max(res["p"]["event_M_per_s"]) / min(res["p"]["event_M_per_s"]), 3)
+    res["o_spread_event"] = round(max(res["o"]["event_M_per_s"]) / min(res["o"]["event_M_per_s"]), 3)
     res["coverage_p"] = p.coverage()
+    res["coverage_o"] = o.coverage()
     for d in ctx.values():
         d.close()
     print(json.dumps(res))

@@ -24,7 +24,9 @@ usage: tools/isa_mix.py [file.s] [mangled kernel name] [--json]     |     tools/
        tools/isa_mix.py --tr    (the Taproot kernels: registers, loops, the static VALU counts of the tagged hash and the window loop)
        tools/isa_mix.py --pub   (the public-key kernels: registers, loops, the static per-key VALU count beside -a c's from the same assembly)
        tools/isa_mix.py --bsgs  (the kernels `bsgs` adds: the insert walk beside -a x's from the same assembly, the origin set-up kernel)
-       tools/isa_mix.py --kangaroo  (the herd walk of `kangaroo`: registers, the two per-kangaroo loops, a jump's static count and the inversion's share by M)"""
+       tools/isa_mix.py --kangaroo  (the herd walk of `kangaroo`: registers, the two per-kangaroo loops, a jump's static count and the inversion's share by M)
+       tools/isa_mix.py --splitkey  (the two verification kernels of the split-key search: registers, spills, static VALU count, scratch in the window loop)
+       tools/isa_mix.py --compare other.s [file.s]  (every kernel of both assemblies: instruction mix, registers, spills, LDS, scratch, kernarg size; which differ, which are new)"""
 import json
 import os
 import re
@@ -391,6 +393,65 @@ def analyse_herd(path=ASM):
     return {"herd walk": r, "herd init": {"kernel": o, "registers": spills(path, o).get(o)}}
 
 
+# the kernels the split-key search adds (-p with -k): the re-derivation of a hit, O + k G by the window-table sum and one more complete addition
+SPLITKEY_KERNELS = {"verify origin": "_Z15k_verify_originPKjjS0_PjS1_Ph", "verify origin eth": "_Z19k_verify_origin_ethPKjjS0_PjPh"}
+SPLITKEY_MIRRORS = {"verify origin": "_Z8k_verifyPKjjS0_PjS1_Ph", "verify origin eth": "_Z12k_verify_ethPKjjS0_PjPh"}
+
+
+def kernel_meta(path=ASM):
+    """name -> the code object's metadata of every kernel: register counts, spill counts, scratch, LDS and kernarg sizes"""
+    s = open(path).read()
+    out = {}
+    for m in re.finditer(r"- \.agpr_count:.*?\n(?=  - \.agpr_count:|amdhsa\.target|\.\.\.)", s, re.S):
+        blk = m.group(0)
+        name = re.search(r"\.name:\s+(\S+)", blk)
+        if not name:
+            continue
+        g = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", blk).group(1))
+        out[name.group(1)] = {k: g(k) for k in ("vgpr_count", "sgpr_count", "agpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size",
+                                                "group_segment_fixed_size", "kernarg_segment_size")}
+    return out
+
+
+def kernel_table(path=ASM):
+    """name -> metadata + the static instruction mix of every kernel of the assembly"""
+    out = {}
+    for name, meta in kernel_meta(path).items():
+        bl, _ = blocks(path, name)
+        total = zero()
+        for b in bl:
+            for k in KEYS:
+                total[k] += b["c"][k]
+        out[name] = {**meta, **total}
+    return out
+
+
+def compare(other, path=ASM):
+    """the kernels of `path` against those of `other` (the parent's build): identical, different (with both rows), new, gone"""
+    a, b = kernel_table(other), kernel_table(path)
+    return {"kernels_other": len(a), "kernels": len(b), "identical": sum(1 for k in a if k in b and a[k] == b[k]),
+            "different": {k: {"other": a[k], "this": b[k]} for k in a if k in b and a[k] != b[k]},
+            "new": sorted(k for k in b if k not in a), "gone": sorted(k for k in a if k not in b)}
+
+
+def analyse_splitkey(path=ASM):
+    """the two verification kernels beside the kernels whose bodies they are (k_verify, k_verify_eth) from the same assembly: registers /
+    spills / scratch, the static instruction mix, their loops (the window loop is the one with the multiply-adds: the sum of table points)
+    and the scratch instructions inside it - tests/test_splitkey_host.py wants 0"""
+    meta = kernel_meta(path)
+    out = {}
+    for label, k in SPLITKEY_KERNELS.items():
+        r = {}
+        for tag, name in (("kernel", k), ("mirror", SPLITKEY_MIRRORS[label])):
+            a = analyse(path, name)
+            loops = [{x: l[x] for x in ("header", "depth", "parent", "valu", "mad64", "vmem", "scratch", "scratch_at_calls")} for l in a["loops"]]
+            win = max(loops, key=lambda l: l["mad64"]) if loops else None
+            r[tag] = {"name": name, "registers": meta.get(name), "total": a["total"], "loops": loops,
+                      "window_loop": win, "window_loop_scratch": win["scratch"] if win else None}
+        out[label] = r
+    return out
+
+
 def analyse_all(path=ASM):
     """every shipped instantiation of the two search kernels: fingerprint, registers / spills, and the scratch instructions inside the
     per-key loops (k_add: prefix-product, table and `which` loops; k_mul_check: window loop) - tests/test_profiles_fresh.py wants 0 there"""
@@ -435,6 +496,14 @@ def main():
     if "--kangaroo" in sys.argv:
         rest = [a for a in sys.argv[1:] if not a.startswith("--")]
         print(json.dumps(analyse_herd(rest[0] if rest else ASM), indent=1))
+        return
+    if "--splitkey" in sys.argv:
+        rest = [a for a in sys.argv[1:] if not a.startswith("--")]
+        print(json.dumps(analyse_splitkey(rest[0] if rest else ASM), indent=1))
+        return
+    if "--compare" in sys.argv:
+        rest = [a for a in sys.argv[1:] if not a.startswith("--")]
+        print(json.dumps(compare(rest[0], rest[1] if len(rest) > 1 else ASM), indent=1))
         return
     if "--all" in sys.argv:
         rest = [a for a in sys.argv[1:] if not a.startswith("--")]
