@@ -21,6 +21,7 @@
 // offset B = C, offset B+1+i = C + G_i.
 #pragma once
 #include "bloom.h"
+#include "emit33.h"
 #include "hash160.h"
 #include "keccak.h"
 #include "pub_emit.h"
@@ -320,6 +321,35 @@ __device__ __forceinline__ void check_point(const add_args& a, cand_queues* q, b
       eth_address(h, xs, ys);
       filter_check<true, PREFIX>(a, q, live, off, h, e, 3);
     }
+  }
+}
+
+// check_point<true, false, false, ENDO> for the walk kernels (k_add<true, false, ENDO>): the same hashes, probes and records by emit33.h's
+// shorter way - limbs to message words, y for its parity alone, probe 0 from RIPEMD-160's native words, the h160_t byte order only for
+// what is parked.  ENDO: the images in check_point's numbering.  x: magnitude <= 4, y: magnitude <= 3.
+template <bool ENDO>
+__device__ __forceinline__ void check_point33(const add_args& a, cand_queues* q, bool live, const fe& x, const fe& y, u64 off) {
+  u32 xw[ENDO ? 3 : 1][9];
+  if (ENDO) {
+    const u32 bw[8] = FE_BETA1_W;
+    const fe bx = fe_mul(x, fe_from_words(bw));  // magnitude 1
+    const fe b2x = fe_neg(fe_add(x, bx), 5);     // beta^2 = -1 - beta; magnitude 6
+    emit33_xwords(xw[1], bx);
+    emit33_xwords(xw[ENDO ? 2 : 0], b2x);
+  }
+  emit33_xwords(xw[0], x);
+  const u32 par = emit33_parity(y);
+  const int nvar = ENDO ? 6 : 1;
+#pragma unroll 1
+  for (int e = 0; e < nvar; ++e) {
+    u32 w[9], o[5], h[5];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) w[i] = ENDO ? (e < 2 ? xw[0][i] : (e < 4 ? xw[1][i] : xw[ENDO ? 2 : 0][i])) : xw[0][i];
+    w[0] |= (0x02u | ((par ^ (u32)e) & 1u)) << 24;  // parity(-y) = !parity(y): p is odd, y != 0
+    emit33_hash(o, w);
+    const bool pass = live && emit33_probe0(a.bloom, o);
+    emit33_h160(h, o);
+    cand_push<false>(a, q, pass, off, h, (u32)e | (1u << 8));
   }
 }
 

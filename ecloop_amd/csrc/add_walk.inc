@@ -133,7 +133,8 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
 #elif defined(ECL_WALK_PREFIX)
           check_point<A33, A65, false, ENDO, ETH, true>(a, &q, live, px, py, off);
 #else
-          check_point<A33, A65, ECL_WALK_P2SH, ENDO, ETH>(a, &q, live, px, py, off);
+          if constexpr (A33 && !A65 && !ECL_WALK_P2SH && !ETH) check_point33<ENDO>(a, &q, live, px, py, off);
+          else check_point<A33, A65, ECL_WALK_P2SH, ENDO, ETH>(a, &q, live, px, py, off);
 #endif
         }
       }

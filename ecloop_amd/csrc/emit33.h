@@ -1,0 +1,109 @@
+// emit33.h — what the addr33-only add kernels (k_add<true, false, ENDO>) do with a walked point: from the raw limbs of (x, y) to the
+// probe of the filter with no representation in between that the result does not need.  Same hashes, same probe, same records as
+// check_point's general path (add_kernel.h: fe_normalize + fe_to_words + hash160_33 + bloom_stage1), bit for bit; the other modes keep
+// that path.  What is left out:
+//   * x goes from its carried limbs straight to the nine SHA-256 message words (prefix byte, x, pad): the 33-byte message is the
+//     number (prefix 2^256 + x) 2^24 + 0x800000 in big-endian words, so limb i sits at bit 29 i + 24 and every word is two limbs, one
+//     field extract and one shift-or.  The carry pass keeps the carried-out bits in place (the extract and the shift drop them), so no
+//     limb is masked, and no 8 x 32 canonical words are formed on the way;
+//   * the canonical residue differs from the weakly normalised one only when limb 8 comes out at 2^24 - 1 or above (fe_weak_ge_p needs
+//     n[8] == FE_TOP or bit 24): one compare per key selects the rare exact path (2^-24 per key) instead of the full test;
+//   * y is needed for one bit.  With S = sum n[i] 2^(29 i) = k 2^256 + r, r < 2^256, the canonical residue is r + k (2^32 + 977) unless
+//     that reaches p, and then its parity is (n[0] ^ k) & 1.  k is read off the top: A = (n[8] << 5) + (n[7] >> 24) is floor(S / 2^227)
+//     or one less (what lies below is (n[7] mod 2^24) 2^203 + n[6] 2^174 + ... < 2^227 (1 + 2^-21) for limbs below 2^32), so
+//     k = A >> 29 unless the low 29 bits of A are all ones; and r + k (2^32 + 977) >= p needs r >= 2^256 - 2^37, i.e. the low 29 bits of
+//     floor(S / 2^227) all ones, i.e. those of A at 2^29 - 2 or above.  That one test (2^-28 per key) selects fe_parity; otherwise no
+//     carry pass at all.  n[8] << 5 needs n[8] < 2^27: y has magnitude <= 3 here;
+//   * probe 0's index, a[0] << 24 | a[1] >> 24 of the h160_t words (bloom.h), is byte selections of RIPEMD-160's native chaining
+//     words: one v_perm_b32 and one and-or per half, instead of four byte swaps and the 64-bit shifts.  The h160_t byte order is applied
+//     where a record is parked in the ring (cand_push), not before.
+#pragma once
+#include "bloom.h"
+#include "hash160.h"
+
+// D = bytes of {hi, lo} by selector (v_perm_b32: selector byte 0..3 = byte of lo, 4..7 = byte of hi)
+H_FN u32 emit33_perm(u32 hi, u32 lo, u32 sel) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_perm(hi, lo, sel);
+#else
+  const u64 v = (u64)hi << 32 | lo;
+  u32 r = 0;
+  for (int i = 0; i < 4; ++i) r |= (u32)((v >> (8 * ((sel >> (8 * i)) & 7u))) & 0xFFu) << (8 * i);
+  return r;
+#endif
+}
+
+// bits [off, off + width) of x as an opaque value: one v_bfe_u32, and the word it goes into is one v_lshl_or_b32 (left visible, the
+// compiler folds the mask into a three-operand and-or and shifts both limbs of a word separately: three instructions per word)
+H_FN u32 emit33_bfe(u32 x, u32 off, u32 width) {
+  u32 r = (x >> off) & ((1u << width) - 1u);
+  FE_HIDE24(r);
+  return r;
+}
+
+// fe_normalize_weak's carry pass without the masks: c[i] & FE_M (i < 8) and c[8] are its limbs
+FE_FN void emit33_carry(u32 c[9], const fe& a) {
+  const u32 t = a.n[8] >> 24;
+  c[0] = a.n[0] + t * 0x3D1u;
+  c[1] = a.n[1] + (t << 3) + (c[0] >> 29);
+#pragma unroll
+  for (int i = 2; i < 8; ++i) c[i] = a.n[i] + (c[i - 1] >> 29);
+  c[8] = (a.n[8] & FE_TOP) + (c[7] >> 29);
+}
+// SHA-256 message words 0..8 of the compressed key with x = a (any magnitude <= 7), prefix byte left zero: w[0] = x's top 24 bits
+FE_FN void emit33_xwords(u32 w[9], const fe& a) {
+  u32 c[9];
+  emit33_carry(c, a);
+  if (__builtin_expect(c[8] >= FE_TOP, 0)) {  // the only values fe_weak_ge_p can be true for
+    fe t = a;
+    fe_normalize(t);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) c[i] = t.n[i];
+  }
+  w[0] = c[8];
+  w[1] = emit33_bfe(c[6], 26, 3) | c[7] << 3;
+  w[2] = emit33_bfe(c[5], 23, 6) | c[6] << 6;
+  w[3] = emit33_bfe(c[4], 20, 9) | c[5] << 9;
+  w[4] = emit33_bfe(c[3], 17, 12) | c[4] << 12;
+  w[5] = emit33_bfe(c[2], 14, 15) | c[3] << 15;
+  w[6] = emit33_bfe(c[1], 11, 18) | c[2] << 18;
+  w[7] = emit33_bfe(c[0], 8, 21) | c[1] << 21;
+  w[8] = c[0] << 24 | 0x00800000u;
+}
+// parity of the canonical residue of y, magnitude <= 3 (limb 8 below 2^27, the others below 2^32)
+FE_FN u32 emit33_parity(const fe& y) {
+  const u32 A = (y.n[8] << 5) + (y.n[7] >> 24);
+  if (__builtin_expect((A & FE_M) >= FE_M - 1u, 0)) return fe_parity(y);
+  return (y.n[0] ^ (A >> 29)) & 1u;
+}
+// hash160 of the key whose message words 0..8 are in w (prefix byte in place): RIPEMD-160's chaining words as they come, o[i] =
+// bswap32 of the h160_t word i
+H_FN void emit33_hash(u32 o[5], const u32 w9[9]) {
+  u32 w[16], st[8], x[16];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) w[i] = w9[i];
+#pragma unroll
+  for (int i = 9; i < 15; ++i) w[i] = 0;
+  w[15] = 33 * 8;
+  sha256_init(st);
+  sha256_compress(st, w);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) x[i] = bswap32(st[i]);
+  x[8] = 0x80u;
+#pragma unroll
+  for (int i = 9; i < 16; ++i) x[i] = 0;
+  x[14] = 256u;
+  rmd160_compress_iv(o, x);
+}
+// bloom_index(a, 0) of bloom_words_of(h), h[i] = bswap32(o[i]):
+//   high word (h0 << 24) | (h1 >> 8) | (h2 >> 24), low word (h1 << 24) | (h2 << 8) | (h3 >> 24)
+H_FN u64 emit33_index0(const u32 o[5]) {
+  const u32 hi = emit33_perm(o[0], o[1], 0x07000102u) | (o[2] & 0xFFu);
+  const u32 lo = emit33_perm(o[2], o[3], 0x05060700u) | (o[1] & 0xFF000000u);
+  return (u64)hi << 32 | lo;
+}
+H_FN bool emit33_probe0(const bloom_t& b, const u32 o[5]) { return bloom_bit(b, emit33_index0(o)); }
+H_FN void emit33_h160(u32 h[5], const u32 o[5]) {
+#pragma unroll
+  for (int i = 0; i < 5; ++i) h[i] = bswap32(o[i]);
+}

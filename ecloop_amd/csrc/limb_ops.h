@@ -8,6 +8,7 @@
 // documented magnitude of what comes back (tests/limb_cases.py lists the magnitudes beside each operation).
 #pragma once
 #include "ec.h"
+#include "emit33.h"
 #include "pub_emit.h"
 
 #define LIMB_IN 6   /* input elements per case */
@@ -37,7 +38,10 @@ enum {
   LIMB_PUB_PAIR_X = 23,   // pub_pair_x(out0, out1, X = in0, Y = in1, gx = in2, gy = in3, invk = in4)
   LIMB_PUB_ENDO_X = 24,   // pub_endo_x(out0, out1, in0)
   LIMB_PUB_WORDS20 = 25,  // out0.n[0..4] = pub_words20(in0)
-  LIMB_OPS = 26
+  // the addr33-only emit path of the add kernels (emit33.h), x = in0 (magnitude <= 4), y = in1 (magnitude <= 3)
+  LIMB_EMIT33 = 26,       // out0 = the nine SHA-256 message words (prefix byte in place), out1.n[0..4] = the h160_t words of the hash160,
+                          // out1.n[5], n[6] = probe 0's index (low, high word) from the native words; flag = emit33_parity(y)
+  LIMB_OPS = 27
 };
 
 // outputs an operation does not produce are zero; returns false for an unknown op (nothing else fails)
@@ -110,6 +114,17 @@ FE_FN bool limb_op(int op, const fe in[LIMB_IN], fe out[LIMB_OUT], u32& flag) {
   case LIMB_PUB_PAIR_X: pub_pair_x(out[0], out[1], in[0], in[1], in[2], in[3], in[4]); break;
   case LIMB_PUB_ENDO_X: pub_endo_x(out[0], out[1], in[0]); break;
   case LIMB_PUB_WORDS20: pub_words20(out[0].n, in[0]); break;
+  case LIMB_EMIT33: {
+    u32 o[5];
+    emit33_xwords(out[0].n, in[0]);
+    flag = emit33_parity(in[1]);
+    out[0].n[0] |= (0x02u | flag) << 24;
+    emit33_hash(o, out[0].n);
+    emit33_h160(out[1].n, o);
+    const u64 idx = emit33_index0(o);
+    out[1].n[5] = (u32)idx, out[1].n[6] = (u32)(idx >> 32);
+    break;
+  }
   default: return false;
   }
   return true;
