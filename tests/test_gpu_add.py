@@ -88,19 +88,21 @@ def test_ragged_sizes_against_oracle():
 
 
 def test_centre_equals_jump_point_doubling_path():
-    """start chosen so that one lane's centre coincides with the jump point T*2B*G (tangent fallback)"""
+    """start chosen so that one lane's centre coincides with the jump point T*2B*G (tangent fallback); every line against the oracle"""
     B, T = 8, 256
-    start = (2 * (T - 3) - 1) * B  # centre of group m=3... start + B + m*2B == T*2B  -> m = 2
-    assert (start + B) % (2 * B) == 0
-    nkeys = 2 * B * T * 2  # two groups per lane so the jump is exercised
+    start = (2 * (T - 3) - 1) * B  # the centre of lane m is start + B + m*2B = 2B (T - 3 + m): lane 3's is T*2B, the jump point's scalar
+    assert (start + B) % (2 * B) == 0 and start + B + 3 * 2 * B == T * 2 * B
+    nkeys = 2 * B * T * 2  # two groups per lane so the jump is exercised: lane 3's second group descends from the tangent
     flt = orc.OrcFilter(bloom_words=ONES)
     lines = lines_of(dev_dump(start, nkeys, geometry=(B, T)), start)
-    xs = {}
     for l in lines[:: max(1, len(lines) // 300)] + lines[-64:]:
         k = int(l.split("\t")[2], 16)
         x, y = orc.point_of(k)
         assert l.split("\t")[1] == orc.hex160(orc.hash160(x, y, True)), hex(k)
     assert len(lines) == nkeys
+    rc, out, n, _, hashed = orc.add_range(flt, start, start + nkeys, verify=False, threads=4, cap=nkeys)  # the four covering 2048-key groups
+    assert rc == 0 and n == hashed == nkeys == 4 * 2048
+    assert lines == sorted(orc.found_lines(out, n))  # all 8192 lines: key and hash
 
 
 def test_lane_centres_from_the_table_of_multiples_and_its_exceptions():

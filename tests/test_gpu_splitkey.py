@@ -5,8 +5,8 @@ call over [a, a + n) must equal, field for field, those of the plain prefix cont
 must equal the oracle's hashes of those keys (tests/orc.py; Ethereum: tests/eth_ref.py) filtered by tests/prefix_ref.py's membership.  The
 tables are built as tests/test_gpu_prefix.py builds them (its table_around), around oracle hashes.
 
-Ethereum at n = 2^17 + 3 with -endo is 786 450 Keccak-256 digests, minutes in eth_ref's pure Python: keccak_many below is eth_ref's sponge
-written over numpy arrays, and eth_ref itself stays the reference - every record the oracle set keeps (every expected hit) and a fixed
+Ethereum at n = 2^17 + 3 with -endo is 786 450 Keccak-256 digests, minutes in eth_ref's pure Python: eth_ref.keccak_many is the same sponge
+written over numpy arrays, and eth_ref's pure-Python one stays the reference - every record the oracle set keeps (every expected hit) and a fixed
 sample of the others are recomputed with eth_ref.eth_words and compared.
 
 Every GPU-using subprocess runs under its own time limit."""
@@ -22,6 +22,7 @@ import pytest
 import eth_ref
 import orc
 import prefix_ref as R
+from eth_ref import keccak_many
 from test_gpu_prefix import keys_of, table_around, table_of
 
 pytestmark = pytest.mark.gpu
@@ -99,40 +100,6 @@ def consecutive_points(k0, n):
         out.extend(res)
         base += m + 1
     return out
-
-
-def keccak_many(msgs):
-    """Keccak-256 (pad 0x01, rate 136) of n messages of 64 bytes, (n, 64) uint8 -> (n, 32) uint8: eth_ref.keccak_f over arrays, in pieces that
-    stay in cache"""
-    n = len(msgs)
-    out = np.zeros((n, 4), np.uint64)
-    lanes = np.ascontiguousarray(msgs).view("<u8").reshape(n, 8)
-    for at in range(0, n, 1 << 14):
-        blk = lanes[at:at + (1 << 14)]
-        m = len(blk)
-        a = [[np.zeros(m, np.uint64) for _ in range(5)] for _ in range(5)]
-        for i in range(8):
-            a[i % 5][i // 5] = blk[:, i].copy()
-        a[8 % 5][8 // 5] = np.full(m, 0x01, np.uint64)
-        a[16 % 5][16 // 5] = np.full(m, 0x80 << 56, np.uint64)
-
-        def rotl(v, r):
-            r %= 64
-            return (v << np.uint64(r)) | (v >> np.uint64(64 - r)) if r else v
-        for rnd in range(24):
-            c = [a[x][0] ^ a[x][1] ^ a[x][2] ^ a[x][3] ^ a[x][4] for x in range(5)]
-            d = [c[(x - 1) % 5] ^ rotl(c[(x + 1) % 5], 1) for x in range(5)]
-            b = [[None] * 5 for _ in range(5)]
-            for x in range(5):
-                for y in range(5):
-                    b[y][(2 * x + 3 * y) % 5] = rotl(a[x][y] ^ d[x], eth_ref.RHO[x][y])
-            for x in range(5):
-                for y in range(5):
-                    a[x][y] = b[x][y] ^ (~b[(x + 1) % 5][y] & b[(x + 2) % 5][y])
-            a[0][0] = a[0][0] ^ np.uint64(eth_ref.RC[rnd])
-        for i in range(4):
-            out[at:at + m, i] = a[i % 5][i // 5]
-    return out.view(np.uint8).reshape(n, 32)
 
 
 @functools.lru_cache(maxsize=None)
