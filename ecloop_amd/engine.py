@@ -396,7 +396,17 @@ class KeySearch:
         for at in range(0, len(scalars), chunk):
             ks = scalars[at : at + chunk]
             c = max(cap, 2 * len(ks))
-            raw, total = self.dev.mul_batch(ks, cap=c)
+            while True:
+                raw, total = self.dev.mul_batch(ks, cap=c)
+                if total <= c:
+                    break
+                # more records than the buffer holds (a dense filter, three types per scalar): as in add_keys - read what the device
+                # kept, and repeat the call with a buffer that fits only if it kept less than the call produced
+                rest = self.dev.fetch_found(c, total - c)
+                if len(rest) == total - c:
+                    raw = np.concatenate([raw, rest])
+                    break
+                c = total
             new = []
             for r in raw:
                 if self.flt.confirm(r["h160"]):

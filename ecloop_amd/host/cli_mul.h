@@ -97,25 +97,29 @@ static void sha256_stream(u32 st[8], const u8 *msg, size_t len) {
   if (total == 128) sha256_block(st, tail + 64);
 }
 
-/* hit records of one device call: the buffer holds MUL_HITS_CAP of them; a call that reports more (ECL_E_OVERFLOW: a dense filter) has
-   kept the rest on the device, fetched here */
+/* hit records of one device call: the buffer starts with room for MUL_HITS_CAP of them.  A call that reports more (ECL_E_OVERFLOW: a dense
+   filter) has kept up to max(cap, 2^20) of them on the device, and they are fetched here.  A call with more hits than the device keeps -
+   2^19 + 1 scalars of `-a cu` through an all-ones filter are enough, and a batch is up to 2^24 scalars - has to be run again with a
+   buffer that fits (include/ecloop_hip.h, ecl_hip_fetch_found; add_worker in cli_add.h does the same): -> true, *cap is then the call's count */
 #define MUL_HITS_CAP (1u << 16)
-static ecl_found *mul_collect(run_t *run, int g, int rc, ecl_found *buf, u32 cap, u32 cnt, const char *what) {
+static bool mul_collect(run_t *run, int g, int rc, ecl_found **buf, u32 *cap, u32 cnt, const char *what) {
   if (rc == ECL_E_OVERFLOW) {
-    u32 got = 0;
-    buf = realloc(buf, sizeof(ecl_found) * cnt);
-    rc = ecl_hip_fetch_found(run->dev[g], cap, buf + cap, cnt - cap, &got);
-    if (rc == ECL_OK && got != cnt - cap) rc = ECL_E_OVERFLOW; /* more than the device keeps (2^20): the batch sizes below never get there */
+    u32 had = *cap, got = 0;
+    *cap = cnt, *buf = realloc(*buf, sizeof(ecl_found) * cnt);
+    if (!*buf) { fprintf(stderr, "out of memory for %u hit records\n", cnt); exit(1); }
+    rc = ecl_hip_fetch_found(run->dev[g], had, *buf + had, cnt - had, &got);
+    if (rc == ECL_OK && got != cnt - had) return true;
   }
   if (rc != ECL_OK) die_ecl(run, g, rc, what);
-  return buf;
+  return false;
 }
 static void mul_flush(run_t *run, int g, u64 (*ks)[4], u32 n) {
   if (!n) return;
   u32 cap = n * 2 + 16 < MUL_HITS_CAP ? n * 2 + 16 : MUL_HITS_CAP, cnt = 0;
   ecl_found *buf = malloc(sizeof(ecl_found) * cap);
-  int rc = ecl_hip_mul_batch(run->dev[g], ks, n, buf, cap, &cnt);
-  buf = mul_collect(run, g, rc, buf, cap, cnt, "mul_batch");
+  int rc;
+  do rc = ecl_hip_mul_batch(run->dev[g], ks, n, buf, cap, &cnt);
+  while (mul_collect(run, g, rc, &buf, &cap, cnt, "mul_batch"));
   for (u32 i = 0; i < cnt; ++i) {
     if (!filter_confirms(&run->flt, buf[i].h160)) continue;
     sc pk;
@@ -132,8 +136,9 @@ static void mul_flush_raw(run_t *run, int g, const u8 *text, size_t text_len, co
   if (!n) return;
   u32 cap = n * 2 + 16 < MUL_HITS_CAP ? n * 2 + 16 : MUL_HITS_CAP, cnt = 0;
   ecl_found *buf = malloc(sizeof(ecl_found) * cap);
-  int rc = ecl_hip_mul_batch_raw(run->dev[g], text, (u32)text_len, lines, n, buf, cap, &cnt);
-  buf = mul_collect(run, g, rc, buf, cap, cnt, "mul_batch_raw");
+  int rc;
+  do rc = ecl_hip_mul_batch_raw(run->dev[g], text, (u32)text_len, lines, n, buf, cap, &cnt);
+  while (mul_collect(run, g, rc, &buf, &cap, cnt, "mul_batch_raw"));
   for (u32 i = 0; i < cnt; ++i) {
     if (!filter_confirms(&run->flt, buf[i].h160)) continue;
     const u64 ln = lines[buf[i].key_offset];

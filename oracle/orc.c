@@ -840,6 +840,7 @@ typedef struct mul_many_state {
   const orc_fe *pk;
   u64 n, next;
   u32 *h33, *h65;
+  u64 *px, *py; /* orc_mul_points_many: the affine points themselves, four limbs each */
   u8 *ok;
   pthread_mutex_t lock;
 } mul_many_state;
@@ -871,17 +872,19 @@ static void *mul_many_worker(void *arg) {
         if (inf[i]) memset(st->h65 + 5 * (at + i), 0, 20);
         else orc_hash160_65(st->h65 + 5 * (at + i), cp[i].x, cp[i].y);
       }
+      if (st->px) {
+        if (inf[i]) memset(st->px + 4 * (at + i), 0, 32), memset(st->py + 4 * (at + i), 0, 32);
+        else memcpy(st->px + 4 * (at + i), cp[i].x, 32), memcpy(st->py + 4 * (at + i), cp[i].y, 32);
+      }
     }
   }
   free(cp), free(inf);
   return NULL;
 }
 
-void orc_mul_hash160_many(const orc_fe *pk, uint64_t n, uint32_t *h33, uint32_t *h65, uint8_t *ok, int threads) {
+static void mul_many_run(mul_many_state *stp, int threads) {
   orc_gtable_init();
-  mul_many_state st;
-  memset(&st, 0, sizeof st);
-  st.pk = pk, st.n = n, st.h33 = h33, st.h65 = h65, st.ok = ok;
+  mul_many_state st = *stp;
   pthread_mutex_init(&st.lock, NULL);
   int nt = threads < 1 ? 1 : threads;
   pthread_t *th = (pthread_t *)malloc(nt * sizeof(pthread_t));
@@ -889,4 +892,18 @@ void orc_mul_hash160_many(const orc_fe *pk, uint64_t n, uint32_t *h33, uint32_t 
   for (int i = 0; i < nt; ++i) pthread_join(th[i], NULL);
   free(th);
   pthread_mutex_destroy(&st.lock);
+}
+
+void orc_mul_hash160_many(const orc_fe *pk, uint64_t n, uint32_t *h33, uint32_t *h65, uint8_t *ok, int threads) {
+  mul_many_state st;
+  memset(&st, 0, sizeof st);
+  st.pk = pk, st.n = n, st.h33 = h33, st.h65 = h65, st.ok = ok;
+  mul_many_run(&st, threads);
+}
+
+void orc_mul_points_many(const orc_fe *pk, uint64_t n, uint64_t *x, uint64_t *y, uint8_t *ok, int threads) {
+  mul_many_state st;
+  memset(&st, 0, sizeof st);
+  st.pk = pk, st.n = n, st.px = x, st.py = y, st.ok = ok;
+  mul_many_run(&st, threads);
 }

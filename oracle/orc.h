@@ -111,6 +111,8 @@ int orc_mul_batch(int check33, int check65, const orc_filter *flt, const orc_fe 
    ec_gtable_mul each, one ec_jacobi_grprdc per job, addr33/addr65; main.c:486-540).  h33 / h65: n x 5 words or NULL; ok[i] = 0 for a
    scalar that is 0 (mod n) (no point; hashes zeroed).  `threads` workers pull jobs from one counter. */
 void orc_mul_hash160_many(const orc_fe *pk, uint64_t n, uint32_t *h33, uint32_t *h65, uint8_t *ok, int threads);
+/* the same workers leaving the affine points in place of the hashes: x / y are n x 4 little-endian limbs, zeroed where ok[i] = 0 */
+void orc_mul_points_many(const orc_fe *pk, uint64_t n, uint64_t *x, uint64_t *y, uint8_t *ok, int threads);
 
 /* calc_priv (main.c:267-276) */
 void orc_calc_priv(orc_fe pk, const orc_fe start, const orc_fe stride, uint64_t off, uint8_t endo);

@@ -167,6 +167,28 @@ def mul_hash160_many(K, a33=True, a65=False, threads=None):
     return h33, h65, ok
 
 
+def mul_points_many(K, threads=None):
+    """the affine point k G of every scalar of K ((n, 4) uint64) by the workers of mul_hash160_many (ec_gtable_mul, one grprdc per
+    2048-scalar job) -> (x, y, ok): (n, 4) uint64 little-endian limbs each, zero where ok[i] = 0 (k = 0 mod n)"""
+    K = np.ascontiguousarray(K, dtype=np.uint64)
+    n = len(K)
+    x, y, ok = np.zeros((n, 4), np.uint64), np.zeros((n, 4), np.uint64), np.zeros(n, np.uint8)
+    if threads is None:
+        threads = max(1, min(len(os.sched_getaffinity(0)), 128))
+    lib().orc_mul_points_many(C.c_void_p(K.ctypes.data), C.c_uint64(n), C.c_void_p(x.ctypes.data), C.c_void_p(y.ctypes.data),
+                              C.c_void_p(ok.ctypes.data), C.c_int(threads))
+    return x, y, ok
+
+
+def blf_has_many(words, h):
+    """the oracle's filter test (blf_has, utils.c:300-326) of every hash of h ((n, 5) uint32) on the bloom words -> (n,) bool"""
+    w = np.ascontiguousarray(words, dtype=np.uint64)
+    h = np.ascontiguousarray(h, dtype=np.uint32).reshape(-1, 5)
+    hit = np.zeros(len(h), np.uint8)
+    lib().orc_blf_has_many(C.c_void_p(w.ctypes.data), C.c_uint64(len(w)), C.c_void_p(h.ctypes.data), C.c_uint64(len(h)), C.c_void_p(hit.ctypes.data))
+    return hit.astype(bool)
+
+
 def sn_from_hex(s):
     r = FE()
     lib().orc_sn_from_hex(r, s.encode())

@@ -844,6 +844,50 @@ def test_mul_raw_fans_out_over_device_threads(cli, tmp_path):
     assert counts(status) == (400, 2 * len(fill) + 2 * len(targets))
 
 
+@pytest.mark.gpu
+def test_mul_device_calls_with_more_hits_than_the_device_keeps(cli, tmp_path):
+    """`mul -a cu` through an all-ones filter: 2^19 + 8 lines are one device call with 2^20 + 16 hits, more than the 2^20 records the device
+    keeps of a call, so fetching the overflow falls short and the call has to be repeated with a buffer that fits (include/ecloop_hip.h;
+    the reference prints every hit).  Once on a file of hex lines, once with -raw on short pass phrases; every input line's two found lines
+    must be there, equal to the ORACLE's (orc.mul_hash160_many), compared as sorted arrays of the 113-byte found lines."""
+    import orc
+    n = (1 << 19) + 8
+    hexd = np.frombuffer(b"0123456789abcdef", dtype=np.uint8)
+
+    def hex_of(b):  # (n, m) uint8 -> (n, 2m) uint8 hex digits
+        out = np.empty((len(b), 2 * b.shape[1]), np.uint8)
+        out[:, 0::2], out[:, 1::2] = hexd[b >> 4], hexd[b & 15]
+        return out
+
+    def expected(b):  # b: (n, 32) uint8, the private keys' big-endian bytes -> the sorted found lines
+        h33, h65, ok = orc.mul_hash160_many(np.ascontiguousarray(b[:, ::-1]).view("<u8").reshape(n, 4), True, True)
+        assert ok.all()
+        lines = np.empty((2 * n, 113), np.uint8)
+        for at, label, hh in ((0, b"addr33", h33), (n, b"addr65", h65)):
+            part = lines[at:at + n]
+            part[:, :6], part[:, 6], part[:, 47], part[:, 112] = np.frombuffer(label, np.uint8), 9, 9, 10
+            part[:, 7:47], part[:, 48:112] = hex_of(hh.astype(">u4").view(np.uint8).reshape(n, 20)), hex_of(b)
+        return np.sort(lines.view("S113").ravel())
+
+    flt = str(tmp_path / "ones.blf")
+    write_blf(flt, np.full(64, 0xFFFFFFFFFFFFFFFF, np.uint64))
+    keys = np.frombuffer(np.random.default_rng(909).bytes(n * 32), dtype=np.uint8).reshape(n, 32)
+    text = np.empty((n, 65), np.uint8)
+    text[:, :64], text[:, 64] = hex_of(keys), 10
+    text.tofile(str(tmp_path / "keys.txt"))
+    phrases = [b"pass phrase %d" % i for i in range(n)]
+    (tmp_path / "phrases.txt").write_bytes(b"\n".join(phrases) + b"\n")
+    digests = np.frombuffer(b"".join(hashlib.sha256(p).digest() for p in phrases), dtype=np.uint8).reshape(n, 32)
+    for name, extra, b in (("keys", [], keys), ("phrases", ["-raw"], digests)):
+        out = str(tmp_path / (name + ".found"))
+        pr = subprocess.run(["timeout", "-k", "10", "300", cli, "mul", "-f", flt, "-a", "cu"] + extra + ["-q", "-o", out],
+                            stdin=open(str(tmp_path / (name + ".txt")), "rb"), stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+        assert pr.returncode == 0, (name, pr.stderr.decode(errors="replace")[-2000:])
+        raw = np.fromfile(out, np.uint8)
+        assert len(raw) == 2 * n * 113, (name, len(raw))
+        assert np.array_equal(np.sort(raw.reshape(-1, 113).view("S113").ravel()), expected(b)), name
+
+
 def test_scan_plan_matches_the_oracles_job_loop(cli):
     """the hidden `plan` command prints what scan_plan() derives from -r / -d: keys hashed and status counter of
     cmd_add (main.c:405-454).  Compared with the oracle, which RUNS the reference's job loop (counter stepping by

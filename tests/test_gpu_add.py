@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import orc
+from mul_ref import digit_edge_scalars as _digit_edge_scalars  # (shared with tests/test_gpu_mul_types.py; the same scalars as before)
 from synth import synth_bloom_words
 
 pytestmark = pytest.mark.gpu
@@ -438,28 +439,6 @@ def _mul_all_against_the_oracle(d, K):
         assert np.array_equal(part["key_offset"][order], want.astype(np.uint64))
         assert np.array_equal(part["h160"][order], hh[want])
     return cnt.value // (2 if both else 1)
-
-
-def _digit_edge_scalars(rng, n, W):
-    """random 256-bit scalars plus the digit patterns a W-bit window table can get wrong: every digit at its maximum,
-    a single digit per window (1 and the maximum, the last window's narrower maximum included), 2^256 - 1, n - 1; and what the
-    signed recoding turns on: a digit of exactly 2^(W-1) (the largest that stays positive), 2^(W-1) + 1 (the first that becomes
-    negative with a carry), those in every window at once, a carry that runs through windows of all ones into the last row"""
-    K = rng.integers(0, 1 << 63, (n, 4), dtype=np.int64).astype(np.uint64) * np.uint64(2) + rng.integers(0, 2, (n, 4), dtype=np.int64).astype(np.uint64)
-    special = [(1 << 256) - 1, orc.N - 1, orc.N + 1, 1, 2]
-    nwin = (256 + W - 1) // W
-    for w in range(nwin):
-        width = min(W, 256 - W * w)
-        special += [1 << (W * w), ((1 << width) - 1) << (W * w), (((1 << width) - 1) << (W * w)) | 1]
-        if width == W:
-            half = 1 << (W - 1)
-            special += [half << (W * w), (half + 1) << (W * w), ((half + 1) << (W * w)) | (((1 << 256) - 1) >> (W * (w + 1)) << (W * (w + 1)))]
-    M256 = (1 << 256) - 1
-    special += [sum((1 << (W - 1)) << (W * w) for w in range(nwin)) & M256, sum(((1 << (W - 1)) + 1) << (W * w) for w in range(nwin)) & M256,
-                sum(((1 << (W - 1)) - 1) << (W * w) for w in range(nwin)) & M256]
-    for i, v in enumerate(special):
-        K[i] = [(v >> (64 * j)) & 0xFFFFFFFFFFFFFFFF for j in range(4)]
-    return K
 
 
 @pytest.mark.parametrize("W", [8, 13, 14, 16, 18, 20, 22, 24, 26, 27, 29])
