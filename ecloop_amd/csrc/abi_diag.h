@@ -8,10 +8,10 @@ extern "C" int ecl_hip_diag_fe(ecl_hip* h, int op, const uint64_t (*a)[4], const
   if (!h || !a || !r || n == 0 || op < 0 || op > 11) return ECL_E_ARG;
   HIPCHK(h, hipSetDevice(h->dev));
   size_t bytes = (size_t)n * 32;
-  dbuf<u32> da, db, dr;
-  HIPCHK(h, hipMalloc(&da.p, bytes));
-  HIPCHK(h, hipMalloc(&db.p, bytes));
-  HIPCHK(h, hipMalloc(&dr.p, bytes));
+  devbuf<u32> da, db, dr;
+  HIPCHK(h, da.grow((size_t)n * 8));
+  HIPCHK(h, db.grow((size_t)n * 8));
+  HIPCHK(h, dr.grow((size_t)n * 8));
   HIPCHK(h, hipMemcpy(da.p, a, bytes, hipMemcpyHostToDevice));  // little-endian u64 limbs == u32 word pairs
   HIPCHK(h, hipMemcpy(db.p, b ? b : a, bytes, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_diag_fe, dim3((n + 63) / 64), dim3(64), 0, h->stream, op, da.p, db.p, dr.p, n);
@@ -26,10 +26,10 @@ extern "C" int ecl_hip_diag_limbs(ecl_hip* h, int op, const uint32_t (*in)[LIMB_
   if (!h || !in || !out || !flag || n == 0 || op < 0 || op >= LIMB_OPS) return ECL_E_ARG;
   HIPCHK(h, hipSetDevice(h->dev));
   const size_t bin = (size_t)n * LIMB_IN * FE_LIMBS * 4, bout = (size_t)n * LIMB_OUT * FE_LIMBS * 4;
-  dbuf<u32> di, dout, df;
-  HIPCHK(h, hipMalloc(&di.p, bin));
-  HIPCHK(h, hipMalloc(&dout.p, bout));
-  HIPCHK(h, hipMalloc(&df.p, (size_t)n * 4));
+  devbuf<u32> di, dout, df;
+  HIPCHK(h, di.grow(bin / 4));
+  HIPCHK(h, dout.grow(bout / 4));
+  HIPCHK(h, df.grow(n));
   HIPCHK(h, hipMemcpy(di.p, in, bin, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_diag_limbs, dim3((unsigned)(((u64)n + 63) / 64)), dim3(64), 0, h->stream, op, di.p, dout.p, df.p, n);
   HIPCHK(h, hipGetLastError());
@@ -43,11 +43,11 @@ extern "C" int ecl_hip_diag_mulg(ecl_hip* h, const uint64_t (*k)[4], uint64_t (*
                                  uint32_t n) {
   if (!h || !k || !x || !y || n == 0) return ECL_E_ARG;
   HIPCHK(h, hipSetDevice(h->dev));
-  dbuf<u32> dk, dout;
-  dbuf<u8> dok;
-  HIPCHK(h, hipMalloc(&dk.p, (size_t)n * 32));
-  HIPCHK(h, hipMalloc(&dout.p, (size_t)n * 64));
-  HIPCHK(h, hipMalloc(&dok.p, n));
+  devbuf<u32> dk, dout;
+  devbuf<u8> dok;
+  HIPCHK(h, dk.grow((size_t)n * 8));
+  HIPCHK(h, dout.grow((size_t)n * 16));
+  HIPCHK(h, dok.grow(n));
   HIPCHK(h, hipMemcpy(dk.p, k, (size_t)n * 32, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_mul_g, dim3((n + 63) / 64), dim3(64), 0, h->stream, dk.p, dout.p, dok.p, n);
   HIPCHK(h, hipGetLastError());
@@ -68,11 +68,11 @@ extern "C" int ecl_hip_diag_hash160(ecl_hip* h, const uint64_t (*x)[4], const ui
                                     uint32_t (*h65)[5], uint32_t n) {
   if (!h || !x || !y || !h33 || !h65 || n == 0) return ECL_E_ARG;
   HIPCHK(h, hipSetDevice(h->dev));
-  dbuf<u32> dx, dy, d33, d65;
-  HIPCHK(h, hipMalloc(&dx.p, (size_t)n * 32));
-  HIPCHK(h, hipMalloc(&dy.p, (size_t)n * 32));
-  HIPCHK(h, hipMalloc(&d33.p, (size_t)n * 20));
-  HIPCHK(h, hipMalloc(&d65.p, (size_t)n * 20));
+  devbuf<u32> dx, dy, d33, d65;
+  HIPCHK(h, dx.grow((size_t)n * 8));
+  HIPCHK(h, dy.grow((size_t)n * 8));
+  HIPCHK(h, d33.grow((size_t)n * 5));
+  HIPCHK(h, d65.grow((size_t)n * 5));
   HIPCHK(h, hipMemcpy(dx.p, x, (size_t)n * 32, hipMemcpyHostToDevice));
   HIPCHK(h, hipMemcpy(dy.p, y, (size_t)n * 32, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_diag_hash, dim3((n + 63) / 64), dim3(64), 0, h->stream, dx.p, dy.p, d33.p, d65.p, n);
@@ -85,18 +85,18 @@ extern "C" int ecl_hip_diag_hash160(ecl_hip* h, const uint64_t (*x)[4], const ui
 
 extern "C" int ecl_hip_bloom_insert(ecl_hip* h, const uint32_t (*h160)[5], uint64_t n) {
   if (!h || (!h160 && n) || (h->flags & ECL_PREFIX)) return ECL_E_ARG;
-  if (!h->d_bloom) return ECL_E_NOBLOOM;
+  if (!h->d_bloom.p) return ECL_E_NOBLOOM;
   if (n == 0) return ECL_OK;
   la_leave(h), h->la_key_valid = false;  // the resident filter is no longer the one that was uploaded: no shared look-ahead on it
   HIPCHK(h, hipSetDevice(h->dev));
   const u64 chunk = 1ull << 24;  // 320 MB of hashes per upload
-  dbuf<u32> dh;
-  HIPCHK(h, hipMalloc(&dh.p, (size_t)(n < chunk ? n : chunk) * 20));
+  devbuf<u32> dh;
+  HIPCHK(h, dh.grow((size_t)(n < chunk ? n : chunk) * 5));
   for (u64 at = 0; at < n; at += chunk) {
     u64 m = n - at < chunk ? n - at : chunk;
     HIPCHK(h, hipMemcpy(dh.p, h160 + at, (size_t)m * 20, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_bloom_insert, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, h->stream,
-                       bloom_make(h->d_bloom, h->bloom_words), h->d_bloom, dh.p, m);
+                       bloom_make(h->d_bloom.p, h->bloom_words), h->d_bloom.p, dh.p, m);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));
   }
@@ -106,29 +106,29 @@ extern "C" int ecl_hip_bloom_insert(ecl_hip* h, const uint32_t (*h160)[5], uint6
 extern "C" int ecl_hip_bloom_insert_count(ecl_hip* h, const uint32_t (*h160)[5], uint64_t n, uint64_t* added) {
   if (!h || (!h160 && n) || !added || (h->flags & ECL_PREFIX)) return ECL_E_ARG;
   *added = 0;
-  if (!h->d_bloom) return ECL_E_NOBLOOM;
+  if (!h->d_bloom.p) return ECL_E_NOBLOOM;
   if (n == 0) return ECL_OK;
   if (h->bloom_words >= (1ull << (64 - BLF_CHUNK_LOG2 - 6))) return ECL_E_ARG;  // bit position must fit 44 bits (2 TB filter)
   la_leave(h), h->la_key_valid = false;
   HIPCHK(h, hipSetDevice(h->dev));
   const u64 chunk = 1ull << BLF_CHUNK_LOG2;
-  dbuf<u32> dh;
-  dbuf<u64> tab;
-  dbuf<unsigned long long> cnt;
-  HIPCHK(h, hipMalloc(&dh.p, (size_t)(n < chunk ? n : chunk) * 20));
-  HIPCHK(h, hipMalloc(&tab.p, sizeof(u64) << BLF_TAB_LOG2));
-  HIPCHK(h, hipMalloc(&cnt.p, sizeof(unsigned long long)));
+  devbuf<u32> dh;
+  devbuf<u64> tab;
+  devbuf<unsigned long long> cnt;
+  HIPCHK(h, dh.grow((size_t)(n < chunk ? n : chunk) * 5));
+  HIPCHK(h, tab.grow((size_t)1 << BLF_TAB_LOG2));
+  HIPCHK(h, cnt.grow(1));
   HIPCHK(h, hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), h->stream));
-  const bloom_t b = bloom_make(h->d_bloom, h->bloom_words);
+  const bloom_t b = bloom_make(h->d_bloom.p, h->bloom_words);
   for (u64 at = 0; at < n; at += chunk) {
     const u32 m = (u32)(n - at < chunk ? n - at : chunk);
     HIPCHK(h, hipMemcpyAsync(dh.p, h160 + at, (size_t)m * 20, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemsetAsync(tab.p, 0xFF, sizeof(u64) << BLF_TAB_LOG2, h->stream));
     hipLaunchKernelGGL(k_blf_claim, dim3((m + 255) / 256), dim3(256), 0, h->stream, b, dh.p, m, tab.p);
     HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(k_blf_count_and_set, dim3((m + 255) / 256), dim3(256), 0, h->stream, b, h->d_bloom, dh.p, m, tab.p, cnt.p);
+    hipLaunchKernelGGL(k_blf_count_and_set, dim3((m + 255) / 256), dim3(256), 0, h->stream, b, h->d_bloom.p, dh.p, m, tab.p, cnt.p);
     HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(k_bloom_insert, dim3((m + 255) / 256), dim3(256), 0, h->stream, b, h->d_bloom, dh.p, (u64)m);
+    hipLaunchKernelGGL(k_bloom_insert, dim3((m + 255) / 256), dim3(256), 0, h->stream, b, h->d_bloom.p, dh.p, (u64)m);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));  // the host buffer slice is free again; next chunk sees these bits
   }
@@ -140,27 +140,27 @@ extern "C" int ecl_hip_bloom_insert_count(ecl_hip* h, const uint32_t (*h160)[5],
 
 extern "C" int ecl_hip_get_bloom(ecl_hip* h, uint64_t* bits, uint64_t nwords) {
   if (!h || !bits || (h->flags & ECL_PREFIX)) return ECL_E_ARG;
-  if (!h->d_bloom) return ECL_E_NOBLOOM;
+  if (!h->d_bloom.p) return ECL_E_NOBLOOM;
   if (nwords != h->bloom_words) return ECL_E_ARG;
   HIPCHK(h, hipSetDevice(h->dev));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  HIPCHK(h, hipMemcpy(bits, h->d_bloom, nwords * sizeof(u64), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(bits, h->d_bloom.p, nwords * sizeof(u64), hipMemcpyDeviceToHost));
   return ECL_OK;
 }
 
 extern "C" int ecl_hip_diag_bloom(ecl_hip* h, const uint32_t (*h160)[5], uint8_t* hit, uint32_t n) {
   if (!h || !h160 || !hit || n == 0) return ECL_E_ARG;
-  if (!h->d_bloom) return ECL_E_NOBLOOM;
+  if (!h->d_bloom.p) return ECL_E_NOBLOOM;
   HIPCHK(h, hipSetDevice(h->dev));
-  dbuf<u32> dh;
-  dbuf<u8> dhit;
-  HIPCHK(h, hipMalloc(&dh.p, (size_t)n * 20));
-  HIPCHK(h, hipMalloc(&dhit.p, n));
+  devbuf<u32> dh;
+  devbuf<u8> dhit;
+  HIPCHK(h, dh.grow((size_t)n * 5));
+  HIPCHK(h, dhit.grow(n));
   HIPCHK(h, hipMemcpy(dh.p, h160, (size_t)n * 20, hipMemcpyHostToDevice));
   if (h->flags & ECL_PREFIX)  // the device's two-stage prefix test on the given values
     hipLaunchKernelGGL(k_diag_prefix, dim3((n + 63) / 64), dim3(64), 0, h->stream, prefix_of(h), dh.p, dhit.p, n);
   else
-    hipLaunchKernelGGL(k_diag_bloom, dim3((n + 63) / 64), dim3(64), 0, h->stream, bloom_make(h->d_bloom, h->bloom_words),
+    hipLaunchKernelGGL(k_diag_bloom, dim3((n + 63) / 64), dim3(64), 0, h->stream, bloom_make(h->d_bloom.p, h->bloom_words),
                        dh.p, dhit.p, n);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -171,9 +171,9 @@ extern "C" int ecl_hip_diag_bloom(ecl_hip* h, const uint32_t (*h160)[5], uint8_t
 extern "C" int ecl_hip_diag_bloom_mod(ecl_hip* h, uint64_t nwords, const uint64_t* x, uint64_t* r, uint32_t n) {
   if (!h || !x || !r || n == 0 || nwords == 0 || nwords >= (1ull << 58)) return ECL_E_ARG;
   HIPCHK(h, hipSetDevice(h->dev));
-  dbuf<u64> dx, dr;
-  HIPCHK(h, hipMalloc(&dx.p, (size_t)n * 8));
-  HIPCHK(h, hipMalloc(&dr.p, (size_t)n * 8));
+  devbuf<u64> dx, dr;
+  HIPCHK(h, dx.grow(n));
+  HIPCHK(h, dr.grow(n));
   HIPCHK(h, hipMemcpy(dx.p, x, (size_t)n * 8, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_diag_bloom_mod, dim3((n + 63) / 64), dim3(64), 0, h->stream, bloom_make(nullptr, nwords), dx.p, dr.p, n);
   HIPCHK(h, hipGetLastError());
@@ -239,16 +239,17 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   const u32 N = 4096, saveB = h->B, saveT = h->Tmax;
   const uint64_t save_cov[3] = {h->cov_requested, h->cov_covered, h->cov_device};  // the caller's totals: "since open" leaves this call out
   const bool saveAuto = h->B_auto;
-  u64* save_bloom = h->d_bloom;
+  // the caller's filter, list and table wait in these three while the context runs the test on its own; swapped back below
+  devbuf<u64> keep_bloom;
+  devbuf<u32> keep_list, keep_tab;
   const u64 save_words = h->bloom_words, save_list_n = h->list_n;
-  const u32 save_prefix_n = h->prefix_n;
-  u32* save_list = h->d_list;
-  h->d_list = nullptr, h->list_n = 0;
+  const u32 save_prefix_n = h->prefix_n, save_tab_B = h->tab_B;
+  keep_bloom.swap(h->d_bloom), keep_list.swap(h->d_list), keep_tab.swap(h->d_tab);
+  h->bloom_words = 0, h->list_n = 0, h->tab_B = 0;
   // ECL_ORIGIN: the same walk from the origin O = 0xdc2a04 G (its x, y from (1)), against the double-and-add kernel's (start + j s + 0xdc2a04) G;
   // ECL_INSERT: the walk sets bits in a zeroed filter, compared with the filter the host builds from the double-and-add kernel's x
   const bool origin = h->flags & ECL_ORIGIN, insert = h->flags & ECL_INSERT;
   std::vector<u64> ones(insert ? 4099 : 64, insert ? 0ull : ~0ull), got_bits(insert ? 4099 : 0);
-  h->d_bloom = nullptr, h->bloom_words = 0;
   h->B = 16, h->Tmax = 256, h->B_auto = false;
   uint64_t start[12] = {0x0123456789abcdefull, 0x1f, 0, 0};
   memcpy(start + 4, x[2], 32), memcpy(start + 8, y[2], 32);
@@ -291,13 +292,12 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   if (h->flags & ECL_PUB)
     for (u32 i = 0; i < N; ++i)
       for (u32 j = 0; j < 5; ++j) rpub[(size_t)i * 5 + j] = (uint32_t)(xs[(size_t)i * 4 + (7 - j) / 2] >> (32 * ((7 - j) & 1)));
-  // restore the caller's state whatever happened
-  if (h->d_bloom) (void)hipFree(h->d_bloom);
-  h->d_bloom = save_bloom, h->bloom_words = save_words, h->prefix_n = save_prefix_n;
-  h->d_list = save_list, h->list_n = save_list_n;
+  // restore the caller's state whatever happened; the test's own filter and table are freed here, not at the end of the function
+  keep_bloom.swap(h->d_bloom), keep_list.swap(h->d_list), keep_tab.swap(h->d_tab);
+  keep_bloom.reset(), keep_tab.reset();
+  h->bloom_words = save_words, h->prefix_n = save_prefix_n, h->list_n = save_list_n, h->tab_B = save_tab_B;
   h->B = saveB, h->Tmax = saveT, h->B_auto = saveAuto;
-  if (h->d_tab) (void)hipFree(h->d_tab);
-  h->d_tab = nullptr, h->tab_B = 0, h->walk_valid = false;
+  h->walk_valid = false;
   h->kernel_ms = 0, h->launches = 0, h->keys = 0, h->setup_ms = 0, h->setups = 0;
   h->cov_requested = save_cov[0], h->cov_covered = save_cov[1], h->cov_device = save_cov[2];
   if (rc != ECL_OK) return rc;

@@ -32,23 +32,18 @@ static int herd_parse(ecl_hip* h, const uint64_t blk[16], herd_params& p) {
 // table and starts of a new herd, queued on h->stream and waited for; the flag word d_counter[6] (zeroed by the caller) comes home in *flags
 static int herd_build(ecl_hip* h, const herd_params& p, u32* flags) {
   const u32 H = 1u << p.herd_log2;
-  if (h->herd_cap < H) {
-    if (h->d_herd) HIPCHK(h, hipFree(h->d_herd));
-    h->d_herd = nullptr, h->herd_cap = 0;
-    HIPCHK(h, hipMalloc(&h->d_herd, (size_t)H * 22 * sizeof(u32)));
-    h->herd_cap = H;
-  }
-  if (!h->d_herdtab) HIPCHK(h, hipMalloc(&h->d_herdtab, 32 * HERD_TAB_IN * sizeof(u32)));
+  HIPCHK(h, h->d_herd.grow((size_t)H * 22));  // (every launch on the herd was waited for by its call's read-back)
+  HIPCHK(h, h->d_herdtab.grow(32 * HERD_TAB_IN));
   kg_stream st = {p.seed};
   kg_u128 s[KG_TABLE];
   kg_table(&st, p.jb, s);
   const u32 chunk = H < HERD_INIT_CHUNK ? H : HERD_INIT_CHUNK, nk = chunk > 32 ? chunk : 32;
-  dbuf<u32> d_k, d_pts, d_r;
-  dbuf<u8> d_ok;
-  HIPCHK(h, hipMalloc(&d_k.p, (size_t)nk * 8 * sizeof(u32)));
-  HIPCHK(h, hipMalloc(&d_pts.p, (size_t)nk * 16 * sizeof(u32)));
-  HIPCHK(h, hipMalloc(&d_r.p, (size_t)chunk * 4 * sizeof(u32)));
-  HIPCHK(h, hipMalloc(&d_ok.p, nk));
+  devbuf<u32> d_k, d_pts, d_r;
+  devbuf<u8> d_ok;
+  HIPCHK(h, d_k.grow((size_t)nk * 8));
+  HIPCHK(h, d_pts.grow((size_t)nk * 16));
+  HIPCHK(h, d_r.grow((size_t)chunk * 4));
+  HIPCHK(h, d_ok.grow(nk));
   std::vector<u32> ks((size_t)nk * 8), rs((size_t)chunk * 4), tab(32 * HERD_TAB_IN);
   // T_j = s_j G by the double-and-add kernel
   for (u32 j = 0; j < 32; ++j) {
@@ -66,7 +61,7 @@ static int herd_build(ecl_hip* h, const herd_params& p, u32* flags) {
     tab[(size_t)j * HERD_TAB_IN + 16] = (u32)s[j].lo, tab[(size_t)j * HERD_TAB_IN + 17] = (u32)(s[j].lo >> 32);
     tab[(size_t)j * HERD_TAB_IN + 18] = (u32)s[j].hi, tab[(size_t)j * HERD_TAB_IN + 19] = (u32)(s[j].hi >> 32);
   }
-  HIPCHK(h, hipMemcpyAsync(h->d_herdtab, tab.data(), tab.size() * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->d_herdtab.p, tab.data(), tab.size() * sizeof(u32), hipMemcpyHostToDevice, h->stream));
   // the starts, a chunk of kangaroos at a time: (B + r_i) G and r_i G by the double-and-add kernel, then Q added to the wild ones
   herd_q q;
   memcpy(q.w, p.q, sizeof q.w);
@@ -83,11 +78,11 @@ static int herd_build(ecl_hip* h, const herd_params& p, u32* flags) {
     HIPCHK(h, hipMemcpyAsync(d_r.p, rs.data(), (size_t)n * 4 * sizeof(u32), hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(k_mul_g, dim3((n + 63) / 64), dim3(64), 0, h->stream, d_k.p, d_pts.p, d_ok.p, n);
     HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(k_herd_init, dim3((n + 63) / 64), dim3(64), 0, h->stream, d_pts.p, d_ok.p, d_r.p, q, h->d_herd, H, first, n, h->d_counter);
+    hipLaunchKernelGGL(k_herd_init, dim3((n + 63) / 64), dim3(64), 0, h->stream, d_pts.p, d_ok.p, d_r.p, q, h->d_herd.p, H, first, n, h->d_counter.p);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));  // the host buffers are filled again
   }
-  HIPCHK(h, hipMemcpy(flags, h->d_counter + 6, sizeof(u32), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(flags, h->d_counter.p + 6, sizeof(u32), hipMemcpyDeviceToHost));
   return ECL_OK;
 }
 
@@ -106,17 +101,8 @@ static int herd_add_core(ecl_hip* h, const uint64_t blk[16], uint64_t nkeys, ecl
   const u32 rcap = raw_cap_of(h, cap ? cap : 1);
   if ((rc = ensure_found(h, rcap)) != ECL_OK) return rc;
   const u32 L = (H + HERD_M - 1) / HERD_M, grid = (L + HERD_BLOCK - 1) / HERD_BLOCK, T = grid * HERD_BLOCK;
-  const size_t need = (size_t)T * HERD_M * 2;
-  if (h->scr_elems < need) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_scr) HIPCHK(h, hipFree(h->d_scr));
-    if (h->d_scr2) HIPCHK(h, hipFree(h->d_scr2));
-    h->d_scr = nullptr, h->d_scr2 = nullptr, h->scr_elems = 0;
-    HIPCHK(h, hipMalloc(&h->d_scr, need * sizeof(uint4)));
-    HIPCHK(h, hipMalloc(&h->d_scr2, (need / 2) * sizeof(u32)));
-    h->scr_elems = need;
-  }
-  HIPCHK(h, hipMemsetAsync(h->d_counter, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
+  if ((rc = ensure_scratch(h, (size_t)T * HERD_M * 2)) != ECL_OK) return rc;
+  HIPCHK(h, hipMemsetAsync(h->d_counter.p, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
   const bool cont = h->herd_valid && memcmp(h->herd_blk, blk, sizeof h->herd_blk) == 0;
   if (!cont) {
     h->herd_valid = false;
@@ -130,8 +116,8 @@ static int herd_add_core(ecl_hip* h, const uint64_t blk[16], uint64_t nkeys, ecl
     }
   }
   herd_args a;
-  a.tab = h->d_herdtab, a.state = h->d_herd, a.scratch = h->d_scr, a.scratch2 = h->d_scr2;
-  a.found = (uint4*)h->d_found, a.counter = h->d_counter, a.jumps = (unsigned long long*)(h->d_counter + 4), a.cap = rcap;
+  a.tab = h->d_herdtab.p, a.state = h->d_herd.p, a.scratch = h->d_scr.p, a.scratch2 = h->d_scr2.p;
+  a.found = (uint4*)h->d_found.p, a.counter = h->d_counter.p, a.jumps = (unsigned long long*)(h->d_counter.p + 4), a.cap = rcap;
   a.H = H, a.L = L, a.T = T, a.dpmask = h->offs >= 32 ? ~0u : (1u << h->offs) - 1u;
   u64 per = (1ull << HERD_LAUNCH_JUMPS_LOG2) >> p.herd_log2;
   if (per > HERD_LAUNCH_STEPS_MAX) per = HERD_LAUNCH_STEPS_MAX;
@@ -159,7 +145,7 @@ static int herd_add_core(ecl_hip* h, const uint64_t blk[16], uint64_t nkeys, ecl
     h->herd_valid = false;
     return ECL_E_COVERAGE;
   }
-  if (h->pin_counter[6] & 1u) {
+  if (h->pin_counter.p[6] & 1u) {
     h->err = "a kangaroo's distance passed 2^128";
     h->herd_valid = false, h->last_held = h->last_total = 0;
     return ECL_E_RANGE;

@@ -3,7 +3,7 @@
 #pragma once
 // ec_gtable_init (lib/ecc.c:880-905) on the device: every slot is an independent double-and-add
 static int ensure_gtable(ecl_hip* h) {
-  if (h->d_gtab) return ECL_OK;
+  if (h->d_gtab.p) return ECL_OK;
   const size_t slots = (size_t)GT_WINDOWS * GT_PER;
   std::vector<u32> ks(slots * 8);
   for (u32 w = 0; w < GT_WINDOWS; ++w) {
@@ -13,14 +13,14 @@ static int ensure_gtable(ecl_hip* h) {
       cur = sc_add(cur, base);
     }
   }
-  dbuf<u32> d_k, tab;  // freed on every way out; the table is handed to the context only when it is complete
-  HIPCHK(h, hipMalloc(&d_k.p, ks.size() * sizeof(u32)));
-  HIPCHK(h, hipMalloc(&tab.p, slots * 16 * sizeof(u32)));
+  devbuf<u32> d_k, tab;  // freed on every way out; the table is handed to the context only when it is complete
+  HIPCHK(h, d_k.grow(ks.size()));
+  HIPCHK(h, tab.grow(slots * 16));
   HIPCHK(h, hipMemcpy(d_k.p, ks.data(), ks.size() * sizeof(u32), hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_mul_g, dim3((unsigned)((slots + 63) / 64)), dim3(64), 0, h->stream, d_k.p, tab.p, (u8*)nullptr, (u32)slots);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->d_gtab = tab.p, tab.p = nullptr;
+  h->d_gtab = std::move(tab);
   return ECL_OK;
 }
 
@@ -36,12 +36,13 @@ static int ensure_gtable(ecl_hip* h) {
 #define MUL_LONG_AFTER (1ull << 30)   /* scalars a context has seen before it moves to MUL_W_LONG: the wider table gains ~0.1 ns per scalar,
                                          so its build is paid back after 10^9 of them */
 struct multab_t {
-  u32* d = nullptr;
+  devbuf<u32> d;
   int refs = 0;
   std::mutex mu;  // held while the table is built: a context that wants the same table waits for it, one that wants another width does not
 };
 static std::mutex g_multab_mu;  // guards the map only (its nodes stay where they are)
-static std::map<std::pair<int, u32>, multab_t> g_multab;
+// (never destroyed: a process that ends with a context still open must not free device memory from a static destructor, after the runtime)
+static std::map<std::pair<int, u32>, multab_t>& g_multab = *new std::map<std::pair<int, u32>, multab_t>;
 static multab_t* multab_entry(int dev, u32 W) {
   std::lock_guard<std::mutex> lk(g_multab_mu);
   return &g_multab[{dev, W}];
@@ -51,21 +52,21 @@ static void release_multable(ecl_hip* h) {
   if (!h->d_multab) return;
   multab_t* t = multab_entry(h->dev, h->multab_W);
   std::lock_guard<std::mutex> lk(t->mu);
-  if (--t->refs == 0) (void)hipFree(t->d), t->d = nullptr;
+  if (--t->refs == 0) t->d.reset();
   h->d_multab = nullptr, h->multab_W = 0;
 }
 
-static int build_multable(ecl_hip* h, u32 W, u32** out) {
-  dbuf<u32> lad_k, lad, tmp, tab, got, want, want_k;
-  dbuf<u64> slots;
+static int build_multable(ecl_hip* h, u32 W, devbuf<u32>* out) {
+  devbuf<u32> lad_k, lad, tmp, tab, got, want, want_k;
+  devbuf<u64> slots;
   const wtab tb = wtab_make(nullptr, W);
   // ladders: 2^j * 2^(W w) * G for j < the row's digit width
   std::vector<u32> ks((size_t)tb.nwin * 32 * 8, 0);
   for (u32 w = 0; w < tb.nwin; ++w)
     for (u32 j = 0; j < W && W * w + j < 256; ++j) words_of(&ks[((size_t)w * 32 + j) * 8], sc_pow2(W * w + j));
   const u32 nlad = tb.nwin * 32;
-  HIPCHK(h, hipMalloc(&lad_k.p, ks.size() * sizeof(u32)));
-  HIPCHK(h, hipMalloc(&lad.p, (size_t)nlad * 16 * sizeof(u32)));
+  HIPCHK(h, lad_k.grow(ks.size()));
+  HIPCHK(h, lad.grow((size_t)nlad * 16));
   HIPCHK(h, hipMemcpyAsync(lad_k.p, ks.data(), ks.size() * sizeof(u32), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_mul_g, dim3((nlad + 63) / 64), dim3(64), 0, h->stream, lad_k.p, lad.p, (u8*)nullptr, nlad);
   HIPCHK(h, hipGetLastError());
@@ -75,8 +76,8 @@ static int build_multable(ecl_hip* h, u32 W, u32** out) {
   const u32 nt = nt_row < (1u << 20) ? nt_row : (1u << 20);
   u32 rows = (1u << 18) / nt;
   rows = rows < 1 ? 1 : (rows > tb.nwin ? tb.nwin : rows);
-  HIPCHK(h, hipMalloc(&tmp.p, (size_t)rows * 16 * 36 * nt * sizeof(u32)));
-  HIPCHK(h, hipMalloc(&tab.p, wtab_slots(tb) * 16 * sizeof(u32)));
+  HIPCHK(h, tmp.grow((size_t)rows * 16 * 36 * nt));
+  HIPCHK(h, tab.grow(wtab_slots(tb) * 16));
   for (u32 w0 = 0; w0 < tb.nwin; w0 += rows) {
     const u32 ny = tb.nwin - w0 < rows ? tb.nwin - w0 : rows;
     for (u32 t0 = 0; t0 < nt_row; t0 += nt)
@@ -101,10 +102,10 @@ static int build_multable(ecl_hip* h, u32 W, u32** out) {
     }
   }
   const u32 ns = (u32)sl.size();
-  HIPCHK(h, hipMalloc(&slots.p, (size_t)ns * 8));
-  HIPCHK(h, hipMalloc(&got.p, (size_t)ns * 64));
-  HIPCHK(h, hipMalloc(&want.p, (size_t)ns * 64));
-  HIPCHK(h, hipMalloc(&want_k.p, (size_t)ns * 32));
+  HIPCHK(h, slots.grow(ns));
+  HIPCHK(h, got.grow((size_t)ns * 16));
+  HIPCHK(h, want.grow((size_t)ns * 16));
+  HIPCHK(h, want_k.grow((size_t)ns * 8));
   HIPCHK(h, hipMemcpyAsync(slots.p, sl.data(), (size_t)ns * 8, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(want_k.p, wk.data(), (size_t)ns * 32, hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_gather_slots, dim3((ns + 63) / 64), dim3(64), 0, h->stream, tab.p, slots.p, got.p, ns);
@@ -118,7 +119,7 @@ static int build_multable(ecl_hip* h, u32 W, u32** out) {
     h->err = "mul window table disagrees with the double-and-add kernel";
     return ECL_E_SELFTEST;
   }
-  *out = tab.p, tab.p = nullptr;
+  *out = std::move(tab);
   return ECL_OK;
 }
 
@@ -129,7 +130,7 @@ static int ensure_multable(ecl_hip* h, u32 W) {
   multab_t* t = multab_entry(h->dev, W);
   {
     std::lock_guard<std::mutex> lk(t->mu);
-    if (!t->d) {
+    if (!t->d.p) {
       const int rc = build_multable(h, W, &t->d);
       if (rc != ECL_OK) return rc;
     }
@@ -140,7 +141,7 @@ static int ensure_multable(ecl_hip* h, u32 W) {
     if (h->stream2) HIPCHK(h, hipStreamSynchronize(h->stream2));  // ... on either compute stream (a call that failed between its pieces never joined them)
     release_multable(h);
   }
-  h->d_multab = t->d, h->multab_W = W;
+  h->d_multab = t->d.p, h->multab_W = W;
   return ECL_OK;
 }
 
@@ -182,33 +183,20 @@ static int mul_setup(ecl_hip* h, u32 n, u32 W) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream2));
     HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-    for (int i = 0; i < MUL_NBUF; ++i) {
-      if (h->d_kbuf[i]) HIPCHK(h, hipFree(h->d_kbuf[i]));
-      if (h->pin_k[i]) HIPCHK(h, hipHostFree(h->pin_k[i]));
-      h->d_kbuf[i] = nullptr, h->pin_k[i] = nullptr;
-    }
-    h->pin_cap = 0;
-    for (int i = 0; i < 2; ++i) {
-      if (h->d_multmp[i]) HIPCHK(h, hipFree(h->d_multmp[i]));
-      h->d_multmp[i] = nullptr;
-    }
+    // a piece's size counts only once every buffer of the group holds it: a call that fails between two of these allocations leaves
+    // kbuf_cap at 0 and the failed buffer empty, and the next call allocates what is still missing
     h->kbuf_cap = 0;
-    for (int i = 0; i < MUL_NBUF; ++i) HIPCHK(h, hipMalloc(&h->d_kbuf[i], (size_t)want * 32));
+    for (int i = 0; i < MUL_NBUF; ++i) HIPCHK(h, h->d_kbuf[i].grow((size_t)want * 8));
     // the kernel indexes the planes as r * 36 * nt + plane * nt + t with nt = ceil(m / R) rounded up to whole workgroups:
     // up to R * 256 slots more than m
-    for (int i = 0; i < 2; ++i) HIPCHK(h, hipMalloc(&h->d_multmp[i], ((size_t)want + MUL_R * 256u) * 36 * sizeof(u32)));
+    for (int i = 0; i < 2; ++i) HIPCHK(h, h->d_multmp[i].grow(((size_t)want + MUL_R * 256u) * 36));
     h->kbuf_cap = want;
   }
-  if ((h->flags & ECL_TR) && h->trslab_mul_cap < h->kbuf_cap) {  // Taproot: a piece is its own slab, one per compute stream
+  const size_t slab_words = (size_t)h->kbuf_cap * TR_SLAB_WORDS;
+  if ((h->flags & ECL_TR) && held_by_all(h->d_trslab_mul) < slab_words) {  // Taproot: a piece is its own slab, one per compute stream
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream2));
-    for (int i = 0; i < 2; ++i) {
-      if (h->d_trslab_mul[i]) HIPCHK(h, hipFree(h->d_trslab_mul[i]));
-      h->d_trslab_mul[i] = nullptr;
-    }
-    h->trslab_mul_cap = 0;
-    for (int i = 0; i < 2; ++i) HIPCHK(h, hipMalloc(&h->d_trslab_mul[i], (size_t)h->kbuf_cap * TR_SLAB_WORDS * sizeof(u32)));
-    h->trslab_mul_cap = h->kbuf_cap;
+    for (int i = 0; i < 2; ++i) HIPCHK(h, h->d_trslab_mul[i].grow(slab_words));
   }
   return ECL_OK;
 }
@@ -227,7 +215,7 @@ static void tr_mul_launch_piece(ecl_hip* h, int lane, const u32* d_k, u32 m, u32
 static void mul_launch_piece(ecl_hip* h, int lane, const u32* d_k, u32 m, u32 at, const wtab& gtab, const add_args& a, bool short_round) {
   u32 R, nt;
   hipStream_t st = lane ? h->stream2 : h->stream;
-  u32* tmp = h->d_multmp[lane];
+  u32* tmp = h->d_multmp[lane].p;
   mul_geometry(m, &R, &nt);
   if (short_round) R -= 1;
   dim3 grid(nt / 256), blk(256);
@@ -314,7 +302,7 @@ template <class CopyIn, class Prepare> static int mul_pieces(ecl_hip* h, u32 n, 
     hipEvent_t ready = h->ev_copied[b];
     if (int rc = prepare(b, at, m, &ready)) return rc;
     HIPCHK(h, hipStreamWaitEvent(st, ready, 0));
-    mul_launch_piece(h, lane, h->d_kbuf[b], m, at, gtab, a, drop && c == 0);
+    mul_launch_piece(h, lane, h->d_kbuf[b].p, m, at, gtab, a, drop && c == 0);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->ev_free[b], st));
   }
@@ -337,7 +325,7 @@ extern "C" int ecl_hip_mul_batch(ecl_hip* h, const uint64_t (*scalars)[4], uint3
   if (!h || (!scalars && n) || (!out && cap) || !nout || cap > ECL_CAP_MAX) return ECL_E_ARG;
   if (h->flags & (ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX)) return ECL_E_ARG;  // the walks of `bsgs` and prefix contexts have no `mul`
   *nout = 0;
-  if (!h->d_bloom) return ECL_E_NOBLOOM;
+  if (!h->d_bloom.p) return ECL_E_NOBLOOM;
   if (n == 0) return ECL_OK;
   HIPCHK(h, hipSetDevice(h->dev));
   int rc;
@@ -366,20 +354,13 @@ extern "C" int ecl_hip_mul_batch(ecl_hip* h, const uint64_t (*scalars)[4], uint3
       }
     }
   }
-  if (!direct && (!h->pin_k[0] || h->pin_cap < h->kbuf_cap)) {
-    for (int i = 0; i < MUL_NBUF; ++i) {
-      if (h->pin_k[i]) HIPCHK(h, hipHostFree(h->pin_k[i]));
-      h->pin_k[i] = nullptr;
-    }
-    h->pin_cap = 0;
-    for (int i = 0; i < MUL_NBUF; ++i) HIPCHK(h, hipHostMalloc(&h->pin_k[i], (size_t)h->kbuf_cap * 32, hipHostMallocDefault));
-    h->pin_cap = h->kbuf_cap;
-  }
+  if (!direct)  // (a staging buffer that is too small has not been used since the device buffers grew, and that waited for every stream)
+    for (int i = 0; i < MUL_NBUF; ++i) HIPCHK(h, h->pin_k[i].grow((size_t)h->kbuf_cap * 8));
   add_args a;
   memset(&a, 0, sizeof a);
-  a.bloom = bloom_make(h->d_bloom, h->bloom_words);
-  a.found = h->d_found, a.counter = h->d_counter, a.cap = rcap, a.keys = (unsigned long long*)(h->d_counter + 4);
-  HIPCHK(h, hipMemsetAsync(h->d_counter, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
+  a.bloom = bloom_make(h->d_bloom.p, h->bloom_words);
+  a.found = h->d_found.p, a.counter = h->d_counter.p, a.cap = rcap, a.keys = (unsigned long long*)(h->d_counter.p + 4);
+  HIPCHK(h, hipMemsetAsync(h->d_counter.p, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
   // Scalars are used as given (4 little-endian u64 = 8 u32 words): the window sum (wtab_sum_fast, any width) is k*G for any
   // 256-bit k, which is (k mod n)*G; k = 0 (mod n) gives the point at infinity and is skipped.
   const bool staged = !direct;
@@ -387,8 +368,8 @@ extern "C" int ecl_hip_mul_batch(ecl_hip* h, const uint64_t (*scalars)[4], uint3
       h, n, gtab, a,
       [&](u32 b, u32 at, u32 m) -> int {  // piece `at`'s scalars onto the copy stream
         const void* src = scalars[at];
-        if (staged) memcpy(h->pin_k[b], scalars[at], (size_t)m * 32), src = h->pin_k[b];
-        HIPCHK(h, hipMemcpyAsync(h->d_kbuf[b], src, (size_t)m * 32, hipMemcpyHostToDevice, h->copy_stream));
+        if (staged) memcpy(h->pin_k[b].p, scalars[at], (size_t)m * 32), src = h->pin_k[b].p;
+        HIPCHK(h, hipMemcpyAsync(h->d_kbuf[b].p, src, (size_t)m * 32, hipMemcpyHostToDevice, h->copy_stream));
         return ECL_OK;
       },
       [](u32, u32, u32, hipEvent_t*) -> int { return ECL_OK; });
@@ -419,7 +400,7 @@ extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t t
   if (!h || (!text && text_bytes) || (!lines && n) || (!out && cap) || !nout || n > MUL_RAW_MAX || text_bytes > 0xFFFFFFF0u || cap > ECL_CAP_MAX) return ECL_E_ARG;
   if (h->flags & (ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX)) return ECL_E_ARG;
   *nout = 0;
-  if (!h->d_bloom) return ECL_E_NOBLOOM;
+  if (!h->d_bloom.p) return ECL_E_NOBLOOM;
   if (n == 0) return ECL_OK;
   HIPCHK(h, hipSetDevice(h->dev));
   int rc;
@@ -431,29 +412,23 @@ extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t t
   const wtab gtab = wtab_make(h->d_multab, W);
   h->mul_seen += n;
   const size_t text_words = ((size_t)text_bytes + 3) / 4 + 2;  // two spare words: the gather reads one word past the last byte
-  if (text_words > h->rawtext_cap || n > h->rawlines_cap) {
+  if (text_words > h->d_rawtext.n || n > h->d_rawlines.n) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream2));
     HIPCHK(h, hipStreamSynchronize(h->copy_stream));
     if (h->prep_stream) HIPCHK(h, hipStreamSynchronize(h->prep_stream));  // (a call that failed between its pieces)
-    if (text_words > h->rawtext_cap) {
-      if (h->d_rawtext) HIPCHK(h, hipFree(h->d_rawtext));
-      h->d_rawtext = nullptr, h->rawtext_cap = 0;
+    if (text_words > h->d_rawtext.n) {
       size_t capw = (size_t)1 << 22;  // 16 MB of text
       while (capw < text_words) capw <<= 1;
-      HIPCHK(h, hipMalloc(&h->d_rawtext, capw * 4));
+      HIPCHK(h, h->d_rawtext.grow(capw));
       // (hipMemset is asynchronous to the host and runs on the legacy stream, which the context's non-blocking streams do not
       // wait for: the clearing goes on the copy stream, in front of the text that is copied there next)
-      HIPCHK(h, hipMemsetAsync(h->d_rawtext, 0, capw * 4, h->copy_stream));
-      h->rawtext_cap = capw;
+      HIPCHK(h, hipMemsetAsync(h->d_rawtext.p, 0, capw * 4, h->copy_stream));
     }
-    if (n > h->rawlines_cap) {
-      if (h->d_rawlines) HIPCHK(h, hipFree(h->d_rawlines));
-      h->d_rawlines = nullptr, h->rawlines_cap = 0;
+    if (n > h->d_rawlines.n) {
       u32 capl = 1u << 20;
       while (capl < n) capl <<= 1;
-      HIPCHK(h, hipMalloc(&h->d_rawlines, (size_t)capl * 8));
-      h->rawlines_cap = capl;
+      HIPCHK(h, h->d_rawlines.grow(capl));
     }
   }
   if (!h->prep_stream) {
@@ -464,11 +439,11 @@ extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t t
   }
   add_args a;
   memset(&a, 0, sizeof a);
-  a.bloom = bloom_make(h->d_bloom, h->bloom_words);
-  a.found = h->d_found, a.counter = h->d_counter, a.cap = rcap, a.keys = (unsigned long long*)(h->d_counter + 4);
-  u64* d_lines = h->d_rawlines;
-  u32* d_flags = h->d_counter + 2;  // [0] a line outside the text, [1] a line beyond the part of the text that was on the device when it was hashed
-  u32* d_text = h->d_rawtext;
+  a.bloom = bloom_make(h->d_bloom.p, h->bloom_words);
+  a.found = h->d_found.p, a.counter = h->d_counter.p, a.cap = rcap, a.keys = (unsigned long long*)(h->d_counter.p + 4);
+  u64* d_lines = h->d_rawlines.p;
+  u32* d_flags = h->d_counter.p + 2;  // [0] a line outside the text, [1] a line beyond the part of the text that was on the device when it was hashed
+  u32* d_text = h->d_rawtext.p;
   // The text goes with the pieces: in front of piece c's share of the table, the text up to the end of that share's LAST line - for a
   // table in the order of the text (any caller that cut lines out of a buffer front to back) every line is then on the device when its
   // piece is hashed, and the first piece starts after its own bytes instead of after all of them (300 MB for 2^24 pass phrases: 5 ms of
@@ -479,7 +454,7 @@ extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t t
   u64 missed_got = 0;
   for (int pass = 0; pass < 2; ++pass) {
     const bool in_order = pass == 0;
-    HIPCHK(h, hipMemsetAsync(h->d_counter, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->d_counter.p, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
     HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));  // the hashing writes the flags: behind their reset
     HIPCHK(h, hipStreamWaitEvent(h->prep_stream, h->ev_fork, 0));
     u32 have = 0;  // bytes of the text on the copy stream so far
@@ -503,7 +478,7 @@ extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t t
           // The hashing has a stream of its own, of higher priority than the compute streams, and runs up to MUL_NBUF - 1 pieces ahead like
           // the copies: on the piece's compute stream it would sit between two k_mul_check launches that each fill the chip.
           HIPCHK(h, hipStreamWaitEvent(h->prep_stream, h->ev_copied[b], 0));
-          hipLaunchKernelGGL(k_raw_scalars, dim3((m + 255) / 256), dim3(256), 0, h->prep_stream, d_text, text_bytes, have, d_lines + at, m, h->d_kbuf[b], d_flags);
+          hipLaunchKernelGGL(k_raw_scalars, dim3((m + 255) / 256), dim3(256), 0, h->prep_stream, d_text, text_bytes, have, d_lines + at, m, h->d_kbuf[b].p, d_flags);
           HIPCHK(h, hipEventRecord(h->ev_hashed[b], h->prep_stream));
           *ready = h->ev_hashed[b];
           return ECL_OK;
@@ -512,7 +487,7 @@ extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t t
     HIPCHK(h, hipEventRecord(h->ev1, h->stream));
     rc = collect_found(h, cap, rcap, out, &cnt, false);  // (the one wait of the call; the flags come back with the counters)
     if (rc != ECL_OK && rc != ECL_E_OVERFLOW) return rc;
-    flags[0] = h->pin_counter[2], flags[1] = h->pin_counter[3];
+    flags[0] = h->pin_counter.p[2], flags[1] = h->pin_counter.p[3];
     const u64 got = counted_keys(h);
     h->cov_device += got;
     if (got != n && !missed) missed = true, missed_got = got;
@@ -557,17 +532,17 @@ static int verify_origin(ecl_hip* h, const uint64_t* k, uint32_t n, uint32_t (*h
   int rc;
   if ((rc = ensure_gtable(h)) != ECL_OK) return rc;
   const size_t in_bytes = (size_t)n * VERIFY_ORIGIN_WORDS * sizeof(u32);
-  dbuf<u8> d;  // entries 96 B, two hashes (eth: one address) 20 B each, flag
-  HIPCHK(h, hipMalloc(&d.p, in_bytes + (size_t)n * 41));
+  devbuf<u8> d;  // entries 96 B, two hashes (eth: one address) 20 B each, flag
+  HIPCHK(h, d.grow(in_bytes + (size_t)n * 41));
   u32* dk = (u32*)d.p;
   u32* d33 = (u32*)(d.p + in_bytes);
   u32* d65 = (u32*)(d.p + in_bytes + (size_t)n * 20);
   u8* dok = d.p + in_bytes + (size_t)n * 40;
   HIPCHK(h, hipMemcpyAsync(dk, ent.data(), in_bytes, hipMemcpyHostToDevice, h->stream));
   if (h65)
-    hipLaunchKernelGGL(k_verify_origin, dim3((n + 63) / 64), dim3(64), 0, h->stream, dk, n, h->d_gtab, d33, d65, dok);
+    hipLaunchKernelGGL(k_verify_origin, dim3((n + 63) / 64), dim3(64), 0, h->stream, dk, n, h->d_gtab.p, d33, d65, dok);
   else
-    hipLaunchKernelGGL(k_verify_origin_eth, dim3((n + 63) / 64), dim3(64), 0, h->stream, dk, n, h->d_gtab, d33, dok);
+    hipLaunchKernelGGL(k_verify_origin_eth, dim3((n + 63) / 64), dim3(64), 0, h->stream, dk, n, h->d_gtab.p, d33, dok);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(h33, d33, (size_t)n * 20, hipMemcpyDeviceToHost, h->stream));
   if (h65) HIPCHK(h, hipMemcpyAsync(h65, d65, (size_t)n * 20, hipMemcpyDeviceToHost, h->stream));
@@ -582,22 +557,20 @@ static int verify_plain(ecl_hip* h, const uint64_t (*k)[4], uint32_t n, uint32_t
   HIPCHK(h, hipSetDevice(h->dev));
   int rc;
   if ((rc = ensure_gtable(h)) != ECL_OK) return rc;
-  if (n > h->ver_cap) {  // grow-only device staging: scalars 32 B, two hashes 20 B each, flag
+  if (n > h->d_ver.n / 76) {  // grow-only device staging: scalars 32 B, two hashes 20 B each, flag
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_ver) HIPCHK(h, hipFree(h->d_ver));
-    h->d_ver = nullptr, h->ver_cap = 0;
     u32 cap = 256;
     while (cap < n) cap <<= 1;
-    HIPCHK(h, hipMalloc(&h->d_ver, (size_t)cap * 76));
-    h->ver_cap = cap;
+    HIPCHK(h, h->d_ver.grow((size_t)cap * 76));
   }
-  u8* base = (u8*)h->d_ver;
+  u8* base = h->d_ver.p;
+  const size_t ver_cap = h->d_ver.n / 76;
   u32* dk = (u32*)base;
-  u32* d33 = (u32*)(base + (size_t)h->ver_cap * 32);
-  u32* d65 = (u32*)(base + (size_t)h->ver_cap * 52);
-  u8* dok = base + (size_t)h->ver_cap * 72;
+  u32* d33 = (u32*)(base + ver_cap * 32);
+  u32* d65 = (u32*)(base + ver_cap * 52);
+  u8* dok = base + ver_cap * 72;
   HIPCHK(h, hipMemcpyAsync(dk, k, (size_t)n * 32, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(k_verify, dim3((n + 63) / 64), dim3(64), 0, h->stream, dk, n, h->d_gtab, d33, d65, dok);
+  hipLaunchKernelGGL(k_verify, dim3((n + 63) / 64), dim3(64), 0, h->stream, dk, n, h->d_gtab.p, d33, d65, dok);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(h33, d33, (size_t)n * 20, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemcpyAsync(h65, d65, (size_t)n * 20, hipMemcpyDeviceToHost, h->stream));
@@ -617,13 +590,13 @@ static int verify_eth_plain(ecl_hip* h, const uint64_t (*k)[4], uint32_t n, uint
   HIPCHK(h, hipSetDevice(h->dev));
   int rc;
   if ((rc = ensure_gtable(h)) != ECL_OK) return rc;
-  dbuf<u8> d;  // scalars 32 B, address 20 B, flag
-  HIPCHK(h, hipMalloc(&d.p, (size_t)n * 53));
+  devbuf<u8> d;  // scalars 32 B, address 20 B, flag
+  HIPCHK(h, d.grow((size_t)n * 53));
   u32* dk = (u32*)d.p;
   u32* da = (u32*)(d.p + (size_t)n * 32);
   u8* dok = d.p + (size_t)n * 52;
   HIPCHK(h, hipMemcpyAsync(dk, k, (size_t)n * 32, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(k_verify_eth, dim3((n + 63) / 64), dim3(64), 0, h->stream, dk, n, h->d_gtab, da, dok);
+  hipLaunchKernelGGL(k_verify_eth, dim3((n + 63) / 64), dim3(64), 0, h->stream, dk, n, h->d_gtab.p, da, dok);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(addr, da, (size_t)n * 20, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, h->stream));
@@ -640,8 +613,8 @@ extern "C" int ecl_hip_verify_eth(ecl_hip* h, const uint64_t (*k)[4], uint32_t n
 extern "C" int ecl_hip_p2sh_hash(ecl_hip* h, const uint32_t (*h33)[5], uint32_t (*out)[5], uint32_t n) {
   if (!h || !h33 || !out || n == 0 || n > (1u << 31)) return ECL_E_ARG;
   HIPCHK(h, hipSetDevice(h->dev));
-  dbuf<u32> d;
-  HIPCHK(h, hipMalloc(&d.p, (size_t)n * 40));
+  devbuf<u32> d;
+  HIPCHK(h, d.grow((size_t)n * 10));
   u32* dout = d.p + (size_t)n * 5;
   HIPCHK(h, hipMemcpyAsync(d.p, h33, (size_t)n * 20, hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_p2sh_hash, dim3((n + 63) / 64), dim3(64), 0, h->stream, d.p, dout, n);

@@ -40,24 +40,15 @@ static int tr_buffers(ecl_hip* h, u64 nkeys) {
   const u64 slab = tr_slab_keys(), m = nkeys < slab ? nkeys : slab, words = tr_tmp_words(m);
   int rc;
   if ((rc = mul_streams(h)) != ECL_OK) return rc;
-  if (h->trslab_cap < m) {
+  if (h->d_trslab.n < m * TR_SLAB_WORDS) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream2));
-    if (h->d_trslab) HIPCHK(h, hipFree(h->d_trslab));
-    h->d_trslab = nullptr, h->trslab_cap = 0;
-    HIPCHK(h, hipMalloc(&h->d_trslab, (size_t)m * TR_SLAB_WORDS * sizeof(u32)));
-    h->trslab_cap = m;
+    HIPCHK(h, h->d_trslab.grow((size_t)m * TR_SLAB_WORDS));
   }
-  if (h->trtmp_words < words) {
+  if (held_by_all(h->d_trtmp) < words) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream2));
-    for (int i = 0; i < 2; ++i) {
-      if (h->d_trtmp[i]) HIPCHK(h, hipFree(h->d_trtmp[i]));
-      h->d_trtmp[i] = nullptr;
-    }
-    h->trtmp_words = 0;
-    for (int i = 0; i < 2; ++i) HIPCHK(h, hipMalloc(&h->d_trtmp[i], (size_t)words * sizeof(u32)));
-    h->trtmp_words = words;
+    for (int i = 0; i < 2; ++i) HIPCHK(h, h->d_trtmp[i].grow((size_t)words));
   }
   return ECL_OK;
 }
@@ -76,8 +67,8 @@ static int tr_reserve(ecl_hip* h, uint64_t nkeys) {
 static int tr_launch_check(ecl_hip* h, hipStream_t st, const u32* slab, u32 m, u64 base, const wtab& gtab, u32 rcap, u32 epoch, u32* tmp) {
   add_args a;
   memset(&a, 0, sizeof a);
-  a.bloom = bloom_make(h->d_bloom, h->bloom_words);
-  a.found = h->d_found, a.counter = h->d_counter, a.cap = rcap, a.keys = (unsigned long long*)(h->d_counter + 6);
+  a.bloom = bloom_make(h->d_bloom.p, h->bloom_words);
+  a.found = h->d_found.p, a.counter = h->d_counter.p, a.cap = rcap, a.keys = (unsigned long long*)(h->d_counter.p + 6);
   u32 R, nt;
   tr_geometry(m, &R, &nt);
   hipLaunchKernelGGL(k_tr_check<false>, dim3(nt / 256), dim3(256), 0, st, slab, m, base, gtab, a, epoch, tmp, nt, R, (u32*)nullptr, (u8*)nullptr);
@@ -97,7 +88,7 @@ static int tr_check_slab(ecl_hip* h, u64 m, u64 at, const wtab& gtab, u32 rcap, 
   for (u64 off = 0; off < m; ++c) {
     const u64 n = m - off < even ? m - off : even;
     const int lane = two ? (int)(c & 1u) : 0;
-    int rc = tr_launch_check(h, lane ? h->stream2 : h->stream, h->d_trslab + (size_t)off * TR_SLAB_WORDS, (u32)n, at + off, gtab, rcap, epoch, h->d_trtmp[lane]);
+    int rc = tr_launch_check(h, lane ? h->stream2 : h->stream, h->d_trslab.p + (size_t)off * TR_SLAB_WORDS, (u32)n, at + off, gtab, rcap, epoch, h->d_trtmp[lane].p);
     if (rc != ECL_OK) return rc;
     off += n;
   }
@@ -107,7 +98,7 @@ static int tr_check_slab(ecl_hip* h, u64 m, u64 at, const wtab& gtab, u32 rcap, 
   }
   return ECL_OK;
 }
-static u64 tr_checked_keys(const ecl_hip* h) { return (u64)h->pin_counter[6] | (u64)h->pin_counter[7] << 32; }
+static u64 tr_checked_keys(const ecl_hip* h) { return (u64)h->pin_counter.p[6] | (u64)h->pin_counter.p[7] << 32; }
 
 // ecl_hip_add_range's body on a Taproot context.  A call of 2^32 keys cannot park 2^32 x 96 bytes, so it is walked in slabs of contiguous
 // sub-launches of the emit kernel (the points come from the walk), each followed by k_tr_check over the slab, all on the context's
@@ -126,7 +117,7 @@ static int tr_add_core(ecl_hip* h, const u256& k0, uint64_t nkeys, ecl_found* ou
   h->mul_seen += nkeys;
   const u64 slab = tr_slab_keys();
   const u256 s = sc_pow2(h->offs);
-  HIPCHK(h, hipMemsetAsync(h->d_counter, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
+  HIPCHK(h, hipMemsetAsync(h->d_counter.p, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
   HIPCHK(h, hipEventRecord(h->ev0, h->stream));
   u32 slabs = 0, setups = 0;
   for (u64 at = 0; at < nkeys; ++slabs) {
@@ -135,7 +126,7 @@ static int tr_add_core(ecl_hip* h, const u256& k0, uint64_t nkeys, ecl_found* ou
     h->tr_epoch ^= 1u;
     bool cont = false;
     u64 walked = 0;
-    if ((rc = add_launch(h, ks, m, rcap, false, h->d_trslab, h->tr_epoch, &cont, &walked)) != ECL_OK) {
+    if ((rc = add_launch(h, ks, m, rcap, false, h->d_trslab.p, h->tr_epoch, &cont, &walked)) != ECL_OK) {
       h->walk_valid = false;
       return rc;
     }
@@ -173,10 +164,10 @@ static void tr_mul_launch_piece(ecl_hip* h, int lane, const u32* d_k, u32 m, u32
   if (short_round) R -= 1;
   const u32 epoch = h->tr_epoch_mul[lane] ^= 1u;
   add_args e = a;
-  e.slab = h->d_trslab_mul[lane], e.epoch = epoch;
-  hipLaunchKernelGGL(k_mul_points_tr, dim3(nt / 256), dim3(256), 0, st, d_k, m, 0u, gtab, e, h->d_multmp[lane], nt, R);
+  e.slab = h->d_trslab_mul[lane].p, e.epoch = epoch;
+  hipLaunchKernelGGL(k_mul_points_tr, dim3(nt / 256), dim3(256), 0, st, d_k, m, 0u, gtab, e, h->d_multmp[lane].p, nt, R);
   if (hipGetLastError() != hipSuccess) return;
-  (void)tr_launch_check(h, st, h->d_trslab_mul[lane], m, at, gtab, a.cap, epoch, h->d_multmp[lane]);
+  (void)tr_launch_check(h, st, h->d_trslab_mul[lane].p, m, at, gtab, a.cap, epoch, h->d_multmp[lane].p);
 }
 
 extern "C" int ecl_hip_verify_tr(ecl_hip* h, const uint64_t (*k)[4], uint32_t n, uint32_t (*qx)[8], uint8_t* ok) {
@@ -184,13 +175,13 @@ extern "C" int ecl_hip_verify_tr(ecl_hip* h, const uint64_t (*k)[4], uint32_t n,
   HIPCHK(h, hipSetDevice(h->dev));
   int rc;
   if ((rc = ensure_gtable(h)) != ECL_OK) return rc;
-  dbuf<u8> d;  // scalars 32 B, output key 32 B, flag
-  HIPCHK(h, hipMalloc(&d.p, (size_t)n * 65));
+  devbuf<u8> d;  // scalars 32 B, output key 32 B, flag
+  HIPCHK(h, d.grow((size_t)n * 65));
   u32* dk = (u32*)d.p;
   u32* dq = (u32*)(d.p + (size_t)n * 32);
   u8* dok = d.p + (size_t)n * 64;
   HIPCHK(h, hipMemcpyAsync(dk, k, (size_t)n * 32, hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(k_verify_tr, dim3((n + 63) / 64), dim3(64), 0, h->stream, dk, n, h->d_gtab, dq, dok);
+  hipLaunchKernelGGL(k_verify_tr, dim3((n + 63) / 64), dim3(64), 0, h->stream, dk, n, h->d_gtab.p, dq, dok);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(qx, dq, (size_t)n * 32, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipMemcpyAsync(ok, dok, n, hipMemcpyDeviceToHost, h->stream));
@@ -208,16 +199,16 @@ extern "C" int ecl_hip_diag_tr(ecl_hip* h, const uint64_t (*x)[4], const uint64_
   if ((rc = tr_table(h, 0, &gtab)) != ECL_OK) return rc;
   u32 R, nt;
   tr_geometry(n, &R, &nt);
-  dbuf<u32> dx, dy, slab, tmp, dq;
-  dbuf<u8> dok;
-  dbuf<unsigned long long> cnt;
-  HIPCHK(h, hipMalloc(&dx.p, (size_t)n * 32));
-  HIPCHK(h, hipMalloc(&dy.p, (size_t)n * 32));
-  HIPCHK(h, hipMalloc(&slab.p, (size_t)n * TR_SLAB_WORDS * 4));
-  HIPCHK(h, hipMalloc(&tmp.p, (size_t)R * nt * 27 * 4));
-  HIPCHK(h, hipMalloc(&dq.p, (size_t)n * 32));
-  HIPCHK(h, hipMalloc(&dok.p, n));
-  HIPCHK(h, hipMalloc(&cnt.p, 8));
+  devbuf<u32> dx, dy, slab, tmp, dq;
+  devbuf<u8> dok;
+  devbuf<unsigned long long> cnt;
+  HIPCHK(h, dx.grow((size_t)n * 8));
+  HIPCHK(h, dy.grow((size_t)n * 8));
+  HIPCHK(h, slab.grow((size_t)n * TR_SLAB_WORDS));
+  HIPCHK(h, tmp.grow((size_t)R * nt * 27));
+  HIPCHK(h, dq.grow((size_t)n * 8));
+  HIPCHK(h, dok.grow(n));
+  HIPCHK(h, cnt.grow(1));
   HIPCHK(h, hipMemcpyAsync(dx.p, x, (size_t)n * 32, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(dy.p, y, (size_t)n * 32, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemsetAsync(cnt.p, 0, 8, h->stream));

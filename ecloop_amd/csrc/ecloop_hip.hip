@@ -27,6 +27,23 @@
 #include "tr_kernels.h"
 #include "aux_kernels.h"
 #include "herd_kernel.h"
+#include "devbuf.h"
+
+// the two kinds of memory the library owns (devbuf.h): device memory, and page-locked host memory for its own staging
+struct dev_mem {
+  typedef hipError_t error;
+  static constexpr hipError_t ok = hipSuccess;
+  static hipError_t alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+  static void free(void* p) { (void)hipFree(p); }
+};
+struct pin_mem {
+  typedef hipError_t error;
+  static constexpr hipError_t ok = hipSuccess;
+  static hipError_t alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+  static void free(void* p) { (void)hipHostFree(p); }
+};
+template <typename T> using devbuf = growbuf<T, dev_mem>;
+template <typename T> using pinbuf = growbuf<T, pin_mem>;
 
 // ------------------------------------------------------------------------------------------------ context
 
@@ -41,38 +58,37 @@ struct ecl_hip {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::string err;
-  // device buffers
-  u32* d_tab = nullptr;  u32 tab_B = 0;        // table for (B, offs)
-  u32* d_gtab = nullptr;                       // fixed-base window table for `mul` (19 x 16383 affine points)
-  u32* d_aux = nullptr;                        // [0]=C0, [1]=jump, [2..33]=ladder : 34 points x 16 words
-  u32* d_auxk = nullptr;                       // scalars for the above
-  uint4* d_cxy = nullptr; size_t cxy_T = 0;
-  uint4* d_ctab = nullptr; size_t ctab_cap = 0;  // (g + 1) * D, g < T, for the geometry of d_aux (k_init_centres_table)
+  // device buffers (devbuf / pinbuf: each owns its memory and knows how many elements it holds; the context's destructor frees them)
+  devbuf<u32> d_tab; u32 tab_B = 0;            // table for (B, offs): tab_B = the half group its contents were built for
+  devbuf<u32> d_gtab;                          // fixed-base window table for `mul` (19 x 16383 affine points)
+  devbuf<u32> d_aux;                           // [0]=C0, [1]=jump, [2..33]=ladder : 34 points x 16 words
+  devbuf<u32> d_auxk;                          // scalars for the above
+  devbuf<uint4> d_cxy;                         // lane centres: 4 per lane
+  devbuf<uint4> d_ctab;                        // (g + 1) * D, g < T, for the geometry of d_aux (k_init_centres_table): 4 per lane
   bool ctab_valid = false;
-  uint4* d_scr = nullptr; u32* d_scr2 = nullptr; size_t scr_elems = 0;  // prefix-product chains
-  u64* d_bloom = nullptr; u64 bloom_words = 0;
+  devbuf<uint4> d_scr; devbuf<u32> d_scr2;     // prefix-product chains (ensure_scratch)
+  devbuf<u64> d_bloom; u64 bloom_words = 0;
   u32 prefix_n = 0;  // ECL_PREFIX: d_bloom holds the stage-1 bitmap (PREFIX_BITMAP_WORDS64 words) and behind it the table of prefix_n ranges
   // `mul`: scalars travel in pieces through MUL_NBUF device buffers (and as many pinned staging buffers for pageable callers), the copy
   // engine running up to MUL_NBUF - 1 pieces ahead of the kernel
-  u32* d_kbuf[MUL_NBUF] = {}; u32* pin_k[MUL_NBUF] = {}; u32 kbuf_cap = 0, pin_cap = 0;
-  u32* d_multmp[2] = {};                       // parked window sums of one piece (144 bytes per scalar), one space per compute stream
+  devbuf<u32> d_kbuf[MUL_NBUF]; pinbuf<u32> pin_k[MUL_NBUF]; u32 kbuf_cap = 0;  // kbuf_cap: scalars of a piece, once d_kbuf and d_multmp all hold them
+  devbuf<u32> d_multmp[2];                     // parked window sums of one piece (144 bytes per scalar), one space per compute stream
   const u32* d_multab = nullptr; u32 multab_W = 0;  // `mul`'s window table in use: one per (device, width), shared by the contexts
   u32 mul_W_fixed = 0;                         // ecl_hip_set_mul_window: 0 = automatic
   uint64_t mul_seen = 0;                       // scalars this context has multiplied (never reset: the automatic width goes by it)
   bool mul_long_failed = false;                // the long table could not be allocated: do not try again
-  void* d_ver = nullptr; u32 ver_cap = 0;      // staging of ecl_hip_verify
+  devbuf<u8> d_ver;                            // staging of ecl_hip_verify: 76 bytes per scalar
   // Taproot (ECL_TR): the slab of `add` (t, P' of up to one slab of keys, 96 bytes each) and the parking space of its k_tr_check; one slab
   // per compute stream for the pieces of `mul`; the mark the next emit launch gives its entries (tr_emit)
-  u32* d_trslab = nullptr; u64 trslab_cap = 0; u32* d_trtmp[2] = {}; u64 trtmp_words = 0;
-  u32* d_trslab_mul[2] = {}; u32 trslab_mul_cap = 0;
+  devbuf<u32> d_trslab, d_trtmp[2], d_trslab_mul[2];
   u32 tr_epoch = 0, tr_epoch_mul[2] = {};
-  u32* d_rawtext = nullptr; size_t rawtext_cap = 0; u64* d_rawlines = nullptr; u32 rawlines_cap = 0;  // `mul -raw`: text and line table of one call
+  devbuf<u32> d_rawtext; devbuf<u64> d_rawlines;  // `mul -raw`: text and line table of one call
   hipStream_t copy_stream = nullptr, stream2 = nullptr;  // `mul`: the copy engine's stream; the second compute stream (pieces alternate)
   hipEvent_t ev_copied[MUL_NBUF] = {}, ev_free[MUL_NBUF] = {}, ev_fork = nullptr, ev_join = nullptr;
   hipStream_t prep_stream = nullptr; hipEvent_t ev_hashed[MUL_NBUF] = {};  // `mul -raw`: the lines are hashed on a stream of their own, ahead of the pieces
-  u32* d_list = nullptr; u64 list_n = 0;       // optional sorted hash list (exact confirm on the device)
-  ecl_found_dev* d_found = nullptr; u32 found_cap = 0;
-  u32* d_counter = nullptr; u32* pin_counter = nullptr;  // (the counters' page-locked host copy: read back by the copy engine, no compute slot needed)
+  devbuf<u32> d_list; u64 list_n = 0;          // optional sorted hash list (exact confirm on the device)
+  devbuf<ecl_found_dev> d_found;
+  devbuf<u32> d_counter; pinbuf<u32> pin_counter;  // (the counters' page-locked host copy: read back by the copy engine, no compute slot needed)
   // key coverage (ecl_hip_get_coverage): keys / scalars of the calls that launched or were served from a sweep, those of them whose device
   // count matched, and the keys the kernels of this context's launches counted; never reset
   uint64_t cov_requested = 0, cov_covered = 0, cov_device = 0;
@@ -92,7 +108,7 @@ struct ecl_hip {
   u32 origin_w[16] = {}, walk_origin[16] = {};
   // ECL_HERD: the resident herd (22 words per kangaroo), its jump table, and the sixteen limbs it was built from: a call continues the
   // herd only if its block equals them
-  u32* d_herd = nullptr; u32 herd_cap = 0; u32* d_herdtab = nullptr;
+  devbuf<u32> d_herd, d_herdtab;
   uint64_t herd_blk[16] = {}; bool herd_valid = false;
   LA_CONTEXT_MEMBERS
   // timing
@@ -110,11 +126,6 @@ struct ecl_hip {
     }                                                                                      \
   } while (0)
 
-template <typename T>
-struct dbuf {
-  T* p = nullptr;
-  ~dbuf() { if (p) (void)hipFree(p); }
-};
 
 static void release_multable(struct ecl_hip* h);
 static void la_leave(struct ecl_hip* h);
@@ -178,13 +189,13 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   HIPCHK(h, hipEventCreate(&h->ev1));
   HIPCHK(h, hipEventCreate(&h->ev_s0));
   HIPCHK(h, hipEventCreate(&h->ev_s1));
-  HIPCHK(h, hipMalloc(&h->d_aux, (ECL_AUX_WORDS + 1) * sizeof(u32)));
-  HIPCHK(h, hipMalloc(&h->d_auxk, 34 * 8 * sizeof(u32)));
+  HIPCHK(h, h->d_aux.grow(ECL_AUX_WORDS + 1));
+  HIPCHK(h, h->d_auxk.grow(34 * 8));
   // [0] records appended, [1] records confirmed by the list, [2] [3] input flags of mul_batch_raw, [4] [5] the u64 count of keys hashed
   // (Taproot: of points emitted), [6] [7] Taproot: the u64 count of slab entries that reached k_tr_check's probe step
-  HIPCHK(h, hipMalloc(&h->d_counter, ECL_COUNTER_WORDS * sizeof(u32)));
-  HIPCHK(h, hipHostMalloc((void**)&h->pin_counter, (ECL_COUNTER_WORDS + 1) * sizeof(u32), hipHostMallocDefault));
-  h->pin_counter[ECL_COUNTER_WORDS] = 0;
+  HIPCHK(h, h->d_counter.grow(ECL_COUNTER_WORDS));
+  HIPCHK(h, h->pin_counter.grow(ECL_COUNTER_WORDS + 1));
+  h->pin_counter.p[ECL_COUNTER_WORDS] = 0;
   // the self-test checks the CODE (known answers, walk kernel against the double-and-add kernel): once per process
   // for every (device, kernel selection) is enough - eight handles for eight shards of one scan do not repeat it
   static std::mutex mu;
@@ -207,33 +218,17 @@ void ecl_hip_close(ecl_hip* h) {
   if (!h) return;
   la_leave(h);
   (void)hipSetDevice(h->dev);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  if (h->stream2) (void)hipStreamSynchronize(h->stream2);
-  if (h->prep_stream) (void)hipStreamSynchronize(h->prep_stream);
-  (void)hipFree(h->d_tab), (void)hipFree(h->d_gtab), (void)hipFree(h->d_aux), (void)hipFree(h->d_auxk), (void)hipFree(h->d_cxy), (void)hipFree(h->d_ctab);
-  (void)hipFree(h->d_scr), (void)hipFree(h->d_scr2), (void)hipFree(h->d_bloom), (void)hipFree(h->d_list), (void)hipFree(h->d_found), (void)hipFree(h->d_counter);
-  (void)hipFree(h->d_herd), (void)hipFree(h->d_herdtab);
-  if (h->pin_counter) (void)hipHostFree(h->pin_counter);
-  for (int i = 0; i < MUL_NBUF; ++i) {
-    (void)hipFree(h->d_kbuf[i]);
-    if (h->pin_k[i]) (void)hipHostFree(h->pin_k[i]);
-    if (h->ev_copied[i]) (void)hipEventDestroy(h->ev_copied[i]);
-    if (h->ev_free[i]) (void)hipEventDestroy(h->ev_free[i]);
-    if (h->ev_hashed[i]) (void)hipEventDestroy(h->ev_hashed[i]);
-  }
-  if (h->copy_stream) (void)hipStreamDestroy(h->copy_stream);
-  if (h->stream2) (void)hipStreamDestroy(h->stream2);
-  if (h->prep_stream) (void)hipStreamDestroy(h->prep_stream);
-  if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-  if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-  (void)hipFree(h->d_trslab), (void)hipFree(h->d_trtmp[0]), (void)hipFree(h->d_trtmp[1]), (void)hipFree(h->d_trslab_mul[0]), (void)hipFree(h->d_trslab_mul[1]);
-  (void)hipFree(h->d_multmp[0]), (void)hipFree(h->d_multmp[1]), (void)hipFree(h->d_ver), (void)hipFree(h->d_rawtext), (void)hipFree(h->d_rawlines);
+  // no buffer is freed before every stream of the context has been waited for: the buffers are the context's members and go with it, last
+  for (hipStream_t st : {h->stream, h->stream2, h->copy_stream, h->prep_stream})
+    if (st) (void)hipStreamSynchronize(st);
   release_multable(h);
-  if (h->ev_s0) (void)hipEventDestroy(h->ev_s0);
-  if (h->ev_s1) (void)hipEventDestroy(h->ev_s1);
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
+  for (int i = 0; i < MUL_NBUF; ++i)
+    for (hipEvent_t ev : {h->ev_copied[i], h->ev_free[i], h->ev_hashed[i]})
+      if (ev) (void)hipEventDestroy(ev);
+  for (hipEvent_t ev : {h->ev_fork, h->ev_join, h->ev_s0, h->ev_s1, h->ev0, h->ev1})
+    if (ev) (void)hipEventDestroy(ev);
+  for (hipStream_t st : {h->copy_stream, h->stream2, h->prep_stream, h->stream})
+    if (st) (void)hipStreamDestroy(st);
   delete h;
 }
 
@@ -243,7 +238,7 @@ void ecl_hip_close(ecl_hip* h) {
 #define PREFIX_BITMAP_WORDS64 ((((u64)1 << PREFIX_BUCKET_BITS) / 64u))
 static prefix_t prefix_of(const ecl_hip* h) {
   prefix_t p;
-  p.bitmap = (const u32*)h->d_bloom, p.table = (const u32*)(h->d_bloom + PREFIX_BITMAP_WORDS64);
+  p.bitmap = (const u32*)h->d_bloom.p, p.table = (const u32*)(h->d_bloom.p + PREFIX_BITMAP_WORDS64);
   p.n = h->prefix_n, p.shift = 32u - PREFIX_BUCKET_BITS;
   return p;
 }
@@ -255,13 +250,12 @@ static int prefix_set_table(ecl_hip* h, const u32* table, uint64_t nwords) {
   const u32 n = (u32)(nwords / 5);
   HIPCHK(h, hipSetDevice(h->dev));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (h->d_bloom) HIPCHK(h, hipFree(h->d_bloom));
-  h->d_bloom = nullptr, h->bloom_words = 0, h->prefix_n = 0;
+  h->d_bloom.reset(), h->bloom_words = 0, h->prefix_n = 0;  // (a filter is as large as it is: never kept for a smaller one)
   std::vector<u64> img(PREFIX_BITMAP_WORDS64 + nwords);
   prefix_build_bitmap((u32*)img.data(), table, n, 32u - PREFIX_BUCKET_BITS);
   memcpy(img.data() + PREFIX_BITMAP_WORDS64, table, (size_t)nwords * sizeof(u64));
-  HIPCHK(h, hipMalloc(&h->d_bloom, img.size() * sizeof(u64)));
-  HIPCHK(h, hipMemcpyAsync(h->d_bloom, img.data(), img.size() * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, h->d_bloom.grow(img.size()));
+  HIPCHK(h, hipMemcpyAsync(h->d_bloom.p, img.data(), img.size() * sizeof(u64), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->bloom_words = img.size(), h->prefix_n = n;
   return ECL_OK;
@@ -273,12 +267,11 @@ int ecl_hip_set_bloom(ecl_hip* h, const uint64_t* bits, uint64_t nwords) {
   HIPCHK(h, hipSetDevice(h->dev));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   la_leave(h), h->la_key_valid = false;
-  if (h->d_bloom) HIPCHK(h, hipFree(h->d_bloom));
-  h->d_bloom = nullptr, h->bloom_words = 0;
-  HIPCHK(h, hipMalloc(&h->d_bloom, nwords * sizeof(u64)));
+  h->d_bloom.reset(), h->bloom_words = 0;
+  HIPCHK(h, h->d_bloom.grow(nwords));
   // on the handle's own stream: device threads upload in parallel, each over its own PCIe link; memory from ecl_hip_alloc_host goes
   // by DMA at link rate, a pageable buffer is staged by the runtime
-  HIPCHK(h, hipMemcpyAsync(h->d_bloom, bits, nwords * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->d_bloom.p, bits, nwords * sizeof(u64), hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->bloom_words = nwords;
   la_filter_changed(h, bits, nwords);
@@ -313,12 +306,11 @@ int ecl_hip_set_list(ecl_hip* h, const uint32_t (*h160)[5], uint64_t n) {
   HIPCHK(h, hipSetDevice(h->dev));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   la_leave(h);
-  if (h->d_list) HIPCHK(h, hipFree(h->d_list));
-  h->d_list = nullptr, h->list_n = 0;
+  h->d_list.reset(), h->list_n = 0;
   la_list_changed(h, h160, 0);
   if (n == 0) return ECL_OK;
-  HIPCHK(h, hipMalloc(&h->d_list, n * 20));
-  HIPCHK(h, hipMemcpy(h->d_list, h160, n * 20, hipMemcpyHostToDevice));
+  HIPCHK(h, h->d_list.grow(n * 5));
+  HIPCHK(h, hipMemcpy(h->d_list.p, h160, n * 20, hipMemcpyHostToDevice));
   h->list_n = n;
   la_list_changed(h, h160, n);
   return ECL_OK;
@@ -376,18 +368,18 @@ int ecl_hip_sort_list(ecl_hip* h, uint32_t (*h160)[5], uint64_t n, uint64_t* kep
   u32 nt = (N + 255u) / 256u;
   nt = nt < RSORT_BLOCK ? RSORT_BLOCK : nt > 65536u ? 65536u : nt;
   const u32 L = (N + nt - 1) / nt;
-  dbuf<u32> rec, out, key[2], perm[2], flag, pos, counts, tmp;
-  HIPCHK(h, hipMalloc(&rec.p, (size_t)N * 20));
-  HIPCHK(h, hipMalloc(&out.p, (size_t)N * 20));
+  devbuf<u32> rec, out, key[2], perm[2], flag, pos, counts, tmp;
+  HIPCHK(h, rec.grow((size_t)N * 5));
+  HIPCHK(h, out.grow((size_t)N * 5));
   for (int i = 0; i < 2; ++i) {
-    HIPCHK(h, hipMalloc(&key[i].p, (size_t)N * 4));
-    HIPCHK(h, hipMalloc(&perm[i].p, (size_t)N * 4));
+    HIPCHK(h, key[i].grow(N));
+    HIPCHK(h, perm[i].grow(N));
   }
-  HIPCHK(h, hipMalloc(&flag.p, (size_t)N * 4));
-  HIPCHK(h, hipMalloc(&pos.p, (size_t)N * 4));
-  HIPCHK(h, hipMalloc(&counts.p, (size_t)256 * nt * 4));
+  HIPCHK(h, flag.grow(N));
+  HIPCHK(h, pos.grow(N));
+  HIPCHK(h, counts.grow((size_t)256 * nt));
   const u64 tmp_words = scan_tmp_words((u64)256 * nt) > scan_tmp_words(N) ? scan_tmp_words((u64)256 * nt) : scan_tmp_words(N);
-  HIPCHK(h, hipMalloc(&tmp.p, (size_t)tmp_words * 4));
+  HIPCHK(h, tmp.grow((size_t)tmp_words));
   HIPCHK(h, hipMemcpyAsync(rec.p, h160, (size_t)N * 20, hipMemcpyHostToDevice, h->stream));
   const dim3 grid((N + 255) / 256), blk(256);
   hipLaunchKernelGGL(k_list_iota, grid, blk, 0, h->stream, perm[0].p, N);
@@ -494,18 +486,15 @@ static add_kernel_t pick_add_kernel(u32 flags) {
 // without the search kernel running again.
 #define ECL_RAW_CAP_MIN (1u << 20)
 static int ensure_found(ecl_hip* h, u32 cap) {
-  if (cap <= h->found_cap) return ECL_OK;
+  if (cap <= h->d_found.n) return ECL_OK;
   h->last_held = h->last_total = 0;  // the buffer that held the last call's records goes away
-  if (h->d_found) HIPCHK(h, hipFree(h->d_found));
-  h->d_found = nullptr, h->found_cap = 0;
-  HIPCHK(h, hipMalloc(&h->d_found, (size_t)cap * sizeof(ecl_found_dev)));
-  h->found_cap = cap;
+  HIPCHK(h, h->d_found.grow(cap));
   return ECL_OK;
 }
 
 static u32 raw_cap_of(const ecl_hip*, u32 cap) { return cap > ECL_RAW_CAP_MIN ? cap : ECL_RAW_CAP_MIN; }
 #define ECL_CAP_MAX (1u << 30)  /* records one call can be asked to deliver (32 GB of them); list mode allocates twice the count */
-static u32 found_words_of(const ecl_hip* h, u32 rcap) { return h->d_list ? 2u * rcap : rcap; }  // records to allocate for a call (rcap <= 2^30)
+static u32 found_words_of(const ecl_hip* h, u32 rcap) { return h->d_list.p ? 2u * rcap : rcap; }  // records to allocate for a call (rcap <= 2^30)
 static void found_to_host(ecl_found* out, const ecl_found_dev* tmp, u32 n, bool keep_endo) {
   for (u32 i = 0; i < n; ++i) {
     out[i].key_offset = tmp[i].key_offset;
@@ -516,26 +505,26 @@ static void found_to_host(ecl_found* out, const ecl_found_dev* tmp, u32 n, bool 
 }
 // after the search kernel has been queued on h->stream: optional list confirm, then counters and records to the host
 static int collect_found(ecl_hip* h, u32 cap, u32 rcap, ecl_found* out, u32* nout, bool keep_endo) {
-  const bool lst = h->d_list != nullptr;
+  const bool lst = h->d_list.p != nullptr;
   if (lst) {
     const u32 blocks = (rcap + 255) / 256 < 1024 ? (rcap + 255) / 256 : 1024;
-    hipLaunchKernelGGL(k_list_filter, dim3(blocks), dim3(256), 0, h->stream, h->d_found, h->d_counter, rcap, h->d_list, h->list_n,
-                       h->d_found + rcap, h->d_counter + 1, rcap);
+    hipLaunchKernelGGL(k_list_filter, dim3(blocks), dim3(256), 0, h->stream, h->d_found.p, h->d_counter.p, rcap, h->d_list.p, h->list_n,
+                       h->d_found.p + rcap, h->d_counter.p + 1, rcap);
     HIPCHK(h, hipGetLastError());
   }
   // One read-back and one wait per call, into page-locked memory: a copy into pageable memory goes through a staging kernel, and with
   // a second context's k_mul_check launches filling the chip every small kernel waits milliseconds for a slot (each such wait at the
   // end of a `mul` call is time this context has nothing in flight).  All the words: mul_batch_raw reads its flags from the same copy, and
   // every caller the count of keys hashed (counted_keys).
-  u32* cnts = h->pin_counter;
-  HIPCHK(h, hipMemcpyAsync(cnts, h->d_counter, ECL_COUNTER_WORDS * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+  u32* cnts = h->pin_counter.p;
+  HIPCHK(h, hipMemcpyAsync(cnts, h->d_counter.p, ECL_COUNTER_WORDS * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   const u32 cnt = lst ? cnts[1] : cnts[0];
   const u32 take = cnt < cap ? cnt : cap;
   h->last_at = lst ? rcap : 0, h->last_held = cnt < rcap ? cnt : rcap, h->last_total = cnt, h->last_endo = keep_endo;
   if (take) {
     std::vector<ecl_found_dev> tmp(take);
-    HIPCHK(h, hipMemcpy(tmp.data(), h->d_found + h->last_at, (size_t)take * sizeof(ecl_found_dev), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(tmp.data(), h->d_found.p + h->last_at, (size_t)take * sizeof(ecl_found_dev), hipMemcpyDeviceToHost));
     found_to_host(out, tmp.data(), take, keep_endo);
   }
   *nout = cnt;
@@ -551,7 +540,7 @@ static int collect_found(ecl_hip* h, u32 cap, u32 rcap, ecl_found* out, u32* nou
 // Key coverage.  Every launch of a search kernel counts, on the device, the keys that reach the hash-and-probe step inside its range
 // (add_kernel.h: keys_count / keys_flush) into the u64 at d_counter + 4, which the one read-back of collect_found brings home.  A call whose
 // count differs from the keys it asked for returns ECL_E_COVERAGE: no records, nothing to fetch, and the resident walk is dropped.
-static u64 counted_keys(const ecl_hip* h) { return (u64)h->pin_counter[4] | (u64)h->pin_counter[5] << 32; }
+static u64 counted_keys(const ecl_hip* h) { return (u64)h->pin_counter.p[4] | (u64)h->pin_counter.p[5] << 32; }
 static int coverage_failed(ecl_hip* h, const char* what, u64 want, u64 got, u32* nout) {
   char msg[160];
   snprintf(msg, sizeof msg, "%s: the device hashed %llu keys of the %llu asked for", what, (unsigned long long)got, (unsigned long long)want);
@@ -583,7 +572,7 @@ extern "C" int ecl_hip_fetch_found(ecl_hip* h, uint32_t first, ecl_found* out, u
   const u32 take = h->last_held - first < n ? h->last_held - first : n;
   HIPCHK(h, hipSetDevice(h->dev));
   std::vector<ecl_found_dev> tmp(take);
-  HIPCHK(h, hipMemcpy(tmp.data(), h->d_found + h->last_at + first, (size_t)take * sizeof(ecl_found_dev), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(tmp.data(), h->d_found.p + h->last_at + first, (size_t)take * sizeof(ecl_found_dev), hipMemcpyDeviceToHost));
   found_to_host(out, tmp.data(), take, h->last_endo);
   *got = take;
   return ECL_OK;
@@ -615,9 +604,8 @@ static int default_lanes(ecl_hip* h) {
 
 // table of (i+1)*stride*G, i < B (ctx_precompute_gpoints, main.c:219-246: only x,y of the positive half are stored)
 static int ensure_table(ecl_hip* h) {
-  if (h->d_tab && h->tab_B == h->B) return ECL_OK;
-  if (h->d_tab) HIPCHK(h, hipFree(h->d_tab));
-  h->d_tab = nullptr;
+  if (h->d_tab.p && h->tab_B == h->B) return ECL_OK;
+  h->d_tab.reset(), h->tab_B = 0;  // (a table is as large as its half group)
   const u32 B = h->B;
   std::vector<u32> ks((size_t)B * 8);
   u256 s = sc_pow2(h->offs), cur = s;
@@ -625,14 +613,14 @@ static int ensure_table(ecl_hip* h) {
     words_of(&ks[(size_t)i * 8], cur);
     cur = sc_add(cur, s);
   }
-  dbuf<u32> d_k, d_w;  // freed on every way out (a failed call used to leak them)
-  HIPCHK(h, hipMalloc(&d_k.p, ks.size() * sizeof(u32)));
-  HIPCHK(h, hipMalloc(&d_w.p, (size_t)B * 16 * sizeof(u32)));
-  HIPCHK(h, hipMalloc(&h->d_tab, (size_t)B * ECL_TAB_STRIDE * sizeof(u32)));
+  devbuf<u32> d_k, d_w;  // freed on every way out
+  HIPCHK(h, d_k.grow(ks.size()));
+  HIPCHK(h, d_w.grow((size_t)B * 16));
+  HIPCHK(h, h->d_tab.grow((size_t)B * ECL_TAB_STRIDE));
   HIPCHK(h, hipMemcpyAsync(d_k.p, ks.data(), ks.size() * sizeof(u32), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_mul_g, dim3((B + 63) / 64), dim3(64), 0, h->stream, d_k.p, d_w.p, (u8*)nullptr, B);
   HIPCHK(h, hipGetLastError());
-  hipLaunchKernelGGL(k_tab_to_limbs, dim3((B + 63) / 64), dim3(64), 0, h->stream, d_w.p, h->d_tab, B);
+  hipLaunchKernelGGL(k_tab_to_limbs, dim3((B + 63) / 64), dim3(64), 0, h->stream, d_w.p, h->d_tab.p, B);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->tab_B = B;
@@ -726,32 +714,26 @@ extern "C" int ecl_hip_plan_geometry(ecl_hip* h, uint64_t nkeys, uint32_t* half_
 }
 
 // device buffers of a call with that geometry: lane centres and prefix-product chains
-static int ensure_walk_buffers(ecl_hip* h, u32 B, u32 T) {
-  if (h->cxy_T < T) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_cxy) HIPCHK(h, hipFree(h->d_cxy));
-    h->d_cxy = nullptr, h->cxy_T = 0, h->walk_valid = false;
-    HIPCHK(h, hipMalloc(&h->d_cxy, (size_t)T * 4 * sizeof(uint4)));
-    h->cxy_T = T;
-  }
-  if (h->ctab_cap < T) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_ctab) HIPCHK(h, hipFree(h->d_ctab));
-    h->d_ctab = nullptr, h->ctab_cap = 0, h->ctab_valid = false, h->aux_B = h->aux_T = 0;
-    HIPCHK(h, hipMalloc(&h->d_ctab, (size_t)T * 4 * sizeof(uint4)));
-    h->ctab_cap = T;
-  }
-  const size_t need = (size_t)T * B * 2;
-  if (h->scr_elems < need) {
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (h->d_scr) HIPCHK(h, hipFree(h->d_scr));
-    if (h->d_scr2) HIPCHK(h, hipFree(h->d_scr2));
-    h->d_scr = nullptr, h->d_scr2 = nullptr, h->scr_elems = 0;
-    HIPCHK(h, hipMalloc(&h->d_scr, need * sizeof(uint4)));
-    HIPCHK(h, hipMalloc(&h->d_scr2, (need / 2) * sizeof(u32)));
-    h->scr_elems = need;
-  }
+// the chains of the add walk and of the herd: `need` 16-byte elements and half as many words
+static int ensure_scratch(ecl_hip* h, size_t need) {
+  if (h->d_scr.n >= need && h->d_scr2.n >= need / 2) return ECL_OK;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  HIPCHK(h, h->d_scr.grow(need));
+  HIPCHK(h, h->d_scr2.grow(need / 2));
   return ECL_OK;
+}
+static int ensure_walk_buffers(ecl_hip* h, u32 B, u32 T) {
+  if (h->d_cxy.n < (size_t)T * 4) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->walk_valid = false;
+    HIPCHK(h, h->d_cxy.grow((size_t)T * 4));
+  }
+  if (h->d_ctab.n < (size_t)T * 4) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->ctab_valid = false, h->aux_B = h->aux_T = 0;
+    HIPCHK(h, h->d_ctab.grow((size_t)T * 4));
+  }
+  return ensure_scratch(h, (size_t)T * B * 2);
 }
 
 static int ensure_gtable(ecl_hip* h);
@@ -808,7 +790,7 @@ static int add_launch(ecl_hip* h, const u256& k0, uint64_t nkeys, u32 rcap, bool
   bool cont = h->walk_valid && h->walk_T == T && h->walk_B == B && u256_eq(h->walk_next, k0);
   const bool origin = h->flags & ECL_ORIGIN;
   if (origin && memcmp(h->walk_origin, h->origin_w, sizeof h->origin_w) != 0) cont = false;  // another origin: re-position
-  h->pin_counter[ECL_COUNTER_WORDS] = 0;
+  h->pin_counter.p[ECL_COUNTER_WORDS] = 0;
   if (!cont) {
     if ((rc = ensure_gtable(h)) != ECL_OK) return rc;
     HIPCHK(h, hipEventRecord(h->ev_s0, h->stream));
@@ -823,16 +805,16 @@ static int add_launch(ecl_hip* h, const u256& k0, uint64_t nkeys, u32 rcap, bool
         words_of(&ks[(size_t)(1 + j) * 8], l);
         l = sc_add(l, l);
       }
-      HIPCHK(h, hipMemcpyAsync(h->d_auxk, ks.data(), ks.size() * sizeof(u32), hipMemcpyHostToDevice, h->stream));
-      hipLaunchKernelGGL(k_mul_g, dim3(1), dim3(64), 0, h->stream, h->d_auxk, h->d_aux + 16, (u8*)nullptr, 33u);
+      HIPCHK(h, hipMemcpyAsync(h->d_auxk.p, ks.data(), ks.size() * sizeof(u32), hipMemcpyHostToDevice, h->stream));
+      hipLaunchKernelGGL(k_mul_g, dim3(1), dim3(64), 0, h->stream, h->d_auxk.p, h->d_aux.p + 16, (u8*)nullptr, 33u);
       HIPCHK(h, hipGetLastError());
-      HIPCHK(h, hipMemcpyAsync(h->jump_host, h->d_aux + 16, 16 * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipMemcpyAsync(h->jump_host, h->d_aux.p + 16, 16 * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
       // ... and so do the multiples (g + 1) * D, g < T (D = 2B * 2^offs * G = the first ladder point): the lane centres C_0 = D, D = D
       if (B >= 8)
-        hipLaunchKernelGGL(k_init_centres_batched, dim3((T / INIT_R + 255) / 256), dim3(256), 0, h->stream, h->d_aux + 32, h->d_aux + 32,
-                           h->d_ctab, T, (u32*)h->d_scr);
+        hipLaunchKernelGGL(k_init_centres_batched, dim3((T / INIT_R + 255) / 256), dim3(256), 0, h->stream, h->d_aux.p + 32, h->d_aux.p + 32,
+                           h->d_ctab.p, T, (u32*)h->d_scr.p);
       else
-        hipLaunchKernelGGL(k_init_centres, dim3(T / 256), dim3(256), 0, h->stream, h->d_aux + 32, h->d_aux + 32, h->d_ctab, T);
+        hipLaunchKernelGGL(k_init_centres, dim3(T / 256), dim3(256), 0, h->stream, h->d_aux.p + 32, h->d_aux.p + 32, h->d_ctab.p, T);
       HIPCHK(h, hipGetLastError());
       HIPCHK(h, hipStreamSynchronize(h->stream));
       h->aux_B = B, h->aux_T = T, h->ctab_valid = true;
@@ -845,41 +827,41 @@ static int add_launch(ecl_hip* h, const u256& k0, uint64_t nkeys, u32 rcap, bool
     const bool from_table = h->ctab_valid && (es.w[0] | es.w[1] | es.w[2] | es.w[3]) != 0;
     scalar_arg c0;
     words_of(c0.w, from_table ? es : c0s);
-    hipLaunchKernelGGL(k_mul_window_one, dim3(1), dim3(64), 0, h->stream, c0, h->d_gtab, h->d_aux);
+    hipLaunchKernelGGL(k_mul_window_one, dim3(1), dim3(64), 0, h->stream, c0, h->d_gtab.p, h->d_aux.p);
     HIPCHK(h, hipGetLastError());
     if (origin) {  // the base point shifted by O; the flag comes home with the call's one wait (add_core)
       origin_arg o;
       memcpy(o.w, h->origin_w, sizeof o.w);
-      hipLaunchKernelGGL(k_origin_add, dim3(1), dim3(64), 0, h->stream, h->d_aux, o, h->d_aux + ECL_AUX_WORDS);
+      hipLaunchKernelGGL(k_origin_add, dim3(1), dim3(64), 0, h->stream, h->d_aux.p, o, h->d_aux.p + ECL_AUX_WORDS);
       HIPCHK(h, hipGetLastError());
-      HIPCHK(h, hipMemcpyAsync(h->pin_counter + ECL_COUNTER_WORDS, h->d_aux + ECL_AUX_WORDS, sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipMemcpyAsync(h->pin_counter.p + ECL_COUNTER_WORDS, h->d_aux.p + ECL_AUX_WORDS, sizeof(u32), hipMemcpyDeviceToHost, h->stream));
       memcpy(h->walk_origin, h->origin_w, sizeof h->walk_origin);
     }
     if (from_table && T >= (1u << 19))
-      hipLaunchKernelGGL(k_init_centres_table<8u>, dim3((T / 8u + 255) / 256), dim3(256), 0, h->stream, h->d_aux, h->d_ctab, h->d_cxy, T);
+      hipLaunchKernelGGL(k_init_centres_table<8u>, dim3((T / 8u + 255) / 256), dim3(256), 0, h->stream, h->d_aux.p, h->d_ctab.p, h->d_cxy.p, T);
     else if (from_table)
-      hipLaunchKernelGGL(k_init_centres_table<4u>, dim3((T / 4u + 255) / 256), dim3(256), 0, h->stream, h->d_aux, h->d_ctab, h->d_cxy, T);
+      hipLaunchKernelGGL(k_init_centres_table<4u>, dim3((T / 4u + 255) / 256), dim3(256), 0, h->stream, h->d_aux.p, h->d_ctab.p, h->d_cxy.p, T);
     else if (B >= 8)  // the chain scratch (T * B * 36 bytes) holds the 144 bytes per lane the batched set-up parks
-      hipLaunchKernelGGL(k_init_centres_batched, dim3((T / INIT_R + 255) / 256), dim3(256), 0, h->stream, h->d_aux, h->d_aux + 32,
-                         h->d_cxy, T, (u32*)h->d_scr);
+      hipLaunchKernelGGL(k_init_centres_batched, dim3((T / INIT_R + 255) / 256), dim3(256), 0, h->stream, h->d_aux.p, h->d_aux.p + 32,
+                         h->d_cxy.p, T, (u32*)h->d_scr.p);
     else
-      hipLaunchKernelGGL(k_init_centres, dim3(T / 256), dim3(256), 0, h->stream, h->d_aux, h->d_aux + 32, h->d_cxy, T);
+      hipLaunchKernelGGL(k_init_centres, dim3(T / 256), dim3(256), 0, h->stream, h->d_aux.p, h->d_aux.p + 32, h->d_cxy.p, T);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->ev_s1, h->stream));
     h->walk_T = T, h->walk_B = B;
   }
   add_args a;
-  a.tab = h->d_tab;
+  a.tab = h->d_tab.p;
   memcpy(a.jump, h->jump_host, sizeof a.jump);
-  a.cxy = h->d_cxy, a.scratch = h->d_scr, a.scratch2 = h->d_scr2;
-  a.bloom = bloom_make(h->d_bloom, h->bloom_words);
+  a.cxy = h->d_cxy.p, a.scratch = h->d_scr.p, a.scratch2 = h->d_scr2.p;
+  a.bloom = bloom_make(h->d_bloom.p, h->bloom_words);
   if (h->flags & ECL_PREFIX) a.prefix = prefix_of(h);
-  a.found = h->d_found, a.counter = h->d_counter, a.cap = rcap, a.keys = (unsigned long long*)(h->d_counter + 4);
+  a.found = h->d_found.p, a.counter = h->d_counter.p, a.cap = rcap, a.keys = (unsigned long long*)(h->d_counter.p + 4);
   if (slab) a.slab = slab, a.epoch = epoch;
   a.B = B, a.T = T, a.nb = nb, a.nkeys = nkeys;
   if (h->diag_drop) h->diag_drop = false, a.nb = nb - 1;  // (test hook: lane 0's last group is in the range, so keys go missing)
   if (own_call) {
-    HIPCHK(h, hipMemsetAsync(h->d_counter, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
+    HIPCHK(h, hipMemsetAsync(h->d_counter.p, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
     HIPCHK(h, hipEventRecord(h->ev0, h->stream));
   }
   hipLaunchKernelGGL(pick_add_kernel(h->flags), dim3(T / ECL_ADD_BLOCK), dim3(ECL_ADD_BLOCK), 0, h->stream, a);
@@ -911,7 +893,7 @@ static int add_core(ecl_hip* h, const u256& k0, uint64_t nkeys, ecl_found* out, 
     h->setup_ms += ms, h->setups += 1;
   }
   if (check_coverage(h, "add_range", nkeys, rc, nout) == ECL_E_COVERAGE) return ECL_E_COVERAGE;
-  if ((h->flags & ECL_ORIGIN) && h->pin_counter[ECL_COUNTER_WORDS]) {  // origin + base point = the point at infinity: nothing was walked from it
+  if ((h->flags & ECL_ORIGIN) && h->pin_counter.p[ECL_COUNTER_WORDS]) {  // origin + base point = the point at infinity: nothing was walked from it
     h->err = "the origin is the negative of the walk's base point";
     h->walk_valid = false, h->last_held = h->last_total = 0;
     return ECL_E_RANGE;
@@ -945,8 +927,8 @@ static bool origin_from_limbs(u32 w[16], const uint64_t xy[8]) {
 // fingerprint of what a filter / a list holds, computed over ALL of its words where they are resident (k_fingerprint, aux_kernels.h: a 6 GB
 // filter takes 2 ms): contexts share sweeps only if flags, stride, sizes and these agree.  A failure here only switches the look-ahead off.
 static bool la_device_fingerprint(ecl_hip* h, const void* d_words, u64 nwords64, u64* fp) {
-  dbuf<unsigned long long> acc;
-  if (hipMalloc(&acc.p, 8) != hipSuccess || hipMemsetAsync(acc.p, 0, 8, h->stream) != hipSuccess) return false;
+  devbuf<unsigned long long> acc;
+  if (acc.grow(1) != hipSuccess ||hipMemsetAsync(acc.p, 0, 8, h->stream) != hipSuccess) return false;
   const u64 blocks = (nwords64 + 255) / 256;
   hipLaunchKernelGGL(k_fingerprint, dim3((unsigned)(blocks < 16384 ? (blocks ? blocks : 1) : 16384)), dim3(256), 0, h->stream, (const u64*)d_words, nwords64, acc.p);
   unsigned long long v = 0;
@@ -956,14 +938,14 @@ static bool la_device_fingerprint(ecl_hip* h, const void* d_words, u64 nwords64,
   *fp = v;
   return true;
 }
-static void la_filter_changed(ecl_hip* h, const uint64_t*, uint64_t nwords) { h->la_key_valid = la_device_fingerprint(h, h->d_bloom, nwords, &h->la_bloom_fp); }
+static void la_filter_changed(ecl_hip* h, const uint64_t*, uint64_t nwords) { h->la_key_valid = la_device_fingerprint(h, h->d_bloom.p, nwords, &h->la_bloom_fp); }
 static void la_list_changed(ecl_hip* h, const uint32_t (*list)[5], uint64_t n) {
   h->la_list_fp = 0;
   if (!n) return;
   // the list's 20-byte entries as 64-bit words (n * 5 / 2, a last odd 32-bit word left to the entry count in the key: lists are sorted and
   // unique, so two lists that agree in everything but that word differ in it alone - it is added from the host copy)
   u64 fp = 0;
-  if (!la_device_fingerprint(h, h->d_list, n * 5 / 2, &fp)) h->la_key_valid = false;
+  if (!la_device_fingerprint(h, h->d_list.p, n * 5 / 2, &fp)) h->la_key_valid = false;
   if ((n * 5) & 1) fp += 0x9E3779B97F4A7C15ull * ((u64)list[n - 1][4] + 1);
   h->la_list_fp = fp;
 }
@@ -978,7 +960,7 @@ extern "C" int ecl_hip_add_range(ecl_hip* h, const uint64_t start[4], uint64_t n
     HIPCHK(h, hipSetDevice(h->dev));
     return count_call(h, nkeys, herd_add_core(h, start, nkeys, out, cap, nout));
   }
-  if (!h->d_bloom) return ECL_E_NOBLOOM;
+  if (!h->d_bloom.p) return ECL_E_NOBLOOM;
   if (nkeys == 0) return ECL_OK;
   HIPCHK(h, hipSetDevice(h->dev));
   const u256 k0 = sc_reduce(u256_from(start));
