@@ -29,7 +29,7 @@ static int herd_parse(ecl_hip* h, const uint64_t blk[16], herd_params& p) {
   return ECL_OK;
 }
 
-// table and starts of a new herd, queued on h->stream and waited for; the flag word d_counter[6] (zeroed by the caller) comes home in *flags
+// table and starts of a new herd, queued on h->stream and waited for; the flag word CW_HERD_FLAGS (zeroed by the caller) comes home in *flags
 static int herd_build(ecl_hip* h, const herd_params& p, u32* flags) {
   const u32 H = 1u << p.herd_log2;
   HIPCHK(h, h->d_herd.grow((size_t)H * 22));  // (every launch on the herd was waited for by its call's read-back)
@@ -82,7 +82,7 @@ static int herd_build(ecl_hip* h, const herd_params& p, u32* flags) {
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipStreamSynchronize(h->stream));  // the host buffers are filled again
   }
-  HIPCHK(h, hipMemcpy(flags, h->d_counter.p + 6, sizeof(u32), hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemcpy(flags, h->d_counter.p + CW_HERD_FLAGS, sizeof(u32), hipMemcpyDeviceToHost));
   return ECL_OK;
 }
 
@@ -97,12 +97,11 @@ static int herd_add_core(ecl_hip* h, const uint64_t blk[16], uint64_t nkeys, ecl
     h->err = "nkeys is not a multiple of the herd";
     return ECL_E_ARG;
   }
-  h->last_held = h->last_total = 0, h->last_from_host = false;
-  const u32 rcap = raw_cap_of(h, cap ? cap : 1);
-  if ((rc = ensure_found(h, rcap)) != ECL_OK) return rc;
+  call_frame f = {h, "add_range", nullptr, nkeys, out, cap, nout, false, true};
+  if ((rc = f.begin()) != ECL_OK) return rc;
   const u32 L = (H + HERD_M - 1) / HERD_M, grid = (L + HERD_BLOCK - 1) / HERD_BLOCK, T = grid * HERD_BLOCK;
   if ((rc = ensure_scratch(h, (size_t)T * HERD_M * 2)) != ECL_OK) return rc;
-  HIPCHK(h, hipMemsetAsync(h->d_counter.p, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
+  if ((rc = f.reset()) != ECL_OK) return rc;
   const bool cont = h->herd_valid && memcmp(h->herd_blk, blk, sizeof h->herd_blk) == 0;
   if (!cont) {
     h->herd_valid = false;
@@ -110,18 +109,19 @@ static int herd_add_core(ecl_hip* h, const uint64_t blk[16], uint64_t nkeys, ecl
     HIPCHK(h, hipEventRecord(h->ev_s0, h->stream));
     if ((rc = herd_build(h, p, &flags)) != ECL_OK) return rc;
     HIPCHK(h, hipEventRecord(h->ev_s1, h->stream));
-    if (flags & 2u) {
+    if (flags & HERD_FLAG_INFINITY) {
       h->err = "a kangaroo's start is the point at infinity";
       return ECL_E_RANGE;
     }
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));  // the walk's time starts behind the set-up
   }
+  const add_args c = f.args();  // (no filter: the records, the counters, the jumps counted where the keys are)
   herd_args a;
   a.tab = h->d_herdtab.p, a.state = h->d_herd.p, a.scratch = h->d_scr.p, a.scratch2 = h->d_scr2.p;
-  a.found = (uint4*)h->d_found.p, a.counter = h->d_counter.p, a.jumps = (unsigned long long*)(h->d_counter.p + 4), a.cap = rcap;
+  a.found = (uint4*)c.found, a.counter = c.counter, a.jumps = c.keys, a.cap = c.cap;
   a.H = H, a.L = L, a.T = T, a.dpmask = h->offs >= 32 ? ~0u : (1u << h->offs) - 1u;
   u64 per = (1ull << HERD_LAUNCH_JUMPS_LOG2) >> p.herd_log2;
   if (per > HERD_LAUNCH_STEPS_MAX) per = HERD_LAUNCH_STEPS_MAX;
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
   for (u64 left = nkeys / H; left;) {
     const u64 n = left < per ? left : per;
     a.steps = (u32)n;
@@ -130,28 +130,12 @@ static int herd_add_core(ecl_hip* h, const uint64_t blk[16], uint64_t nkeys, ecl
     HIPCHK(h, hipGetLastError());
     left -= n;
   }
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  u32 cnt = 0;
-  rc = collect_found(h, cap, rcap, out, &cnt, true);
-  if (rc != ECL_OK && rc != ECL_E_OVERFLOW) return rc;
-  float ms = 0;
-  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  h->kernel_ms += ms, h->launches += 1, h->keys += nkeys;
-  if (!cont) {
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev_s0, h->ev_s1));
-    h->setup_ms += ms, h->setups += 1;
-  }
-  if (check_coverage(h, "add_range", nkeys, rc, nout) == ECL_E_COVERAGE) {  // the herd is not where the caller thinks it is: built anew next time
-    h->herd_valid = false;
-    return ECL_E_COVERAGE;
-  }
-  if (h->pin_counter.p[6] & 1u) {
-    h->err = "a kangaroo's distance passed 2^128";
-    h->herd_valid = false, h->last_held = h->last_total = 0;
-    return ECL_E_RANGE;
-  }
+  if ((rc = f.collect()) != ECL_OK) return rc;
+  rc = f.finish(1, cont ? 0 : 1);
+  h->herd_valid = false;
+  if (rc == ECL_E_COVERAGE) return rc;  // the herd is not where the caller thinks it is: built anew next time
+  if (herd_flags(h->pin_counter.p) & HERD_FLAG_DISTANCE) return f.refuse(ECL_E_RANGE, "a kangaroo's distance passed 2^128");
   h->herd_valid = true;
   memcpy(h->herd_blk, blk, sizeof h->herd_blk);
-  *nout = cnt;
   return rc;
 }

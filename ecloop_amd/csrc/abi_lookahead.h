@@ -195,7 +195,7 @@ static int la_sweep(ecl_hip* h, la_region* r) {
   u32 cnt = 0;
   int rc = add_core(h, r->start, r->nkeys, h->la_buf.data(), LA_REC_CAP, &cnt);
   if (rc == ECL_E_OVERFLOW) {
-    if (cnt > h->last_held) return ECL_E_OVERFLOW;  // more hits than the device kept: this filter is too dense to look ahead
+    if (cnt > h->last.held) return ECL_E_OVERFLOW;  // more hits than the device kept: this filter is too dense to look ahead
     r->recs.resize(cnt);
     memcpy(r->recs.data(), h->la_buf.data(), (size_t)LA_REC_CAP * sizeof(ecl_found));
     u32 got = 0;
@@ -247,10 +247,11 @@ static int la_claim_and_sweep(ecl_hip* h, la_group& g, std::unique_lock<std::mut
 }
 
 static int la_fetch(ecl_hip* h, uint32_t first, ecl_found* out, uint32_t n, uint32_t* got) {
-  if (!h->last_region || first >= h->last_host_n || n == 0) return ECL_OK;
-  const u32 take = h->last_host_n - first < n ? h->last_host_n - first : n;
-  const ecl_found* src = h->last_region->recs.data() + h->last_host_at + first;
-  for (u32 i = 0; i < take; ++i) out[i] = src[i], out[i].key_offset -= h->last_host_off;
+  const last_records& l = h->last;
+  if (!l.region || first >= l.n || n == 0) return ECL_OK;
+  const u32 take = l.n - first < n ? l.n - first : n;
+  const ecl_found* src = l.region->recs.data() + l.host_at + first;
+  for (u32 i = 0; i < take; ++i) out[i] = src[i], out[i].key_offset -= l.off;
   *got = take;
   return ECL_OK;
 }
@@ -282,8 +283,7 @@ static int la_add_range(ecl_hip* h, const u256& k0, u64 n, ecl_found* out, u32 c
       const size_t i1 = std::lower_bound(r->recs.begin(), r->recs.end(), hi, cmp) - r->recs.begin();
       const u32 cnt = (u32)(i1 - i0), take = cnt < cap ? cnt : cap;
       for (u32 i = 0; i < take; ++i) out[i] = r->recs[i0 + i], out[i].key_offset -= off;
-      h->last_region = r, h->last_host_at = i0, h->last_host_n = cnt, h->last_host_off = off, h->last_from_host = true;
-      h->last_held = h->last_total = 0;
+      h->last.on_host(r, i0, cnt, off);
       r->consumed += n;
       if (r->consumed >= r->nkeys)
         for (auto it = g.regions.begin(); it != g.regions.end(); ++it)

@@ -145,7 +145,6 @@ static int ensure_multable(ecl_hip* h, u32 W) {
   return ECL_OK;
 }
 
-static u64 tr_checked_keys(const ecl_hip* h);
 extern "C" int ecl_hip_set_mul_window(ecl_hip* h, uint32_t bits) {
   if (!h || (bits != 0 && (bits < MUL_W_MIN || bits > MUL_W_MAX))) return ECL_E_ARG;
   h->mul_W_fixed = bits;
@@ -204,9 +203,9 @@ static int mul_setup(ecl_hip* h, u32 n, u32 W) {
 // MUL_R) as still keep 65536 x ECL_MUL_WAVES threads in flight - what the chip holds at once; a few blocks more would wait for a whole
 // round - in whole workgroups, so that every row of scalars and every parking plane starts on a 1 KiB boundary
 static const u32 MUL_NT = 65536u * ECL_MUL_WAVES;
-static void mul_geometry(u32 m, u32* R_out, u32* nt_out) {
+static void mul_geometry(u32 m, u32 rmax, u32* R_out, u32* nt_out) {  // rmax: MUL_R; TR_R for Taproot's k_tr_check
   u32 R = (m + MUL_NT - 1) / MUL_NT;
-  R = R < 1 ? 1 : (R > MUL_R ? MUL_R : R);
+  R = R < 1 ? 1 : (R > rmax ? rmax : R);
   *R_out = R, *nt_out = ((m + R - 1) / R + 255u) / 256u * 256u;
 }
 // one piece on compute stream `lane` (0: the context's stream, 1: the second one), parking space `lane`; short_round: one scalar per
@@ -216,7 +215,7 @@ static void mul_launch_piece(ecl_hip* h, int lane, const u32* d_k, u32 m, u32 at
   u32 R, nt;
   hipStream_t st = lane ? h->stream2 : h->stream;
   u32* tmp = h->d_multmp[lane].p;
-  mul_geometry(m, &R, &nt);
+  mul_geometry(m, MUL_R, &R, &nt);
   if (short_round) R -= 1;
   dim3 grid(nt / 256), blk(256);
   if (h->flags & ECL_TR) {  // alone (ecl_hip_open): two kernels (abi_tr.h)
@@ -241,22 +240,22 @@ static void mul_launch_piece(ecl_hip* h, int lane, const u32* d_k, u32 m, u32 at
   default: hipLaunchKernelGGL((k_mul_check_p2sh<true, true>), grid, blk, 0, st, d_k, m, at, gtab, a, tmp, nt, R); break;
   }
 }
-// window width of the next call: the caller's, or the short table until this context has seen enough scalars to pay for the long one
-static u32 mul_window_for(const ecl_hip* h, u32 n) {
-  return h->mul_W_fixed ? h->mul_W_fixed : (h->mul_seen + n >= MUL_LONG_AFTER && !h->mul_long_failed ? MUL_W_LONG : MUL_W_START);
-}
-// mul_setup at the width in force; if the automatic choice was the long table and there is no room for it (3.6 GB while it is
-// built), the context stays on the short one for good.  Shared by ecl_hip_mul_batch, ecl_hip_mul_batch_raw and ecl_hip_reserve_mul.
-static int mul_setup_auto(ecl_hip* h, u32 n, u32* W_used) {
-  u32 W = mul_window_for(h, n);
-  int rc = mul_setup(h, n, W);
+// setup(W) at the window width in force for a call of n more scalars: the caller's, or the short table until this context has seen enough
+// scalars to pay for the long one; if the automatic choice was the long table and there is no room for it (3.6 GB while it is built), the
+// context stays on the short one for good.  The `mul` calls set up table and buffers (mul_setup_auto), a Taproot `add` the table (tr_table).
+template <class Setup> static int mul_at_width_in_force(ecl_hip* h, u64 n, u32* W_used, Setup setup) {
+  u32 W = h->mul_W_fixed ? h->mul_W_fixed : (h->mul_seen + n >= MUL_LONG_AFTER && !h->mul_long_failed ? MUL_W_LONG : MUL_W_START);
+  int rc = setup(W);
   if (rc == ECL_E_HIP && !h->mul_W_fixed && W == MUL_W_LONG) {
     (void)hipGetLastError();
     h->mul_long_failed = true, W = MUL_W_START;
-    rc = mul_setup(h, n, W);
+    rc = setup(W);
   }
   *W_used = W;
   return rc;
+}
+static int mul_setup_auto(ecl_hip* h, u32 n, u32* W_used) {
+  return mul_at_width_in_force(h, n, W_used, [&](u32 W) { return mul_setup(h, n, W); });
 }
 
 // The body of a `mul` call, shared by ecl_hip_mul_batch (scalars from the host) and ecl_hip_mul_batch_raw (scalars hashed on the device from
@@ -285,7 +284,6 @@ template <class CopyIn, class Prepare> static int mul_pieces(ecl_hip* h, u32 n, 
   u32 lim = top < unit ? top : (u32)unit;
   const bool drop = h->diag_drop;
   h->diag_drop = false;
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
   HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));  // the second stream starts behind the counters' reset (and behind the call before)
   HIPCHK(h, hipStreamWaitEvent(h->stream2, h->ev_fork, 0));
   for (u32 at = 0, c = 0, m = 0; at < n; at += m, ++c, lim = (u64)lim * 2 <= top ? (u32)((u64)lim * 2) & ~1023u : top) {
@@ -315,7 +313,7 @@ extern "C" int ecl_hip_reserve_mul(ecl_hip* h, uint32_t n, uint32_t cap) {
   if (!h || n == 0 || cap > ECL_CAP_MAX) return ECL_E_ARG;
   HIPCHK(h, hipSetDevice(h->dev));
   int rc;
-  if ((rc = ensure_found(h, found_words_of(h, raw_cap_of(h, cap ? cap : 1)))) != ECL_OK) return rc;
+  if ((rc = ensure_found(h, raw_cap_of(cap))) != ECL_OK) return rc;
   u32 W;
   return mul_setup_auto(h, n, &W);
 }
@@ -328,10 +326,9 @@ extern "C" int ecl_hip_mul_batch(ecl_hip* h, const uint64_t (*scalars)[4], uint3
   if (!h->d_bloom.p) return ECL_E_NOBLOOM;
   if (n == 0) return ECL_OK;
   HIPCHK(h, hipSetDevice(h->dev));
+  call_frame f = {h, "mul_batch", (h->flags & ECL_TR) ? "mul_batch (Taproot, output keys)" : nullptr, n, out, cap, nout, true, false};
   int rc;
-  h->last_held = h->last_total = 0, h->last_from_host = false;  // the records of the call before are about to be overwritten
-  const u32 rcap = raw_cap_of(h, cap ? cap : 1);
-  if ((rc = ensure_found(h, found_words_of(h, rcap))) != ECL_OK) return rc;
+  if ((rc = f.begin()) != ECL_OK) return rc;
   u32 W;
   if ((rc = mul_setup_auto(h, n, &W)) != ECL_OK) return rc;
   const wtab gtab = wtab_make(h->d_multab, W);
@@ -356,16 +353,12 @@ extern "C" int ecl_hip_mul_batch(ecl_hip* h, const uint64_t (*scalars)[4], uint3
   }
   if (!direct)  // (a staging buffer that is too small has not been used since the device buffers grew, and that waited for every stream)
     for (int i = 0; i < MUL_NBUF; ++i) HIPCHK(h, h->pin_k[i].grow((size_t)h->kbuf_cap * 8));
-  add_args a;
-  memset(&a, 0, sizeof a);
-  a.bloom = bloom_make(h->d_bloom.p, h->bloom_words);
-  a.found = h->d_found.p, a.counter = h->d_counter.p, a.cap = rcap, a.keys = (unsigned long long*)(h->d_counter.p + 4);
-  HIPCHK(h, hipMemsetAsync(h->d_counter.p, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
+  if ((rc = f.reset()) != ECL_OK) return rc;
   // Scalars are used as given (4 little-endian u64 = 8 u32 words): the window sum (wtab_sum_fast, any width) is k*G for any
   // 256-bit k, which is (k mod n)*G; k = 0 (mod n) gives the point at infinity and is skipped.
   const bool staged = !direct;
   rc = mul_pieces(
-      h, n, gtab, a,
+      h, n, gtab, f.args(),
       [&](u32 b, u32 at, u32 m) -> int {  // piece `at`'s scalars onto the copy stream
         const void* src = scalars[at];
         if (staged) memcpy(h->pin_k[b].p, scalars[at], (size_t)m * 32), src = h->pin_k[b].p;
@@ -373,20 +366,8 @@ extern "C" int ecl_hip_mul_batch(ecl_hip* h, const uint64_t (*scalars)[4], uint3
         return ECL_OK;
       },
       [](u32, u32, u32, hipEvent_t*) -> int { return ECL_OK; });
-  if (rc != ECL_OK) return rc;
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  u32 cnt = 0;
-  rc = collect_found(h, cap, rcap, out, &cnt, false);
-  *nout = cnt;
-  if (rc == ECL_OK || rc == ECL_E_OVERFLOW) {
-    float ms = 0;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));  // copies + kernels of this call, as the stream saw them
-    h->mul_ms += ms, h->mul_calls += 1, h->mul_scalars += n;
-    rc = check_coverage(h, "mul_batch", n, rc, nout);  // the counts of all pieces, summed on the device
-    if (rc != ECL_E_COVERAGE && (h->flags & ECL_TR) && tr_checked_keys(h) != n)  // Taproot: ... and the entries that reached k_tr_check's probe step
-      rc = coverage_failed(h, "mul_batch (Taproot, output keys)", n, tr_checked_keys(h), nout);
-  }
-  return count_call(h, n, rc);
+  if (rc != ECL_OK || (rc = f.collect()) != ECL_OK) return rc;
+  return count_call(h, n, f.finish());  // (the counts of all pieces, summed on the device)
 }
 
 // `mul -raw`: lines of text in, SHA-256 on the device, then the `mul` body on the digests (n <= 2^26 lines a call): the pieces of
@@ -403,10 +384,9 @@ extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t t
   if (!h->d_bloom.p) return ECL_E_NOBLOOM;
   if (n == 0) return ECL_OK;
   HIPCHK(h, hipSetDevice(h->dev));
+  call_frame f = {h, "mul_batch_raw", (h->flags & ECL_TR) ? "mul_batch_raw" : nullptr, n, out, cap, nout, true, false};
   int rc;
-  h->last_held = h->last_total = 0, h->last_from_host = false;
-  const u32 rcap = raw_cap_of(h, cap ? cap : 1);
-  if ((rc = ensure_found(h, found_words_of(h, rcap))) != ECL_OK) return rc;
+  if ((rc = f.begin()) != ECL_OK) return rc;
   u32 W;
   if ((rc = mul_setup_auto(h, n, &W)) != ECL_OK) return rc;
   const wtab gtab = wtab_make(h->d_multab, W);
@@ -437,24 +417,19 @@ extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t t
     HIPCHK(h, hipStreamCreateWithPriority(&h->prep_stream, hipStreamNonBlocking, hi));  // (lowest priority instead: no difference measured)
     for (int i = 0; i < MUL_NBUF; ++i) HIPCHK(h, hipEventCreateWithFlags(&h->ev_hashed[i], hipEventDisableTiming));
   }
-  add_args a;
-  memset(&a, 0, sizeof a);
-  a.bloom = bloom_make(h->d_bloom.p, h->bloom_words);
-  a.found = h->d_found.p, a.counter = h->d_counter.p, a.cap = rcap, a.keys = (unsigned long long*)(h->d_counter.p + 4);
   u64* d_lines = h->d_rawlines.p;
-  u32* d_flags = h->d_counter.p + 2;  // [0] a line outside the text, [1] a line beyond the part of the text that was on the device when it was hashed
+  u32* d_flags = h->d_counter.p + CW_RAW_OUTSIDE;  // [0] a line outside the text, [1] CW_RAW_LATE: a line beyond the part of the text that was on the device when it was hashed
   u32* d_text = h->d_rawtext.p;
   // The text goes with the pieces: in front of piece c's share of the table, the text up to the end of that share's LAST line - for a
   // table in the order of the text (any caller that cut lines out of a buffer front to back) every line is then on the device when its
   // piece is hashed, and the first piece starts after its own bytes instead of after all of them (300 MB for 2^24 pass phrases: 5 ms of
   // a 20 ms call).  The kernel checks it line by line; a table in another order raises flag [1], and the call is run again with the
   // whole text sent first.  Page-locked text and table (ecl_hip_alloc_host) go by DMA from where they are.
-  u32 flags[2] = {0, 0}, cnt = 0;
-  bool missed = false;  // a pass whose device count differs from n: the call fails even if a second pass was whole
-  u64 missed_got = 0;
+  bool missed = false;  // a pass whose device count differs from n: the call fails, by that pass's verdict, even if a second pass was whole
+  call_verdict short_pass = {};
   for (int pass = 0; pass < 2; ++pass) {
     const bool in_order = pass == 0;
-    HIPCHK(h, hipMemsetAsync(h->d_counter.p, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
+    if ((rc = f.reset()) != ECL_OK) return rc;
     HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));  // the hashing writes the flags: behind their reset
     HIPCHK(h, hipStreamWaitEvent(h->prep_stream, h->ev_fork, 0));
     u32 have = 0;  // bytes of the text on the copy stream so far
@@ -463,7 +438,7 @@ extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t t
       have = text_bytes;
     }
     rc = mul_pieces(
-        h, n, gtab, a,
+        h, n, gtab, f.args(),
         [&](u32, u32 at, u32 m) -> int {  // (the copy stream is in order: the piece's table is behind its text)
           const u64 last = lines[at + m - 1], end = (last & 0xFFFFFFFFull) + (last >> 32);
           const u32 want = at + m == n || end > text_bytes ? text_bytes : (u32)end;
@@ -483,30 +458,13 @@ extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t t
           *ready = h->ev_hashed[b];
           return ECL_OK;
         });
-    if (rc != ECL_OK) return rc;
-    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-    rc = collect_found(h, cap, rcap, out, &cnt, false);  // (the one wait of the call; the flags come back with the counters)
-    if (rc != ECL_OK && rc != ECL_E_OVERFLOW) return rc;
-    flags[0] = h->pin_counter.p[2], flags[1] = h->pin_counter.p[3];
-    const u64 got = counted_keys(h);
-    h->cov_device += got;
-    if (got != n && !missed) missed = true, missed_got = got;
-    if ((h->flags & ECL_TR) && tr_checked_keys(h) != n && !missed) missed = true, missed_got = tr_checked_keys(h);
-    if (flags[0] || !flags[1]) break;
+    if (rc != ECL_OK || (rc = f.collect()) != ECL_OK) return rc;  // (the one wait of the pass; the flags come back with the counters)
+    if (f.v.rc == ECL_E_COVERAGE && !missed) missed = true, short_pass = f.v;
+    if (raw_line_outside(h->pin_counter.p) || !raw_line_late(h->pin_counter.p)) break;
   }
-  if (flags[0]) {
-    h->err = "mul_batch_raw: a line of the table lies outside the text";
-    h->last_held = h->last_total = 0;
-    return ECL_E_ARG;
-  }
-  *nout = cnt;
-  if (rc == ECL_OK || rc == ECL_E_OVERFLOW) {
-    float ms = 0;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-    h->mul_ms += ms, h->mul_calls += 1, h->mul_scalars += n;
-    if (missed) rc = coverage_failed(h, "mul_batch_raw", n, missed_got, nout);
-  }
-  return count_call(h, n, rc);
+  if (raw_line_outside(h->pin_counter.p)) return f.refuse(ECL_E_ARG, "mul_batch_raw: a line of the table lies outside the text");
+  if (missed) f.v = short_pass;
+  return count_call(h, n, f.finish());
 }
 
 // Split-key contexts (ECL_PREFIX | ECL_ORIGIN): an entry of ecl_hip_verify / ecl_hip_verify_eth is twelve limbs - the scalar, then x and y of

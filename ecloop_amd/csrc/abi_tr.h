@@ -14,11 +14,7 @@ static u64 tr_slab_keys() {
 // stage B walks a slab in launches of TR_CHUNK entries - what the chip holds at once at TR_R keys per thread, the size of `mul`'s full
 // pieces - alternating between the context's two compute streams, each with its own parking space, as `mul`'s pieces do
 #define TR_CHUNK (MUL_NT * TR_R)
-static void tr_geometry(u32 m, u32* R_out, u32* nt_out) {  // (m > TR_CHUNK - a long piece of `mul`: more threads than are resident)
-  u32 R = (m + MUL_NT - 1) / MUL_NT;
-  R = R < 1 ? 1 : (R > TR_R ? TR_R : R);
-  *R_out = R, *nt_out = ((m + R - 1) / R + 255u) / 256u * 256u;
-}
+static void tr_geometry(u32 m, u32* R, u32* nt) { mul_geometry(m, TR_R, R, nt); }  // (m > TR_CHUNK - a long piece of `mul`: more threads than are resident)
 static u64 tr_tmp_words(u64 m) {
   u32 R, nt;
   tr_geometry((u32)(m < TR_CHUNK ? m : TR_CHUNK), &R, &nt);
@@ -26,13 +22,8 @@ static u64 tr_tmp_words(u64 m) {
 }
 // the `mul` table of a Taproot `add` call of nkeys keys: the width policy and accounting of `mul` - tweaked keys are scalars seen
 static int tr_table(ecl_hip* h, u64 nkeys, wtab* gtab) {
-  u32 W = h->mul_W_fixed ? h->mul_W_fixed : (h->mul_seen + nkeys >= MUL_LONG_AFTER && !h->mul_long_failed ? MUL_W_LONG : MUL_W_START);
-  int rc = ensure_multable(h, W);
-  if (rc == ECL_E_HIP && !h->mul_W_fixed && W == MUL_W_LONG) {
-    (void)hipGetLastError();
-    h->mul_long_failed = true, W = MUL_W_START;
-    rc = ensure_multable(h, W);
-  }
+  u32 W;
+  const int rc = mul_at_width_in_force(h, nkeys, &W, [&](u32 w) { return ensure_multable(h, w); });
   if (rc == ECL_OK) *gtab = wtab_make(h->d_multab, W);
   return rc;
 }
@@ -63,12 +54,9 @@ static int tr_reserve(ecl_hip* h, uint64_t nkeys) {
   call_geometry(h, m, B, nb, T);
   return ensure_walk_buffers(h, B, T);
 }
-// stage B over `m` entries of `slab` (m <= TR_CHUNK) on stream `st`: records with key_offset = base + entry index, counted into d_counter + 6
-static int tr_launch_check(ecl_hip* h, hipStream_t st, const u32* slab, u32 m, u64 base, const wtab& gtab, u32 rcap, u32 epoch, u32* tmp) {
-  add_args a;
-  memset(&a, 0, sizeof a);
-  a.bloom = bloom_make(h->d_bloom.p, h->bloom_words);
-  a.found = h->d_found.p, a.counter = h->d_counter.p, a.cap = rcap, a.keys = (unsigned long long*)(h->d_counter.p + 6);
+// stage B over `m` entries of `slab` (m <= TR_CHUNK) on stream `st`: records with key_offset = base + entry index, counted where `a` says
+// (the frame's args(CW_TR_CHECKED))
+static int tr_launch_check(ecl_hip* h, hipStream_t st, const u32* slab, u32 m, u64 base, const wtab& gtab, const add_args& a, u32 epoch, u32* tmp) {
   u32 R, nt;
   tr_geometry(m, &R, &nt);
   hipLaunchKernelGGL(k_tr_check<false>, dim3(nt / 256), dim3(256), 0, st, slab, m, base, gtab, a, epoch, tmp, nt, R, (u32*)nullptr, (u8*)nullptr);
@@ -77,7 +65,7 @@ static int tr_launch_check(ecl_hip* h, hipStream_t st, const u32* slab, u32 m, u
 }
 // ... over a whole slab of the `add` path, which the emit kernel has just been queued for on h->stream: the second stream joins in behind
 // it, and h->stream goes on (the next slab's emit kernel, the read-back) when both are done
-static int tr_check_slab(ecl_hip* h, u64 m, u64 at, const wtab& gtab, u32 rcap, u32 epoch) {
+static int tr_check_slab(ecl_hip* h, u64 m, u64 at, const wtab& gtab, const add_args& a, u32 epoch) {
   const bool two = m > TR_CHUNK;
   if (two) {
     HIPCHK(h, hipEventRecord(h->ev_fork, h->stream));
@@ -88,7 +76,7 @@ static int tr_check_slab(ecl_hip* h, u64 m, u64 at, const wtab& gtab, u32 rcap, 
   for (u64 off = 0; off < m; ++c) {
     const u64 n = m - off < even ? m - off : even;
     const int lane = two ? (int)(c & 1u) : 0;
-    int rc = tr_launch_check(h, lane ? h->stream2 : h->stream, h->d_trslab.p + (size_t)off * TR_SLAB_WORDS, (u32)n, at + off, gtab, rcap, epoch, h->d_trtmp[lane].p);
+    int rc = tr_launch_check(h, lane ? h->stream2 : h->stream, h->d_trslab.p + (size_t)off * TR_SLAB_WORDS, (u32)n, at + off, gtab, a, epoch, h->d_trtmp[lane].p);
     if (rc != ECL_OK) return rc;
     off += n;
   }
@@ -98,7 +86,6 @@ static int tr_check_slab(ecl_hip* h, u64 m, u64 at, const wtab& gtab, u32 rcap, 
   }
   return ECL_OK;
 }
-static u64 tr_checked_keys(const ecl_hip* h) { return (u64)h->pin_counter.p[6] | (u64)h->pin_counter.p[7] << 32; }
 
 // ecl_hip_add_range's body on a Taproot context.  A call of 2^32 keys cannot park 2^32 x 96 bytes, so it is walked in slabs of contiguous
 // sub-launches of the emit kernel (the points come from the walk), each followed by k_tr_check over the slab, all on the context's
@@ -107,52 +94,32 @@ static u64 tr_checked_keys(const ecl_hip* h) { return (u64)h->pin_counter.p[6] |
 // ECL_E_OVERFLOW, ecl_hip_fetch_found, list mode and the look-ahead see one call.  The call is whole if the points emitted AND the
 // entries that reached the probe step both equal nkeys.
 static int tr_add_core(ecl_hip* h, const u256& k0, uint64_t nkeys, ecl_found* out, uint32_t cap, uint32_t* nout) {
+  call_frame f = {h, "add_range (Taproot, points emitted)", "add_range (Taproot, output keys)", nkeys, out, cap, nout, false, false};
   int rc;
-  h->last_held = h->last_total = 0, h->last_from_host = false;
-  const u32 rcap = raw_cap_of(h, cap ? cap : 1);
-  if ((rc = ensure_found(h, found_words_of(h, rcap))) != ECL_OK) return rc;
+  if ((rc = f.begin()) != ECL_OK) return rc;
   wtab gtab;
   if ((rc = tr_table(h, nkeys, &gtab)) != ECL_OK) return rc;
   if ((rc = tr_buffers(h, nkeys)) != ECL_OK) return rc;
   h->mul_seen += nkeys;
   const u64 slab = tr_slab_keys();
   const u256 s = sc_pow2(h->offs);
-  HIPCHK(h, hipMemsetAsync(h->d_counter.p, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
-  HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+  if ((rc = f.reset()) != ECL_OK) return rc;
+  const add_args check = f.args(CW_TR_CHECKED);
   u32 slabs = 0, setups = 0;
   for (u64 at = 0; at < nkeys; ++slabs) {
     const u64 m = nkeys - at < slab ? nkeys - at : slab;
-    const u256 ks = sc_add(k0, sc_mul_u64(s, at));
     h->tr_epoch ^= 1u;
-    bool cont = false;
-    u64 walked = 0;
-    if ((rc = add_launch(h, ks, m, rcap, false, h->d_trslab.p, h->tr_epoch, &cont, &walked)) != ECL_OK) {
+    const add_launched l = add_launch(h, f, sc_add(k0, sc_mul_u64(s, at)), m, h->d_trslab.p);
+    if (l.rc != ECL_OK) {
       h->walk_valid = false;
-      return rc;
+      return l.rc;
     }
-    setups += cont ? 0u : 1u;
-    h->walk_valid = walked == m;
-    if (h->walk_valid) h->walk_next = sc_add(ks, sc_mul_u64(s, walked));
-    if ((rc = tr_check_slab(h, m, at, gtab, rcap, h->tr_epoch)) != ECL_OK) return rc;
+    setups += l.continued ? 0u : 1u;
+    if ((rc = tr_check_slab(h, m, at, gtab, check, h->tr_epoch)) != ECL_OK) return rc;
     at += m;
   }
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  u32 cnt = 0;
-  rc = collect_found(h, cap, rcap, out, &cnt, false);
-  if (rc != ECL_OK && rc != ECL_E_OVERFLOW) return rc;
-  float ms = 0;
-  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));  // both stages of every slab
-  h->kernel_ms += ms, h->launches += slabs, h->keys += nkeys;
-  if (setups) {  // (the events hold the last set-up of the call: a call re-positions once, or at every odd slab for about as long each)
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev_s0, h->ev_s1));
-    h->setup_ms += ms * setups, h->setups += setups;
-  }
-  const u64 emitted = counted_keys(h), checked = tr_checked_keys(h);
-  h->cov_device += emitted;
-  if (emitted != nkeys) return coverage_failed(h, "add_range (Taproot, points emitted)", nkeys, emitted, nout);
-  if (checked != nkeys) return coverage_failed(h, "add_range (Taproot, output keys)", nkeys, checked, nout);
-  *nout = cnt;
-  return rc;
+  if ((rc = f.collect()) != ECL_OK) return rc;
+  return f.finish(slabs, setups);  // (both stages of every slab; a call re-positions once, or at every odd slab for about as long each)
 }
 
 // a piece of `mul` on a Taproot context: the window sums' points into the piece's own slab (k_mul_points_tr), then k_tr_check over it, on
@@ -160,14 +127,15 @@ static int tr_add_core(ecl_hip* h, const u256& k0, uint64_t nkeys, ecl_found* ou
 static void tr_mul_launch_piece(ecl_hip* h, int lane, const u32* d_k, u32 m, u32 at, const wtab& gtab, const add_args& a, bool short_round) {
   u32 R, nt;
   hipStream_t st = lane ? h->stream2 : h->stream;
-  mul_geometry(m, &R, &nt);
+  mul_geometry(m, MUL_R, &R, &nt);
   if (short_round) R -= 1;
   const u32 epoch = h->tr_epoch_mul[lane] ^= 1u;
-  add_args e = a;
+  add_args e = a, check = a;
   e.slab = h->d_trslab_mul[lane].p, e.epoch = epoch;
+  check.keys = (unsigned long long*)(a.counter + CW_TR_CHECKED);
   hipLaunchKernelGGL(k_mul_points_tr, dim3(nt / 256), dim3(256), 0, st, d_k, m, 0u, gtab, e, h->d_multmp[lane].p, nt, R);
   if (hipGetLastError() != hipSuccess) return;
-  (void)tr_launch_check(h, st, h->d_trslab_mul[lane].p, m, at, gtab, a.cap, epoch, h->d_multmp[lane].p);
+  (void)tr_launch_check(h, st, h->d_trslab_mul[lane].p, m, at, gtab, check, epoch, h->d_multmp[lane].p);
 }
 
 extern "C" int ecl_hip_verify_tr(ecl_hip* h, const uint64_t (*k)[4], uint32_t n, uint32_t (*qx)[8], uint8_t* ok) {

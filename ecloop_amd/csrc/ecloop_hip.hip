@@ -28,6 +28,7 @@
 #include "aux_kernels.h"
 #include "herd_kernel.h"
 #include "devbuf.h"
+#include "callstate.h"
 
 // the two kinds of memory the library owns (devbuf.h): device memory, and page-locked host memory for its own staging
 struct dev_mem {
@@ -47,8 +48,7 @@ template <typename T> using pinbuf = growbuf<T, pin_mem>;
 
 // ------------------------------------------------------------------------------------------------ context
 
-#define ECL_COUNTER_WORDS 8u  /* d_counter: see ecl_hip_open */
-#define ECL_AUX_WORDS (34u * 16u)  /* d_aux: 34 points; one word more behind them: k_origin_add's infinity flag (its host copy: pin_counter[ECL_COUNTER_WORDS]) */
+#define ECL_AUX_WORDS (34u * 16u)  /* d_aux: 34 points; one word more behind them: k_origin_add's infinity flag (its host copy: pin_counter[CW_ORIGIN_INF]) */
 
 struct ecl_hip {
   int dev = 0;
@@ -88,14 +88,12 @@ struct ecl_hip {
   hipStream_t prep_stream = nullptr; hipEvent_t ev_hashed[MUL_NBUF] = {};  // `mul -raw`: the lines are hashed on a stream of their own, ahead of the pieces
   devbuf<u32> d_list; u64 list_n = 0;          // optional sorted hash list (exact confirm on the device)
   devbuf<ecl_found_dev> d_found;
-  devbuf<u32> d_counter; pinbuf<u32> pin_counter;  // (the counters' page-locked host copy: read back by the copy engine, no compute slot needed)
+  devbuf<u32> d_counter; pinbuf<u32> pin_counter;  // the words of callstate.h (the page-locked host copy: read back by the copy engine, no compute slot needed)
   // key coverage (ecl_hip_get_coverage): keys / scalars of the calls that launched or were served from a sweep, those of them whose device
   // count matched, and the keys the kernels of this context's launches counted; never reset
   uint64_t cov_requested = 0, cov_covered = 0, cov_device = 0;
   bool diag_drop = false;  // ecl_hip_diag_drop_round: the next search launch runs one round short
-  // records of the last add_range / mul_batch call that are still on the device (ecl_hip_fetch_found): where they start in d_found,
-  // how many the device holds, the call's total, and whether the endo byte is meaningful
-  u32 last_at = 0, last_held = 0, last_total = 0; bool last_endo = false;
+  last_records last;  // where the records of the last add_range / mul_batch call are (ecl_hip_fetch_found; callstate.h)
   // walk state for contiguous continuation
   bool walk_valid = false;
   u32 walk_T = 0, walk_B = 0;
@@ -191,11 +189,9 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   HIPCHK(h, hipEventCreate(&h->ev_s1));
   HIPCHK(h, h->d_aux.grow(ECL_AUX_WORDS + 1));
   HIPCHK(h, h->d_auxk.grow(34 * 8));
-  // [0] records appended, [1] records confirmed by the list, [2] [3] input flags of mul_batch_raw, [4] [5] the u64 count of keys hashed
-  // (Taproot: of points emitted), [6] [7] Taproot: the u64 count of slab entries that reached k_tr_check's probe step
-  HIPCHK(h, h->d_counter.grow(ECL_COUNTER_WORDS));
-  HIPCHK(h, h->pin_counter.grow(ECL_COUNTER_WORDS + 1));
-  h->pin_counter.p[ECL_COUNTER_WORDS] = 0;
+  HIPCHK(h, h->d_counter.grow(CW_DEVICE_WORDS));
+  HIPCHK(h, h->pin_counter.grow(CW_HOST_WORDS));
+  h->pin_counter.p[CW_ORIGIN_INF] = 0;
   // the self-test checks the CODE (known answers, walk kernel against the double-and-add kernel): once per process
   // for every (device, kernel selection) is enough - eight handles for eight shards of one scan do not repeat it
   static std::mutex mu;
@@ -479,87 +475,117 @@ static add_kernel_t pick_add_kernel(u32 flags) {
   }
 }
 
-// found records of one call: [0, raw_cap) written by the search kernel; in list mode the confirmed ones are
-// compacted into [raw_cap, 2 * raw_cap).  d_counter[0] = records pushed, d_counter[1] = records confirmed.
-// raw_cap = max(cap, 2^20) whatever the caller's `cap` (32 MB of HBM, twice that in list mode): a call that reports
-// ECL_E_OVERFLOW has kept the records that did not fit the caller's buffer, and ecl_hip_fetch_found hands them over
-// without the search kernel running again.
+// found records of one call: [0, rcap) written by the search kernel; in list mode the confirmed ones are compacted into
+// [rcap, 2 * rcap).  rcap = max(cap, 2^20) whatever the caller's `cap` (32 MB of HBM, twice that in list mode): a call that reports
+// ECL_E_OVERFLOW has kept the records that did not fit the caller's buffer, and ecl_hip_fetch_found hands them over without the search
+// kernel running again.
 #define ECL_RAW_CAP_MIN (1u << 20)
-static int ensure_found(ecl_hip* h, u32 cap) {
-  if (cap <= h->d_found.n) return ECL_OK;
-  h->last_held = h->last_total = 0;  // the buffer that held the last call's records goes away
-  HIPCHK(h, h->d_found.grow(cap));
+#define ECL_CAP_MAX (1u << 30)  /* records one call can be asked to deliver (32 GB of them); list mode allocates twice the count */
+static u32 raw_cap_of(u32 cap) { return cap > ECL_RAW_CAP_MIN ? cap : ECL_RAW_CAP_MIN; }
+// the record buffer of a call that keeps rcap records (rcap <= 2^30): the one sizing rule
+static int ensure_found(ecl_hip* h, u32 rcap) {
+  const size_t want = h->d_list.p ? 2 * (size_t)rcap : rcap;
+  if (want <= h->d_found.n) return ECL_OK;
+  if (!h->last.from_host) h->last.forget();  // the buffer that held the last call's records goes away (records on the host stay)
+  HIPCHK(h, h->d_found.grow(want));
   return ECL_OK;
 }
-
-static u32 raw_cap_of(const ecl_hip*, u32 cap) { return cap > ECL_RAW_CAP_MIN ? cap : ECL_RAW_CAP_MIN; }
-#define ECL_CAP_MAX (1u << 30)  /* records one call can be asked to deliver (32 GB of them); list mode allocates twice the count */
-static u32 found_words_of(const ecl_hip* h, u32 rcap) { return h->d_list.p ? 2u * rcap : rcap; }  // records to allocate for a call (rcap <= 2^30)
-static void found_to_host(ecl_found* out, const ecl_found_dev* tmp, u32 n, bool keep_endo) {
+static int fetch_records(ecl_hip* h, ecl_found* out, u32 from, u32 n, bool keep_endo) {
+  if (!n) return ECL_OK;
+  std::vector<ecl_found_dev> tmp(n);
+  HIPCHK(h, hipMemcpy(tmp.data(), h->d_found.p + from, (size_t)n * sizeof(ecl_found_dev), hipMemcpyDeviceToHost));
   for (u32 i = 0; i < n; ++i) {
     out[i].key_offset = tmp[i].key_offset;
     memcpy(out[i].h160, tmp[i].h160, 20);
     out[i].endo = keep_endo ? (uint8_t)(tmp[i].tag & 0xff) : 0, out[i].compressed = (uint8_t)((tmp[i].tag >> 8) & 0xff);
     out[i].pad[0] = out[i].pad[1] = 0;
   }
-}
-// after the search kernel has been queued on h->stream: optional list confirm, then counters and records to the host
-static int collect_found(ecl_hip* h, u32 cap, u32 rcap, ecl_found* out, u32* nout, bool keep_endo) {
-  const bool lst = h->d_list.p != nullptr;
-  if (lst) {
-    const u32 blocks = (rcap + 255) / 256 < 1024 ? (rcap + 255) / 256 : 1024;
-    hipLaunchKernelGGL(k_list_filter, dim3(blocks), dim3(256), 0, h->stream, h->d_found.p, h->d_counter.p, rcap, h->d_list.p, h->list_n,
-                       h->d_found.p + rcap, h->d_counter.p + 1, rcap);
-    HIPCHK(h, hipGetLastError());
-  }
-  // One read-back and one wait per call, into page-locked memory: a copy into pageable memory goes through a staging kernel, and with
-  // a second context's k_mul_check launches filling the chip every small kernel waits milliseconds for a slot (each such wait at the
-  // end of a `mul` call is time this context has nothing in flight).  All the words: mul_batch_raw reads its flags from the same copy, and
-  // every caller the count of keys hashed (counted_keys).
-  u32* cnts = h->pin_counter.p;
-  HIPCHK(h, hipMemcpyAsync(cnts, h->d_counter.p, ECL_COUNTER_WORDS * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  const u32 cnt = lst ? cnts[1] : cnts[0];
-  const u32 take = cnt < cap ? cnt : cap;
-  h->last_at = lst ? rcap : 0, h->last_held = cnt < rcap ? cnt : rcap, h->last_total = cnt, h->last_endo = keep_endo;
-  if (take) {
-    std::vector<ecl_found_dev> tmp(take);
-    HIPCHK(h, hipMemcpy(tmp.data(), h->d_found.p + h->last_at, (size_t)take * sizeof(ecl_found_dev), hipMemcpyDeviceToHost));
-    found_to_host(out, tmp.data(), take, keep_endo);
-  }
-  *nout = cnt;
-  if (lst && cnts[0] > rcap) {  // the bloom let more through than the staging area holds: some were never looked up
-    h->err = "list mode: more bloom hits in one call than the device staging area holds";
-    *nout = cnts[0];
-    h->last_held = 0, h->last_total = cnts[0];  // nothing to fetch: the confirmed set is incomplete
-    return ECL_E_OVERFLOW;
-  }
-  return cnt > cap ? ECL_E_OVERFLOW : ECL_OK;
+  return ECL_OK;
 }
 
-// Key coverage.  Every launch of a search kernel counts, on the device, the keys that reach the hash-and-probe step inside its range
-// (add_kernel.h: keys_count / keys_flush) into the u64 at d_counter + 4, which the one read-back of collect_found brings home.  A call whose
-// count differs from the keys it asked for returns ECL_E_COVERAGE: no records, nothing to fetch, and the resident walk is dropped.
-static u64 counted_keys(const ecl_hip* h) { return (u64)h->pin_counter.p[4] | (u64)h->pin_counter.p[5] << 32; }
-static int coverage_failed(ecl_hip* h, const char* what, u64 want, u64 got, u32* nout) {
-  char msg[160];
-  snprintf(msg, sizeof msg, "%s: the device hashed %llu keys of the %llu asked for", what, (unsigned long long)got, (unsigned long long)want);
-  h->err = msg;
-  h->walk_valid = false, h->last_held = h->last_total = 0, h->last_from_host = false;
-  *nout = 0;
-  return ECL_E_COVERAGE;
-}
-// after collect_found: the launch's device count against `want` (rc: collect_found's result, ECL_OK or ECL_E_OVERFLOW)
-static int check_coverage(ecl_hip* h, const char* what, u64 want, int rc, u32* nout) {
-  const u64 got = counted_keys(h);
-  h->cov_device += got;
-  return got == want ? rc : coverage_failed(h, what, want, got, nout);
-}
-// the totals of ecl_hip_get_coverage for one add / mul call, by its result: a call that returns ECL_OK / ECL_E_OVERFLOW was launched or served
-// and counted whole; one that returns ECL_E_COVERAGE was launched and not
-static int count_call(ecl_hip* h, u64 n, int rc) {
-  if (rc == ECL_OK || rc == ECL_E_OVERFLOW || rc == ECL_E_COVERAGE) h->cov_requested += n;
-  if (rc == ECL_OK || rc == ECL_E_OVERFLOW) h->cov_covered += n;
+// The frame of a search call - add_core, tr_add_core, herd_add_core, ecl_hip_mul_batch, ecl_hip_mul_batch_raw: begin(), args() for the
+// kernels, reset() in front of the launches (once per pass of -raw), collect() behind them, finish().  What a call decides from the words
+// read back is call_verdict_of (callstate.h); here are the HIP calls around it and the books.
+// Key coverage: every launch of a search kernel counts, on the device, the keys that reach the hash-and-probe step inside its range
+// (add_kernel.h: keys_count / keys_flush) into the u64 at CW_KEYS.  A call whose count differs from the keys it asked for returns
+// ECL_E_COVERAGE: no records, nothing to fetch, and the resident walk is dropped.
+struct call_frame {
+  ecl_hip* h;
+  const char* what;   // the call's name in the text of a short count
+  const char* what2;  // null, or: the second count (CW_TR_CHECKED) is checked too, under this name
+  u64 n;              // keys / scalars asked for
+  ecl_found* out;
+  u32 cap;
+  u32* nout;
+  bool mul, endo;     // booked as a `mul` call; the records' endo byte is meaningful
+  u32 rcap = 0;
+  call_verdict v = {};
+
+  // the records of the call before are about to be overwritten
+  int begin() {
+    h->last.forget();
+    rcap = raw_cap_of(cap);
+    return ensure_found(h, rcap);
+  }
+  // the common half of a search kernel's arguments: filter, record buffer, counters, the word its keys are counted into
+  add_args args(u32 keys_at = CW_KEYS) const {
+    add_args a;
+    memset(&a, 0, sizeof a);
+    a.bloom = bloom_make(h->d_bloom.p, h->bloom_words);
+    a.found = h->d_found.p, a.counter = h->d_counter.p, a.cap = rcap, a.keys = (unsigned long long*)(h->d_counter.p + keys_at);
+    return a;
+  }
+  int reset() const {
+    HIPCHK(h, hipMemsetAsync(h->d_counter.p, 0, CW_DEVICE_WORDS * sizeof(u32), h->stream));
+    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
+    return ECL_OK;
+  }
+  // after the search kernels have been queued on h->stream: optional list confirm, then counters and records to the host
+  int collect() {
+    HIPCHK(h, hipEventRecord(h->ev1, h->stream));
+    const bool lst = h->d_list.p != nullptr;
+    if (lst) {
+      const u32 blocks = (rcap + 255) / 256 < 1024 ? (rcap + 255) / 256 : 1024;
+      hipLaunchKernelGGL(k_list_filter, dim3(blocks), dim3(256), 0, h->stream, h->d_found.p, h->d_counter.p + CW_PUSHED, rcap, h->d_list.p, h->list_n,
+                         h->d_found.p + rcap, h->d_counter.p + CW_CONFIRMED, rcap);
+      HIPCHK(h, hipGetLastError());
+    }
+    // One read-back and one wait per call, into page-locked memory: a copy into pageable memory goes through a staging kernel, and with
+    // a second context's k_mul_check launches filling the chip every small kernel waits milliseconds for a slot (each such wait at the
+    // end of a `mul` call is time this context has nothing in flight).  All the words: the records, the flags and both counts.
+    const u32* w = h->pin_counter.p;
+    HIPCHK(h, hipMemcpyAsync(h->pin_counter.p, h->d_counter.p, CW_DEVICE_WORDS * sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    v = call_verdict_of(w, cap, rcap, lst, n, what2 ? &n : nullptr);
+    h->cov_device += counted_keys(w);
+    h->last.on_device(v.from, v.held, v.total, endo);
+    return fetch_records(h, out, v.from, v.take, endo);
+  }
+  // the books (a short call was launched: it is booked too), the verdict's text and state, *nout -> the call's result
+  int finish(u32 launches = 1, u32 setups = 0) {
+    float ms = 0;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));  // copies + kernels of this call, as the stream saw them
+    if (mul) h->mul_ms += ms, h->mul_calls += 1, h->mul_scalars += n;
+    else h->kernel_ms += ms, h->launches += launches, h->keys += n;
+    if (setups) {  // (the events hold the last set-up of the call)
+      HIPCHK(h, hipEventElapsedTime(&ms, h->ev_s0, h->ev_s1));
+      h->setup_ms += ms * setups, h->setups += setups;
+    }
+    char msg[160];
+    if (call_verdict_text(v, what, what2, n, msg, sizeof msg)) h->err = msg;
+    if (v.rc == ECL_E_COVERAGE) h->walk_valid = false, h->last.forget();
+    *nout = v.nout;
+    return v.rc;
+  }
+  // a refusal behind finish(): no records, nothing to fetch
+  int refuse(int rc, const char* why) {
+    h->err = why, h->last.forget(), *nout = 0;
+    return rc;
+  }
+};
+static int count_call(ecl_hip* h, u64 n, int rc) {  // the totals of ecl_hip_get_coverage for one add / mul call, by its result
+  if (rc_was_launched(rc)) h->cov_requested += n;
+  if (rc_was_whole(rc)) h->cov_covered += n;
   return rc;
 }
 
@@ -567,15 +593,13 @@ static int la_fetch(ecl_hip* h, uint32_t first, ecl_found* out, uint32_t n, uint
 extern "C" int ecl_hip_fetch_found(ecl_hip* h, uint32_t first, ecl_found* out, uint32_t n, uint32_t* got) {
   if (!h || !got || (!out && n)) return ECL_E_ARG;
   *got = 0;
-  if (h->last_from_host) return la_fetch(h, first, out, n, got);  // the last call was served from a look-ahead sweep: its records are on the host
-  if (first >= h->last_held || n == 0) return ECL_OK;
-  const u32 take = h->last_held - first < n ? h->last_held - first : n;
+  if (h->last.from_host) return la_fetch(h, first, out, n, got);  // the last call was served from a look-ahead sweep: its records are on the host
+  if (first >= h->last.held || n == 0) return ECL_OK;
+  const u32 take = h->last.held - first < n ? h->last.held - first : n;
   HIPCHK(h, hipSetDevice(h->dev));
-  std::vector<ecl_found_dev> tmp(take);
-  HIPCHK(h, hipMemcpy(tmp.data(), h->d_found.p + h->last_at + first, (size_t)take * sizeof(ecl_found_dev), hipMemcpyDeviceToHost));
-  found_to_host(out, tmp.data(), take, h->last_endo);
-  *got = take;
-  return ECL_OK;
+  const int rc = fetch_records(h, out, h->last.at + first, take, h->last.endo);
+  if (rc == ECL_OK) *got = take;
+  return rc;
 }
 
 static int default_lanes(ecl_hip* h) {
@@ -748,20 +772,22 @@ extern "C" int ecl_hip_reserve(ecl_hip* h, uint64_t nkeys, uint32_t cap) {
   if ((rc = ensure_table(h)) != ECL_OK) return rc;
   if ((rc = ensure_gtable(h)) != ECL_OK) return rc;
   if (!nkeys_ok(h, nkeys)) return ECL_E_ARG;
-  const u32 rcap = raw_cap_of(h, cap ? cap : 1);
-  if ((rc = ensure_found(h, found_words_of(h, rcap))) != ECL_OK) return rc;
+  if ((rc = ensure_found(h, raw_cap_of(cap))) != ECL_OK) return rc;
   if (h->flags & ECL_TR) return tr_reserve(h, nkeys);
   u32 B, nb, T;
   call_geometry(h, nkeys, B, nb, T);
   return ensure_walk_buffers(h, B, T);
 }
 
-// one launch of the search kernel over exactly the keys k0, k0 + s, ..., k0 + (nkeys - 1) s  (k0 reduced mod n): the body of
-// ecl_hip_add_range; the look-ahead (abi_lookahead.h) calls it with a sweep instead of the caller's job
-// the launch itself: geometry, buffers, the walk positioned at k0 (or continued), the kernel queued on h->stream.  own_call: the launch
-// is a call of its own (counters reset and ev0 recorded in front of it); a Taproot call queues one launch per slab between its own
-// reset and read-back, each into `slab` with the mark `epoch` (tr_emit).  *cont: the resident walk was continued; *walked: keys the launch walks
-static int add_launch(ecl_hip* h, const u256& k0, uint64_t nkeys, u32 rcap, bool own_call, u32* slab, u32 epoch, bool* cont_out, u64* walked_out) {
+// one launch of the search kernel over exactly the keys k0, k0 + s, ..., k0 + (nkeys - 1) s  (k0 reduced mod n), in front of the
+// collect() of the call frame `f`: geometry, buffers, the walk positioned at k0 (or continued), the kernel queued on h->stream, the walk
+// state moved on.  slab: null, or where a Taproot call's emit kernel puts this launch's points, under the mark h->tr_epoch (tr_emit).
+struct add_launched {
+  int rc;
+  bool continued;  // the resident walk was continued: no set-up
+  add_launched(int rc_, bool continued_ = false) : rc(rc_), continued(continued_) {}
+};
+static add_launched add_launch(ecl_hip* h, const call_frame& f, const u256& k0, uint64_t nkeys, u32* slab) {
   int rc;
   if ((rc = default_lanes(h)) != ECL_OK) return rc;
   if (!nkeys_ok(h, nkeys)) {
@@ -776,12 +802,12 @@ static int add_launch(ecl_hip* h, const u256& k0, uint64_t nkeys, u32 rcap, bool
   if ((rc = ensure_walk_buffers(h, B, T)) != ECL_OK) return rc;
 
   const u256 s = sc_pow2(h->offs);
+  const u64 walked = (u64)nb * T * group;
   {
     // The walk cannot represent the point at infinity: refuse a scan that contains the scalar 0 (mod n), like the
     // reference's range check (main.c:687-690).  j0 = offset of that key = -k0 / 2^offs (mod n).
     u256 j0 = sc_neg(k0);
     for (u32 i = 0; i < h->offs; ++i) j0 = sc_half(j0);
-    const u64 walked = (u64)nb * T * group;
     if (!(j0.w[1] | j0.w[2] | j0.w[3]) && j0.w[0] < walked && j0.w[0] < nkeys + group) {
       h->err = "the scan contains the private key 0 (mod n)";
       return ECL_E_RANGE;
@@ -790,7 +816,7 @@ static int add_launch(ecl_hip* h, const u256& k0, uint64_t nkeys, u32 rcap, bool
   bool cont = h->walk_valid && h->walk_T == T && h->walk_B == B && u256_eq(h->walk_next, k0);
   const bool origin = h->flags & ECL_ORIGIN;
   if (origin && memcmp(h->walk_origin, h->origin_w, sizeof h->origin_w) != 0) cont = false;  // another origin: re-position
-  h->pin_counter.p[ECL_COUNTER_WORDS] = 0;
+  h->pin_counter.p[CW_ORIGIN_INF] = 0;
   if (!cont) {
     if ((rc = ensure_gtable(h)) != ECL_OK) return rc;
     HIPCHK(h, hipEventRecord(h->ev_s0, h->stream));
@@ -834,7 +860,7 @@ static int add_launch(ecl_hip* h, const u256& k0, uint64_t nkeys, u32 rcap, bool
       memcpy(o.w, h->origin_w, sizeof o.w);
       hipLaunchKernelGGL(k_origin_add, dim3(1), dim3(64), 0, h->stream, h->d_aux.p, o, h->d_aux.p + ECL_AUX_WORDS);
       HIPCHK(h, hipGetLastError());
-      HIPCHK(h, hipMemcpyAsync(h->pin_counter.p + ECL_COUNTER_WORDS, h->d_aux.p + ECL_AUX_WORDS, sizeof(u32), hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(h, hipMemcpyAsync(h->pin_counter.p + CW_ORIGIN_INF, h->d_aux.p + ECL_AUX_WORDS, sizeof(u32), hipMemcpyDeviceToHost, h->stream));
       memcpy(h->walk_origin, h->origin_w, sizeof h->walk_origin);
     }
     if (from_table && T >= (1u << 19))
@@ -850,59 +876,37 @@ static int add_launch(ecl_hip* h, const u256& k0, uint64_t nkeys, u32 rcap, bool
     HIPCHK(h, hipEventRecord(h->ev_s1, h->stream));
     h->walk_T = T, h->walk_B = B;
   }
-  add_args a;
+  add_args a = f.args();
   a.tab = h->d_tab.p;
   memcpy(a.jump, h->jump_host, sizeof a.jump);
   a.cxy = h->d_cxy.p, a.scratch = h->d_scr.p, a.scratch2 = h->d_scr2.p;
-  a.bloom = bloom_make(h->d_bloom.p, h->bloom_words);
   if (h->flags & ECL_PREFIX) a.prefix = prefix_of(h);
-  a.found = h->d_found.p, a.counter = h->d_counter.p, a.cap = rcap, a.keys = (unsigned long long*)(h->d_counter.p + 4);
-  if (slab) a.slab = slab, a.epoch = epoch;
+  if (slab) a.slab = slab, a.epoch = h->tr_epoch;
   a.B = B, a.T = T, a.nb = nb, a.nkeys = nkeys;
   if (h->diag_drop) h->diag_drop = false, a.nb = nb - 1;  // (test hook: lane 0's last group is in the range, so keys go missing)
-  if (own_call) {
-    HIPCHK(h, hipMemsetAsync(h->d_counter.p, 0, ECL_COUNTER_WORDS * sizeof(u32), h->stream));
-    HIPCHK(h, hipEventRecord(h->ev0, h->stream));
-  }
+  if (!slab && (rc = f.reset()) != ECL_OK) return rc;  // a call of its own: its time starts behind the set-up (a Taproot call resets in front of its slabs)
   hipLaunchKernelGGL(pick_add_kernel(h->flags), dim3(T / ECL_ADD_BLOCK), dim3(ECL_ADD_BLOCK), 0, h->stream, a);
   HIPCHK(h, hipGetLastError());
-  *cont_out = cont, *walked_out = (u64)nb * T * group;
-  return ECL_OK;
+  // the centres now sit at the start of group nb*T + g: valid continuation only if the launch was exact
+  h->walk_valid = walked == nkeys;
+  if (h->walk_valid) h->walk_next = sc_add(k0, sc_mul_u64(s, walked));
+  return add_launched(ECL_OK, cont);
 }
 
 static int add_core(ecl_hip* h, const u256& k0, uint64_t nkeys, ecl_found* out, uint32_t cap, uint32_t* nout) {
   *nout = 0;
   if (h->flags & ECL_TR) return tr_add_core(h, k0, nkeys, out, cap, nout);
+  call_frame f = {h, "add_range", nullptr, nkeys, out, cap, nout, false, true};
   int rc;
-  h->last_held = h->last_total = 0, h->last_from_host = false;  // the records of the call before are about to be overwritten
-  const u32 rcap = raw_cap_of(h, cap ? cap : 1);
-  if ((rc = ensure_found(h, found_words_of(h, rcap))) != ECL_OK) return rc;
-  bool cont = false;
-  u64 walked = 0;
-  if ((rc = add_launch(h, k0, nkeys, rcap, true, nullptr, 0, &cont, &walked)) != ECL_OK) return rc;
-  const u256 s = sc_pow2(h->offs);
-  HIPCHK(h, hipEventRecord(h->ev1, h->stream));
-  u32 cnt = 0;
-  rc = collect_found(h, cap, rcap, out, &cnt, true);
-  if (rc != ECL_OK && rc != ECL_E_OVERFLOW) return rc;
-  float ms = 0;
-  HIPCHK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  h->kernel_ms += ms, h->launches += 1, h->keys += nkeys;
-  if (!cont) {
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev_s0, h->ev_s1));
-    h->setup_ms += ms, h->setups += 1;
+  if ((rc = f.begin()) != ECL_OK) return rc;
+  const add_launched l = add_launch(h, f, k0, nkeys, nullptr);
+  if (l.rc != ECL_OK) return l.rc;
+  if ((rc = f.collect()) != ECL_OK) return rc;
+  rc = f.finish(1, l.continued ? 0 : 1);
+  if (rc != ECL_E_COVERAGE && (h->flags & ECL_ORIGIN) && h->pin_counter.p[CW_ORIGIN_INF]) {  // origin + base point = the point at infinity: nothing was walked from it
+    h->walk_valid = false;
+    return f.refuse(ECL_E_RANGE, "the origin is the negative of the walk's base point");
   }
-  if (check_coverage(h, "add_range", nkeys, rc, nout) == ECL_E_COVERAGE) return ECL_E_COVERAGE;
-  if ((h->flags & ECL_ORIGIN) && h->pin_counter.p[ECL_COUNTER_WORDS]) {  // origin + base point = the point at infinity: nothing was walked from it
-    h->err = "the origin is the negative of the walk's base point";
-    h->walk_valid = false, h->last_held = h->last_total = 0;
-    return ECL_E_RANGE;
-  }
-
-  // the centres now sit at the start of group nb*T + g: valid continuation only if the launch was exact
-  h->walk_valid = walked == nkeys;
-  if (h->walk_valid) h->walk_next = sc_add(k0, sc_mul_u64(s, walked));
-  *nout = cnt;
   return rc;
 }
 

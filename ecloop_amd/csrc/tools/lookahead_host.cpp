@@ -22,6 +22,7 @@ typedef uint32_t u32;
 typedef uint64_t u64;
 #include "../scalar_host.h"
 #include "../abi_lookahead_ctx.h"
+#include "../callstate.h"
 
 #define HELD_MAX (1u << 18) /* records the stand-in device keeps per launch (the library: max(cap, 2^20)) */
 
@@ -29,7 +30,7 @@ struct ecl_hip {
   int dev = 0;
   u32 flags = 0, offs = 0;
   u64 bloom_words = 0, list_n = 0;
-  u32 last_held = 0, last_total = 0;
+  last_records last;
   LA_CONTEXT_MEMBERS
   // the stand-in device
   u64 filter = 0, one_in = 4096, dense_from = ~0ull, dense_len = 0, dense_one_in = 1, poison = ~0ull;
@@ -48,7 +49,7 @@ static inline u64 mix(u64 i, u64 f) {
 
 static int add_core(ecl_hip* h, const u256& k0, uint64_t nkeys, ecl_found* out, uint32_t cap, uint32_t* nout) {
   *nout = 0;
-  h->last_held = h->last_total = 0, h->last_from_host = false;
+  h->last.forget();
   u256 q = k0;
   for (u32 i = 0; i < h->offs; ++i) q = sc_half(q);  // exact for the test's scalars (multiples of the stride)
   const u64 i0 = q.w[0];
@@ -76,7 +77,7 @@ static int add_core(ecl_hip* h, const u256& k0, uint64_t nkeys, ecl_found* out, 
   const u32 take = cnt < cap ? (u32)cnt : cap;
   const u32 held = cnt < HELD_MAX ? (u32)cnt : HELD_MAX;
   memcpy(out, h->kept.data(), (size_t)(take < held ? take : held) * sizeof(ecl_found));
-  h->last_held = held, h->last_total = (u32)cnt;
+  h->last.on_device(0, held, (u32)cnt, true);
   *nout = (u32)cnt;
   return cnt > cap ? ECL_E_OVERFLOW : ECL_OK;
 }
@@ -84,9 +85,9 @@ static int add_core(ecl_hip* h, const u256& k0, uint64_t nkeys, ecl_found* out, 
 static int la_fetch(ecl_hip* h, uint32_t first, ecl_found* out, uint32_t n, uint32_t* got);
 extern "C" int ecl_hip_fetch_found(ecl_hip* h, uint32_t first, ecl_found* out, uint32_t n, uint32_t* got) {
   *got = 0;
-  if (h->last_from_host) return la_fetch(h, first, out, n, got);
-  if (first >= h->last_held || n == 0) return ECL_OK;
-  const u32 take = h->last_held - first < n ? h->last_held - first : n;
+  if (h->last.from_host) return la_fetch(h, first, out, n, got);
+  if (first >= h->last.held || n == 0) return ECL_OK;
+  const u32 take = h->last.held - first < n ? h->last.held - first : n;
   memcpy(out, h->kept.data() + first, (size_t)take * sizeof(ecl_found));
   *got = take;
   return ECL_OK;

@@ -295,6 +295,19 @@ class MulRef:
         return canon(np.concatenate(parts))
 
 
+START = 0x6000000123  # the first key of the `add` calls of the tests below
+
+
+@functools.lru_cache(maxsize=None)
+def consecutive(n):
+    """the reference over the scalars START ... START + n - 1: what `add` reports for any part of that range, and `mul` for the array
+    (tests/test_gpu_regrow.py, tests/test_gpu_call_state.py)"""
+    K = np.zeros((n, 4), np.uint64)
+    K[:, 0] = np.uint64(START) + np.arange(n, dtype=np.uint64)
+    K.setflags(write=False)
+    return MulRef(K)
+
+
 @functools.lru_cache(maxsize=None)
 def ref():
     """the reference over shape B's scalars; shape A is its records(name, 0, NA)"""

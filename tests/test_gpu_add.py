@@ -665,8 +665,11 @@ def test_mul_batch_raw_in_pieces_table_in_any_order_against_the_oracle():
         for name, perm in (("text order", np.arange(n)), ("reversed", np.arange(n)[::-1].copy()), ("shuffled", rng.permutation(n))):
             table = np.ascontiguousarray(in_order[perm])
             d.set_bloom(ONES)
+            cov = d.coverage()
             assert d.lib.ecl_hip_mul_batch_raw(d.h, text.ctypes.data, tot, table.ctypes.data, n, out.ctypes.data, 2 * n, C.byref(cnt)) == 0, name
             assert cnt.value == 2 * n, name
+            # one call asked for and whole; the device counted every pass (a table out of the text's order is run again)
+            assert tuple(b - a for a, b in zip(cov, d.coverage())) == (n, n, n if name == "text order" else 2 * n), name
             got = out[: 2 * n]
             line = perm[got["key_offset"].astype(np.int64)]
             comp = got["compressed"].astype(bool)

@@ -18,21 +18,10 @@ import pytest
 import kangaroo_ref
 import mul_ref
 import orc
-from mul_ref import FILTER3, ONES, canon, difference
+from mul_ref import FILTER3, ONES, START, canon, consecutive, difference
 from synth import synth_bloom_words
 
 pytestmark = pytest.mark.gpu
-START = 0x6000000123  # the first key of the `add` calls
-
-
-@functools.lru_cache(maxsize=None)
-def consecutive(n):
-    """the reference over the scalars START ... START + n - 1: what `add` reports for any part of that range, and `mul` for the array"""
-    K = np.zeros((n, 4), np.uint64)
-    K[:, 0] = np.uint64(START) + np.arange(n, dtype=np.uint64)
-    K.setflags(write=False)
-    return mul_ref.MulRef(K)
-
 
 @functools.lru_cache(maxsize=None)
 def random_ref(n):
