@@ -324,11 +324,41 @@ __device__ __forceinline__ void check_point(const add_args& a, cand_queues* q, b
   }
 }
 
+// The exact way to the parity of y3 for the addr33-only walk kernels, where emit33_ypar_short's guard fires (2^-16 per key, so a wave
+// comes here once in about 2^10 walked points): the step of add_walk.inc once more - lam = (+-Gy - Y) invk, x3 = lam^2 - X - Gx,
+// y3 = lam (X - x3) - Y - from values the table loop keeps in any case, so that nothing of the step stays live across the short product
+// for this block's sake (kept, lam and X - x3 cost 63 scratch instructions in it).  Out of line: inlined, its 261 multiply-adds sit in
+// the `which` loop as a block of 500 instructions that is next to never run.  The caller hands over COPIES made where it calls
+// (walk_ypar_copy): arguments by reference are stack objects, and those of X, Y and invk themselves are written where the values are
+// made - in the table loop, for every key.
+__device__ __forceinline__ fe walk_ypar_copy(const fe& a) {
+  fe r = a;
+#pragma unroll
+  for (int l = 0; l < FE_LIMBS; ++l) asm volatile("" : "+v"(r.n[l]));
+  return r;
+}
+// the step itself, from its numerator s = +-Gy - Y: x3 = lam^2 + nxg with lam = s invk, and the parity of lam (X - x3) - Y.  Both forms
+// of the exact way run this and nothing else: walk_ypar_exact below, and the block that add_walk.inc keeps in place with the endomorphism
+__device__ __forceinline__ u32 walk_ypar_step(fe& x3, const fe& s, const fe& invk, const fe& nxg, const fe& X, const fe& Y) {
+  const fe lam = fe_mul(s, invk);
+  x3 = fe_add(fe_sqr(lam), nxg);                                          // magnitude 4
+  return fe_parity(fe_sub(fe_mul(lam, fe_add(X, fe_neg(x3, 4))), Y));     // X - x3: magnitude 6; y3: magnitude 3
+}
+__device__ __noinline__ inline u32 walk_ypar_exact(ctab_ptr gxy, int which, const fe& X, const fe& Y, const fe& invk) {
+  const fe gx = fe_ld_tab(gxy), gy = fe_ld_tab(gxy + FE_LIMBS);
+  const fe c = which == 0 ? fe_add(gy, fe_neg(fe_zero(), 1)) : fe_neg(gy, 2);
+  fe s, x3;
+#pragma unroll
+  for (int l = 0; l < FE_LIMBS; ++l) s.n[l] = c.n[l] - Y.n[l];
+  return walk_ypar_step(x3, s, invk, fe_neg(fe_add(X, gx), 2), X, Y);
+}
+
 // check_point<true, false, false, ENDO> for the walk kernels (k_add<true, false, ENDO>): the same hashes, probes and records by emit33.h's
 // shorter way - limbs to message words, y for its parity alone, probe 0 from RIPEMD-160's native words, the h160_t byte order only for
-// what is parked.  ENDO: the images in check_point's numbering.  x: magnitude <= 4, y: magnitude <= 3.
+// what is parked.  ENDO: the images in check_point's numbering.  x: magnitude <= 4, par: the parity of y's canonical residue (emit33_parity
+// of the centre's y, emit33_ypar for a walked point, whose y is never formed).
 template <bool ENDO>
-__device__ __forceinline__ void check_point33(const add_args& a, cand_queues* q, bool live, const fe& x, const fe& y, u64 off) {
+__device__ __forceinline__ void check_point33(const add_args& a, cand_queues* q, bool live, const fe& x, u32 par, u64 off) {
   u32 xw[ENDO ? 3 : 1][9];
   if (ENDO) {
     const u32 bw[8] = FE_BETA1_W;
@@ -338,7 +368,6 @@ __device__ __forceinline__ void check_point33(const add_args& a, cand_queues* q,
     emit33_xwords(xw[ENDO ? 2 : 0], b2x);
   }
   emit33_xwords(xw[0], x);
-  const u32 par = emit33_parity(y);
   const int nvar = ENDO ? 6 : 1;
 #pragma unroll 1
   for (int e = 0; e < nvar; ++e) {

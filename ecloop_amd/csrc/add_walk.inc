@@ -19,6 +19,12 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
 #else
   constexpr bool ETH = false;
 #endif
+  // the addr33-only kernels (k_add<true, false, ENDO>) take y's parity from a partial product and never form y of a walked point (emit33.h)
+#if defined(ECL_WALK_TR) || defined(ECL_WALK_INSERT) || defined(ECL_WALK_PUB) || defined(ECL_WALK_PREFIX)
+  constexpr bool PAR33 = false, PAR33_CALL = false;
+#else
+  constexpr bool PAR33 = A33 && !A65 && !ECL_WALK_P2SH && !ETH, PAR33_CALL = PAR33 && !ENDO;  // (the exact way: out of line / in place)
+#endif
 #if defined(ECL_WALK_TR) || defined(ECL_WALK_INSERT)
   cand_queues q;  // (the key count alone)
   q.keys = 0;
@@ -84,6 +90,7 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
 #pragma unroll 1
       for (int which = 0; which < nwhich; ++which) {
         fe px, py;
+        u32 par = 0;  // (PAR33 only)
         u64 off;
         bool valid = true;  // wave-uniform
         if (which < 2) {
@@ -100,7 +107,30 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
           for (int l = 0; l < FE_LIMBS; ++l) s.n[l] = c.n[l] - Y.n[l];
           fe lam = fe_mul(s, invk);
           px = fe_add(fe_sqr(lam), nxg);                                   // magnitude 4
-          py = fe_sub(fe_mul(lam, fe_add(X, fe_neg(px, 4))), Y);           // X - px: magnitude 6; py: magnitude 3
+          if constexpr (PAR33) {
+            // y3 for its parity alone.  Where the short product may not be relied on (2^-16 per key) the point is walked again from what
+            // the loop keeps anyway (add_kernel.h, walk_ypar_exact).  Without the endomorphism out of line.  With it in place - there the
+            // call costs two spilled pointers in the table loop; the numerator is formed from an opaque copy of Y, or the compiler shares
+            // lam and X - px with the lines above and keeps both across the short product.  Either way the step is walk_ypar_step
+            u32 rare;
+            par = emit33_ypar_short(lam, fe_add(X, fe_neg(px, 4)), Y, rare);
+            if (__builtin_expect(rare != 0, 0)) {
+              if constexpr (!PAR33_CALL) {
+                fe Yh = Y;
+#pragma unroll
+                for (int l = 0; l < FE_LIMBS; ++l) {
+                  FE_HIDE24(Yh.n[l]);
+                  s.n[l] = c.n[l] - Yh.n[l];
+                }
+                par = walk_ypar_step(px, s, invk, nxg, X, Y);  // (px again: the same value, and the first one need not be kept)
+              } else {
+                const fe Xc = walk_ypar_copy(X), Yc = walk_ypar_copy(Y), invkc = walk_ypar_copy(invk);
+                par = walk_ypar_exact(tab + (size_t)i * ECL_TAB_STRIDE, which, Xc, Yc, invkc);
+              }
+            }
+          } else {
+            py = fe_sub(fe_mul(lam, fe_add(X, fe_neg(px, 4))), Y);         // X - px: magnitude 6; py: magnitude 3
+          }
 #endif
           off = base + (which == 0 ? B + 1 + i : B - 1 - i);  // scalar select, one 64-bit add
           valid = which == 1 || i + 1 < B;
@@ -119,6 +149,7 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
             FE_HIDE24(px.n[l]);
             FE_HIDE24(py.n[l]);
           }
+          if constexpr (PAR33) par = emit33_parity(py);
         }
 #endif
         if (valid) {
@@ -133,7 +164,7 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
 #elif defined(ECL_WALK_PREFIX)
           check_point<A33, A65, false, ENDO, ETH, true>(a, &q, live, px, py, off);
 #else
-          if constexpr (A33 && !A65 && !ECL_WALK_P2SH && !ETH) check_point33<ENDO>(a, &q, live, px, py, off);
+          if constexpr (PAR33) check_point33<ENDO>(a, &q, live, px, par, off);
           else check_point<A33, A65, ECL_WALK_P2SH, ENDO, ETH>(a, &q, live, px, py, off);
 #endif
         }

@@ -16,7 +16,21 @@
 //     carry pass at all.  n[8] << 5 needs n[8] < 2^27: y has magnitude <= 3 here;
 //   * probe 0's index, a[0] << 24 | a[1] >> 24 of the h160_t words (bloom.h), is byte selections of RIPEMD-160's native chaining
 //     words: one v_perm_b32 and one and-or per half, instead of four byte swaps and the 64-bit shifts.  The h160_t byte order is applied
-//     where a record is parked in the ring (cand_push), not before.
+//     where a record is parked in the ring (cand_push), not before;
+//   * y of a walked point is lam b - Y (b = X - x3), and of that product the parity formula above reads bit 0 of limb 0, the top five
+//     bits of limb 7 and limb 8.  emit33_ypar runs fe_mul's two streams for those alone: the d stream (columns 8..16) whole, the c stream
+//     from column 6 on, started at u_5 R1 - what column 5 hands up less its carry x = c_5 >> 29.  No product of columns 0..5 (21), no
+//     u_k R0 for k <= 5, no u_k R1 for k <= 4, nothing of the tail past limb 8.
+//       - Every column sum of fe_mul is below 2^64 (fe256.h), so x < 2^35.  Column 6 comes out low by x, its carry into column 7 low by
+//         e, 0 <= e <= (x >> 29) + 1 <= 64, and so does c7, the sum of column 7 before it is masked.  Of c7 only bits >= 24 are read
+//         (limb 7's top five bits, and the carry into limb 8 with all that follows from it: limb 8, and ct = c >> 24 of the tail), and
+//         those are the true ones unless (c7 mod 2^24) + e reaches 2^24: (c7 mod 2^24) >= 2^24 - G with G = 256 >= 65 selects the exact
+//         product (2^-16 per key); below it the low 24 bits of c7 are the true ones less e, no more.
+//       - Bit 0 of the product's limb 0, ((a0 b0 + u_0 R0) mod 2^29 + (ct + d 2^13) 977) mod 2^29, is (a0 & b0 ^ ct) & 1: R0 and d 2^13
+//         are even, 977 is odd.  y = product + 2p - Y limb-wise (fe_sub): bit 0 flips with Y's, limbs 7 and 8 get 2 p_i - Y_i.
+//       - Limb 7 of y is low by e as well, so the estimate A of the item above is floor(S / 2^227) less 0, 1 or 2 here: k = A >> 29
+//         unless the low 29 bits of A are at 2^29 - 2 or above, and r + k (2^32 + 977) >= p needs them at 2^29 - 3 or above.  One test,
+//         (A mod 2^29) >= 2^29 - 3 (2^-27 per key), beside the guard; both select the same exact path, fe_parity(fe_mul(lam, b) - Y).
 #pragma once
 #include "bloom.h"
 #include "hash160.h"
@@ -75,6 +89,68 @@ FE_FN u32 emit33_parity(const fe& y) {
   const u32 A = (y.n[8] << 5) + (y.n[7] >> 24);
   if (__builtin_expect((A & FE_M) >= FE_M - 1u, 0)) return fe_parity(y);
   return (y.n[0] ^ (A >> 29)) & 1u;
+}
+// parity of the canonical residue of a b - Y by the short way alone (a: magnitude 1, b: magnitude <= 6, Y: magnitude 1), and in `rare`
+// whether it may be relied on: 0, or 1 where the guard or the test on A asks for the exact product.  fe_mul's schedule with the c stream
+// started at column 6; c7_out (if asked for) gets the low word of column 7's truncated sum, for the tests
+#define EMIT33_YPAR_G 256u
+FE_FN u32 emit33_ypar_short(const fe& a, const fe& b, const fe& Y, u32& rare, u32* c7_out = nullptr) {
+  u64 c = 0, d = 0;
+  const u32 R1 = fe_opaque(FE_R1);
+#pragma unroll
+  for (int i = 0; i < 9; ++i) {
+    FE_PIN64(d);
+    d += (u64)a.n[i] * b.n[8 - i];
+  }
+  const u32 t8 = (u32)d & FE_M;
+  d >>= 29;
+  u32 c7 = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+#pragma unroll
+    for (int i = k + 1; i < 9; ++i) {
+      FE_PIN64(d);
+      d += (u64)a.n[i] * b.n[9 + k - i];
+    }
+    const u32 u = (u32)d & FE_M;
+    d >>= 29;
+    if (k < 5) continue;  // u_0..u_4: shifted out, not used
+    if (k > 5) {
+#pragma unroll
+      for (int i = 0; i <= k; ++i) {
+        FE_PIN64(c);
+        c += (u64)a.n[i] * b.n[k - i];
+      }
+      FE_PIN64(c);
+      c += (u64)u * FE_R0;
+      if (k == 7) c7 = (u32)c;
+      c >>= 29;
+    }
+    FE_PIN64(c);
+    c += (u64)u * R1;
+  }
+  u32 dd = (u32)d;
+  FE_HIDE24(dd);
+  c += (u64)dd * FE_R0 + t8;
+  const u32 ct = (u32)(c >> 24);  // (+ d << 13: even)
+  const u32 y7 = (c7 & FE_M) + (2u * FE_PM - Y.n[7]);
+  const u32 y8 = ((u32)c & FE_TOP) + (2u * FE_P8 - Y.n[8]);
+  const u32 A = (y8 << 5) + (y7 >> 24);
+  if (c7_out) *c7_out = c7;
+  rare = ((c7 & FE_TOP) >= (1u << 24) - EMIT33_YPAR_G) | ((A & FE_M) >= FE_M - 2u);
+  return ((a.n[0] & b.n[0]) ^ ct ^ Y.n[0] ^ (A >> 29)) & 1u;
+}
+// parity of the canonical residue of y = lam b - Y for a walked point: lam a product (magnitude 1), b = X - x3 (magnitude <= 6), Y
+// magnitude 1.  path (if asked for): 1 when the exact product was taken.  This is the function as a whole, for the host program and the
+// diag op (LIMB_PAR33).  The walk kernels call emit33_ypar_short themselves and go ANOTHER exact way where `rare` is set: they have
+// neither lam nor b to spare by then and walk the point again (add_kernel.h: walk_ypar_step), which tests/test_gpu_par33.py reaches
+// through calls of 2^18 keys and more
+FE_FN u32 emit33_ypar(const fe& lam, const fe& b, const fe& Y, u32* path = nullptr) {
+  u32 rare;
+  u32 par = emit33_ypar_short(lam, b, Y, rare);
+  if (__builtin_expect(rare != 0, 0)) par = fe_parity(fe_sub(fe_mul(lam, b), Y));
+  if (path) *path = rare;
+  return par;
 }
 // hash160 of the key whose message words 0..8 are in w (prefix byte in place): RIPEMD-160's chaining words as they come, o[i] =
 // bswap32 of the h160_t word i

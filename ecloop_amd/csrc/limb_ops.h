@@ -41,7 +41,9 @@ enum {
   // the addr33-only emit path of the add kernels (emit33.h), x = in0 (magnitude <= 4), y = in1 (magnitude <= 3)
   LIMB_EMIT33 = 26,       // out0 = the nine SHA-256 message words (prefix byte in place), out1.n[0..4] = the h160_t words of the hash160,
                           // out1.n[5], n[6] = probe 0's index (low, high word) from the native words; flag = emit33_parity(y)
-  LIMB_OPS = 27
+  LIMB_PAR33 = 27,        // flag = emit33_ypar(lam = in0 (magnitude 1), b = in1 (magnitude <= 6), Y = in2 (magnitude 1)): the parity of lam b - Y;
+                          // out0.n[0] = 1 when the exact product was taken
+  LIMB_OPS = 28
 };
 
 // outputs an operation does not produce are zero; returns false for an unknown op (nothing else fails)
@@ -125,6 +127,7 @@ FE_FN bool limb_op(int op, const fe in[LIMB_IN], fe out[LIMB_OUT], u32& flag) {
     out[1].n[5] = (u32)idx, out[1].n[6] = (u32)(idx >> 32);
     break;
   }
+  case LIMB_PAR33: flag = emit33_ypar(in[0], in[1], in[2], &out[0].n[0]); break;
   default: return false;
   }
   return true;
