@@ -17,6 +17,11 @@ the 26-bit table, a wave of short scalars with one long one, bit lengths 1 ... 6
 the CPU where each one sits.  The records must equal mul_ref.MulRef.records() exactly, each once, the total their number, and the three
 coverage totals must grow by the call's scalars (those without a point are counted, not reported).  Every assertion is an equality.
 
+And shape A again on every context at 8 and at 13 bits (ecl_hip_set_mul_window): at 22 and 26 bits only the planted scalars take the
+out-of-line complete sum, at 8 bits every eighth random scalar has a zero signed digit and the call is mixed into nearly every thread's
+chain - in both rounds of a thread, in the first alone, in the second alone (tests/test_digit_ref.py counts 1820, 13 690 and 13 412 such
+threads; on context `t` k_tr_check meets the same on the tweaks' digits: 1730, 13 468, 13 330).  The expectation does not depend on the width.
+
 Then the calls that produce more records than fit: the header's words for `mul` (ECL_E_OVERFLOW, ecl_hip_fetch_found, the repeat with
 cap = total), and engine.KeySearch.cmd_mul on a context with three records per scalar."""
 import ctypes as C
@@ -85,6 +90,28 @@ def test_every_scalar_of_every_round_and_piece(name):
     finally:
         d.close()
     print("%s: %.1f s with the context's bring-up and both tables" % (name, time.perf_counter() - t0))
+    assert wrong == [], "%s: %s" % (name, "; ".join(wrong))
+
+
+@pytest.mark.parametrize("W", [8, 13])
+@pytest.mark.parametrize("name", list(CONTEXTS))
+def test_every_kernel_at_narrow_widths(name, W):
+    from ecloop_amd import Device
+    K, _ = mul_ref.scalars()
+    ref = mul_ref.ref()
+    letters, kw = CONTEXTS[name]
+    want_a = ref.records(name, 0, NA)
+    assert len(want_a) == len(letters) * int(ref.ok[:NA].sum())  # (the expectation)
+    assert mul_ref.pieces(NA) == [(0, NA, 2, 131328, 0)]  # one piece, two scalars per thread
+    wrong = []
+    d = Device(0, **kw)
+    try:
+        d.set_bloom(ONES)
+        d.set_mul_window(W)
+        checked_call(d, name, K[:NA], want_a, "A, W = %d" % W, wrong)
+        assert d.mul_window() == W
+    finally:
+        d.close()
     assert wrong == [], "%s: %s" % (name, "; ".join(wrong))
 
 
