@@ -139,6 +139,8 @@ void kh_set(void* p, uint32_t i, const uint32_t* xw, const uint32_t* yw) {
   kh_herd* h = (kh_herd*)p;
   h->x[i] = fe_from_words(xw), h->y[i] = fe_from_words(yw);
 }
+// herd_is_dp on the eight canonical words of an x, with the mask k_herd_walk is given for dp bits (dp <= 32)
+int kh_is_dp(const uint32_t* xw, uint32_t dp) { return herd_is_dp(fe_from_words(xw), dp >= 32 ? ~0u : (1u << dp) - 1u); }
 uint64_t kh_zero_factors(void* p) { return ((kh_herd*)p)->zero_factors; }
 uint32_t kh_overflow(void* p) { return ((kh_herd*)p)->overflow; }
 // out: wbits, herd_log2, dp, jb, sb, round_steps, base[4]  (10 words)

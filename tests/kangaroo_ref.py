@@ -79,6 +79,19 @@ def sort_key(rec):
     return identity_of(rec), distance_of(rec), rec[2]
 
 
+def start_of(base, q, r, i):
+    """the start of kangaroo i with offset r: (base + r) G (tame, i even) or Q + r G (wild, i odd); None is the point at infinity"""
+    return add_points(q, point_of(r)) if i & 1 else point_of(base + r)
+
+
+def jump_of(s, T, pt, d):
+    """one jump of one kangaroo standing on pt with distance d, over the distances s and the table points T -> (j, point, distance)"""
+    j = (pt[0] >> 32) & 31
+    if T[j][0] == pt[0]:
+        j = (j + 1) & 31
+    return j, add_points(pt, T[j]), d + s[j]
+
+
 class Herd:
     def __init__(self, base, q, seed, herd_log2, jb, sb):
         self.H = 1 << herd_log2

@@ -59,6 +59,8 @@ def K(tmp_path_factory):
     lib.kh_zero_factors.restype = C.c_uint64
     lib.kh_overflow.argtypes = [V]
     lib.kh_overflow.restype = C.c_uint32
+    lib.kh_is_dp.argtypes = [V, C.c_uint32]
+    lib.kh_is_dp.restype = C.c_int
     lib.kh_plan.argtypes = [V, V, C.c_int, C.c_int, V]
     lib.kh_give_up.argtypes = [V, V, C.c_int, C.c_int, C.c_uint32, V]
     lib.kh_candidates.argtypes = [V] * 5
@@ -161,6 +163,18 @@ def test_distance_overflow_is_reported(K):
         assert K.kh_overflow(mine.h) == 1
     finally:
         mine.close()
+
+
+def test_distinguished_across_the_limb_boundary(K):
+    """herd_is_dp reads limb 0 (bits 0 ... 28) and limb 1 from bit 29 on: for every dp 0 ... 32, on x = 2^b with b on both sides of every dp,
+    and on the four constructed points of tests/kangaroo_cases.py, the answer is Python's x & (2^dp - 1) == 0"""
+    import kangaroo_cases as kc
+    xs = [1 << b for b in range(41)] + [kc.dp_target(name)[2][0] for name in kc.DP_TARGETS]
+    xs += [x | 1 << 255 for x in xs[:41]] + [P - 1, 0]
+    for x in xs:
+        w = words8(x)
+        for dp in range(33):
+            assert bool(K.kh_is_dp(w.ctypes.data, dp)) == (x & ((1 << dp) - 1) == 0), (hex(x), dp)
 
 
 def test_a_kangaroo_on_its_own_table_point_takes_the_next_one(K):
