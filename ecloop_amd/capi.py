@@ -13,6 +13,7 @@ ADDR33, ADDR65, ENDO, P2SH, ETH, TR, PUB = 1, 2, 4, 16, 64, 128, 256
 ORIGIN, INSERT = 512, 1024  # the two walks of `bsgs`, each valid only beside PUB alone (include/ecloop_hip.h)
 HERD = 2048  # the herd of `kangaroo`, valid only beside PUB alone; ord_offs is then the number of distinguished-point bits
 PREFIX = 4096  # the prefix filter in place of the bloom: beside ADDR33 / ADDR65 or ETH, with or without ENDO (include/ecloop_hip.h)
+MASK = 8192  # the mask filter in place of the bloom: beside ETH alone, with or without ENDO / ORIGIN (include/ecloop_hip.h)
 E_ARG = -1
 E_NOBLOOM = -5
 E_RANGE = -6
@@ -137,11 +138,13 @@ class Device:
     """One GPU context (ecl_hip handle)."""
 
     def __init__(self, device=0, a33=True, a65=False, endo=False, ord_offs=0, p2sh=False, eth=False, tr=False, pub=False, origin=False,
-                 insert=False, herd=False, prefix=False):
+                 insert=False, herd=False, prefix=False, mask=False):
         if prefix and (p2sh or tr or pub or insert or herd or not (a33 or a65 or eth)):
             raise ValueError("the prefix filter goes with a33 / a65 or with eth: Device(prefix=True), Device(a33=False, eth=True, prefix=True)")
-        self.prefix = bool(prefix)
-        self.splitkey = bool(prefix and origin)  # the split-key search: the prefix walk from an origin (twelve limbs per start and per verify entry)
+        if mask and (prefix or a33 or a65 or p2sh or tr or pub or insert or herd or not eth):
+            raise ValueError("the mask filter goes with eth alone: Device(a33=False, eth=True, mask=True)")
+        self.prefix, self.mask = bool(prefix), bool(mask)
+        self.splitkey = bool((prefix or mask) and origin)  # the split-key search: the prefix / mask walk from an origin (twelve limbs per start and per verify entry)
         if pub and (a33 or a65 or p2sh or eth or tr):  # (before the library is asked)
             raise ValueError("public keys are searched alone: Device(a33=False, pub=True), with or without endo")
         if (origin or insert) and not self.splitkey and (not pub or endo or (origin and insert)):
@@ -158,7 +161,7 @@ class Device:
         if tr and (a33 or a65 or p2sh or eth or endo):
             raise ValueError("Taproot is searched alone and without the endomorphism: Device(a33=False, tr=True)")
         flags = (ADDR33 if a33 else 0) | (ADDR65 if a65 else 0) | (P2SH if p2sh else 0) | (ETH if eth else 0) | (TR if tr else 0) | (PUB if pub else 0) | (ENDO if endo else 0) | \
-                (ORIGIN if origin else 0) | (INSERT if insert else 0) | (HERD if herd else 0) | (PREFIX if prefix else 0)
+                (ORIGIN if origin else 0) | (INSERT if insert else 0) | (HERD if herd else 0) | (PREFIX if prefix else 0) | (MASK if mask else 0)
         rc = self.lib.ecl_hip_open(C.byref(self.h), device, flags, ord_offs)
         if rc != 0:
             msg = self.lib.ecl_hip_last_error(self.h).decode() if self.h else ""
@@ -190,6 +193,14 @@ class Device:
         if not self.prefix or R.ndim != 2 or R.shape[1] != 10:
             raise ValueError("set_prefixes takes an (n, 10) uint32 table on a Device(prefix=True)")
         self._chk(self.lib.ecl_hip_set_bloom(self.h, R.ctypes.data, 5 * len(R)))
+
+    def set_masks(self, table):
+        """the mask table of a Device(eth=True, mask=True): (n, 10) uint32, m[5] then v[5] per entry, most significant word first, 1 <= n <= 16,
+        no bit of v outside m, no entry twice (engine.mask_table plans one from patterns)"""
+        M = np.ascontiguousarray(table, dtype=np.uint32)
+        if not self.mask or M.ndim != 2 or M.shape[1] != 10:
+            raise ValueError("set_masks takes an (n, 10) uint32 table on a Device(eth=True, mask=True)")
+        self._chk(self.lib.ecl_hip_set_bloom(self.h, M.ctypes.data, 5 * len(M)))
 
     def set_list(self, hashes):
         """sorted unique (n x 5) uint32 hash list for the on-device exact confirm; None / empty removes it"""
@@ -321,7 +332,7 @@ class Device:
         for all, or one per scalar; None in a list stands for the point at infinity)"""
         K = limbs_array(ks)
         if self.splitkey != (origin is not None):
-            raise ValueError("verify(origin=...) goes with Device(prefix=True, origin=True), and only with it")
+            raise ValueError("verify(origin=...) goes with Device(prefix=True, origin=True) or Device(mask=True, origin=True), and only with them")
         if origin is None:
             return K
         pts = list(origin) if isinstance(origin, list) else [origin] * len(K)

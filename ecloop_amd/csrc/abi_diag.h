@@ -84,7 +84,7 @@ extern "C" int ecl_hip_diag_hash160(ecl_hip* h, const uint64_t (*x)[4], const ui
 }
 
 extern "C" int ecl_hip_bloom_insert(ecl_hip* h, const uint32_t (*h160)[5], uint64_t n) {
-  if (!h || (!h160 && n) || (h->flags & ECL_PREFIX)) return ECL_E_ARG;
+  if (!h || (!h160 && n) || (h->flags & (ECL_PREFIX | ECL_MASK))) return ECL_E_ARG;
   if (!h->d_bloom.p) return ECL_E_NOBLOOM;
   if (n == 0) return ECL_OK;
   la_leave(h), h->la_key_valid = false;  // the resident filter is no longer the one that was uploaded: no shared look-ahead on it
@@ -104,7 +104,7 @@ extern "C" int ecl_hip_bloom_insert(ecl_hip* h, const uint32_t (*h160)[5], uint6
 }
 
 extern "C" int ecl_hip_bloom_insert_count(ecl_hip* h, const uint32_t (*h160)[5], uint64_t n, uint64_t* added) {
-  if (!h || (!h160 && n) || !added || (h->flags & ECL_PREFIX)) return ECL_E_ARG;
+  if (!h || (!h160 && n) || !added || (h->flags & (ECL_PREFIX | ECL_MASK))) return ECL_E_ARG;
   *added = 0;
   if (!h->d_bloom.p) return ECL_E_NOBLOOM;
   if (n == 0) return ECL_OK;
@@ -139,7 +139,7 @@ extern "C" int ecl_hip_bloom_insert_count(ecl_hip* h, const uint32_t (*h160)[5],
 }
 
 extern "C" int ecl_hip_get_bloom(ecl_hip* h, uint64_t* bits, uint64_t nwords) {
-  if (!h || !bits || (h->flags & ECL_PREFIX)) return ECL_E_ARG;
+  if (!h || !bits || (h->flags & (ECL_PREFIX | ECL_MASK))) return ECL_E_ARG;
   if (!h->d_bloom.p) return ECL_E_NOBLOOM;
   if (nwords != h->bloom_words) return ECL_E_ARG;
   HIPCHK(h, hipSetDevice(h->dev));
@@ -159,6 +159,8 @@ extern "C" int ecl_hip_diag_bloom(ecl_hip* h, const uint32_t (*h160)[5], uint8_t
   HIPCHK(h, hipMemcpy(dh.p, h160, (size_t)n * 20, hipMemcpyHostToDevice));
   if (h->flags & ECL_PREFIX)  // the device's two-stage prefix test on the given values
     hipLaunchKernelGGL(k_diag_prefix, dim3((n + 63) / 64), dim3(64), 0, h->stream, prefix_of(h), dh.p, dhit.p, n);
+  else if (h->flags & ECL_MASK)  // the device's mask test on the given values
+    hipLaunchKernelGGL(k_diag_mask, dim3((n + 63) / 64), dim3(64), 0, h->stream, mask_of(h), dh.p, dhit.p, n);
   else
     hipLaunchKernelGGL(k_diag_bloom, dim3((n + 63) / 64), dim3(64), 0, h->stream, bloom_make(h->d_bloom.p, h->bloom_words),
                        dh.p, dhit.p, n);
@@ -243,7 +245,7 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   devbuf<u64> keep_bloom;
   devbuf<u32> keep_list, keep_tab;
   const u64 save_words = h->bloom_words, save_list_n = h->list_n;
-  const u32 save_prefix_n = h->prefix_n, save_tab_B = h->tab_B;
+  const u32 save_prefix_n = h->prefix_n, save_mask_n = h->mask_n, save_tab_B = h->tab_B;
   keep_bloom.swap(h->d_bloom), keep_list.swap(h->d_list), keep_tab.swap(h->d_tab);
   h->bloom_words = 0, h->list_n = 0, h->tab_B = 0;
   // ECL_ORIGIN: the same walk from the origin O = 0xdc2a04 G (its x, y from (1)), against the double-and-add kernel's (start + j s + 0xdc2a04) G;
@@ -262,6 +264,9 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   if (h->flags & ECL_PREFIX) {
     ones.assign(5, 0ull);
     ones[2] = ~0ull << 32, ones[3] = ones[4] = ~0ull;
+    rc = ecl_hip_set_bloom(h, ones.data(), 5);
+  } else if (h->flags & ECL_MASK) {  // ECL_MASK: one entry with an all-zero mask matches every value
+    ones.assign(5, 0ull);
     rc = ecl_hip_set_bloom(h, ones.data(), 5);
   } else {
     rc = ecl_hip_set_bloom(h, ones.data(), ones.size());
@@ -295,7 +300,7 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
   // restore the caller's state whatever happened; the test's own filter and table are freed here, not at the end of the function
   keep_bloom.swap(h->d_bloom), keep_list.swap(h->d_list), keep_tab.swap(h->d_tab);
   keep_bloom.reset(), keep_tab.reset();
-  h->bloom_words = save_words, h->prefix_n = save_prefix_n, h->list_n = save_list_n, h->tab_B = save_tab_B;
+  h->bloom_words = save_words, h->prefix_n = save_prefix_n, h->mask_n = save_mask_n, h->list_n = save_list_n, h->tab_B = save_tab_B;
   h->B = saveB, h->Tmax = saveT, h->B_auto = saveAuto;
   h->walk_valid = false;
   h->kernel_ms = 0, h->launches = 0, h->keys = 0, h->setup_ms = 0, h->setups = 0;

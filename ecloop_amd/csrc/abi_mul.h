@@ -321,7 +321,7 @@ extern "C" int ecl_hip_reserve_mul(ecl_hip* h, uint32_t n, uint32_t cap) {
 extern "C" int ecl_hip_mul_batch(ecl_hip* h, const uint64_t (*scalars)[4], uint32_t n, ecl_found* out, uint32_t cap,
                                  uint32_t* nout) {
   if (!h || (!scalars && n) || (!out && cap) || !nout || cap > ECL_CAP_MAX) return ECL_E_ARG;
-  if (h->flags & (ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX)) return ECL_E_ARG;  // the walks of `bsgs` and prefix contexts have no `mul`
+  if (h->flags & (ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX | ECL_MASK)) return ECL_E_ARG;  // the walks of `bsgs`, prefix and mask contexts have no `mul`
   *nout = 0;
   if (!h->d_bloom.p) return ECL_E_NOBLOOM;
   if (n == 0) return ECL_OK;
@@ -379,7 +379,7 @@ extern "C" int ecl_hip_mul_batch(ecl_hip* h, const uint64_t (*scalars)[4], uint3
 extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t text_bytes, const uint64_t* lines, uint32_t n, ecl_found* out,
                                      uint32_t cap, uint32_t* nout) {
   if (!h || (!text && text_bytes) || (!lines && n) || (!out && cap) || !nout || n > MUL_RAW_MAX || text_bytes > 0xFFFFFFF0u || cap > ECL_CAP_MAX) return ECL_E_ARG;
-  if (h->flags & (ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX)) return ECL_E_ARG;
+  if (h->flags & (ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX | ECL_MASK)) return ECL_E_ARG;
   *nout = 0;
   if (!h->d_bloom.p) return ECL_E_NOBLOOM;
   if (n == 0) return ECL_OK;
@@ -467,10 +467,10 @@ extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t t
   return count_call(h, n, f.finish());
 }
 
-// Split-key contexts (ECL_PREFIX | ECL_ORIGIN): an entry of ecl_hip_verify / ecl_hip_verify_eth is twelve limbs - the scalar, then x and y of
+// Split-key contexts (ECL_PREFIX | ECL_ORIGIN, ECL_MASK | ECL_ORIGIN): an entry of ecl_hip_verify / ecl_hip_verify_eth is twelve limbs - the scalar, then x and y of
 // its origin (k_verify_origin, k_verify_origin_eth).  Every origin is checked on the host like the origin of a walk (a point of the curve;
 // all eight limbs zero: the point at infinity, the sum is k G alone), ECL_E_ARG otherwise and nothing is launched.  h65 = nullptr: the eth half.
-static bool verify_takes_origins(const ecl_hip* h) { return (h->flags & (ECL_PREFIX | ECL_ORIGIN)) == (ECL_PREFIX | ECL_ORIGIN); }
+static bool verify_takes_origins(const ecl_hip* h) { return (h->flags & ECL_ORIGIN) && (h->flags & (ECL_PREFIX | ECL_MASK)); }
 static int verify_origin(ecl_hip* h, const uint64_t* k, uint32_t n, uint32_t (*h33)[5], uint32_t (*h65)[5], uint8_t* ok) {
   if (n > (1u << 24)) return ECL_E_ARG;  // (hits of one call; 96 bytes each on the host first)
   std::vector<u32> ent((size_t)n * VERIFY_ORIGIN_WORDS);

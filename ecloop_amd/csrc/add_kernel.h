@@ -26,6 +26,7 @@
 #include "keccak.h"
 #include "pub_emit.h"
 #include "prefix.h"
+#include "mask.h"
 
 struct ecl_found_dev {
   u64 key_offset;
@@ -42,6 +43,7 @@ struct add_args {
   union {
     bloom_t bloom;
     prefix_t prefix;  // the prefix kernels (k_add_pfx, k_add_pfx_eth): bitmap, range table, n, bucket shift in the same 24 bytes
+    mask_t mask;      // the mask kernels (k_add_msk_eth): table, n, padding in the same 24 bytes
   };
   union {
     ecl_found_dev* found;
@@ -228,10 +230,25 @@ __device__ __forceinline__ void prefix_finish(const add_args& a, cand_queue& qa)
   if (valid && prefix_exact(a.prefix, r.h)) found_push(a, r.off, r.h, r.tag & 0xff, (r.tag >> 8) & 3);
 }
 __device__ __forceinline__ void prefix_flush(const add_args& a, cand_queues& q) { prefix_finish(a, q.a); }  // A holds < 64
-template <bool P2SH, bool PREFIX = false>
+// ---- the mask kernels' filter (mask.h): the test is exact on the spot, so ring A alone parks the records - it is there so that found_push
+// (an atomic and a 32-byte store under divergence) stays out of the per-key loop - and is drained 64 at a time and at the end.  One record
+// per (key, image) however many entries match: mask_has answers once.
+__device__ __forceinline__ void mask_finish(const add_args& a, cand_queue& qa) {
+  bool valid;
+  const cand_rec r = cand_take(qa, valid);
+  if (valid) found_push(a, r.off, r.h, r.tag & 0xff, (r.tag >> 8) & 3);
+}
+__device__ __forceinline__ void mask_flush(const add_args& a, cand_queues& q) { mask_finish(a, q.a); }  // A holds < 64
+// PREFIX: 0 the bloom, 1 the prefix filter, 2 the mask filter
+template <bool P2SH, int PREFIX = 0>
 __device__ __forceinline__ void filter_check(const add_args& a, cand_queues* q, bool live, u64 off, const u32 h[5], u32 endo,
                                              u32 compressed) {
-  if (PREFIX) {
+  if (PREFIX == 2) {
+    const bool in = live && mask_has(a.mask, h);
+    if (cand_append(q->a, in, off, h, endo | (compressed << 8))) mask_finish(a, q->a);
+    return;
+  }
+  if (PREFIX == 1) {
     const bool in = live && prefix_stage1(a.prefix, h);
     if (cand_append(q->a, in, off, h, endo | (compressed << 8))) prefix_finish(a, q->a);
     return;
@@ -251,7 +268,7 @@ __device__ __forceinline__ void filter_check(const add_args& a, cand_queues* q, 
 // ETH (no reference counterpart, searched alone: A33 = A65 = P2SH = false): the Ethereum address of the point, Keccak-256 over x || y
 // (keccak.h), type 3; x and y are normalised and the endomorphism images formed as for addr65.
 // x: magnitude <= 4, y: magnitude <= 3.
-template <bool A33, bool A65, bool P2SH, bool ENDO, bool ETH = false, bool PREFIX = false>
+template <bool A33, bool A65, bool P2SH, bool ENDO, bool ETH = false, int PREFIX = 0>
 __device__ __forceinline__ void check_point(const add_args& a, cand_queues* q, bool live, fe x, fe y, u64 off) {
   u32 xw[3][8], yw[2][8], par = 0;
   if (ENDO) {
@@ -576,5 +593,20 @@ __device__ __forceinline__ void pub_insert(const add_args& a, bool live, const f
 #undef ECL_WALK_KERNEL
 #undef ECL_WALK_ETH
 #undef ECL_WALK_PREFIX
+#undef ECL_WALK_P2SH
+#undef ECL_WALK_WAVES
+// Mask instantiations (-p 0xdead*beef, ECL_MASK): k_add_msk_eth<ENDO>, the walk and Keccak of k_add_pfx_eth with the mask filter (mask.h) in
+// place of the prefix filter; one ring, the waves per SIMD of the kernel they mirror.
+#define ECL_WALK_KERNEL k_add_msk_eth
+#define ECL_WALK_ETH
+#define ECL_WALK_PREFIX
+#define ECL_WALK_MASK
+#define ECL_WALK_P2SH false
+#define ECL_WALK_WAVES ECL_ETH_WAVES
+#include "add_walk.inc"
+#undef ECL_WALK_KERNEL
+#undef ECL_WALK_ETH
+#undef ECL_WALK_PREFIX
+#undef ECL_WALK_MASK
 #undef ECL_WALK_P2SH
 #undef ECL_WALK_WAVES

@@ -6,6 +6,8 @@
 // With ECL_WALK_PUB defined the kernel is k_add_pub<ENDO>: public keys by x - no y of a walked point, pub_check in place of check_point.
 // With ECL_WALK_PREFIX defined (alone or beside ECL_WALK_ETH) the kernel is k_add_pfx<A33, A65, ENDO> / k_add_pfx_eth<ENDO>: the prefix
 // filter (prefix.h) in place of the bloom, one candidate ring.
+// With ECL_WALK_MASK defined beside ECL_WALK_PREFIX and ECL_WALK_ETH the kernel is k_add_msk_eth<ENDO>: the mask filter (mask.h) in place of
+// the prefix filter, the same one ring.
 // With ECL_WALK_INSERT defined beside ECL_WALK_PUB the kernel is k_add_pub_ins (no template): pub_insert in place of pub_check, no rings.
 #if defined(ECL_WALK_TR) || defined(ECL_WALK_INSERT)
 #elif defined(ECL_WALK_ETH) || defined(ECL_WALK_PUB)
@@ -161,8 +163,10 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
           pub_insert(a, live, px);
 #elif defined(ECL_WALK_PUB)
           pub_check<ENDO>(a, q, live, px, off);
+#elif defined(ECL_WALK_MASK)
+          check_point<A33, A65, false, ENDO, ETH, 2>(a, &q, live, px, py, off);
 #elif defined(ECL_WALK_PREFIX)
-          check_point<A33, A65, false, ENDO, ETH, true>(a, &q, live, px, py, off);
+          check_point<A33, A65, false, ENDO, ETH, 1>(a, &q, live, px, py, off);
 #else
           if constexpr (PAR33) check_point33<ENDO>(a, &q, live, px, par, off);
           else check_point<A33, A65, ECL_WALK_P2SH, ENDO, ETH>(a, &q, live, px, py, off);
@@ -187,6 +191,8 @@ __global__ void __launch_bounds__(ECL_ADD_BLOCK, ECL_WALK_WAVES) ECL_WALK_KERNEL
 #if defined(ECL_WALK_INSERT)
 #elif defined(ECL_WALK_PUB)
   cand1_flush<5u, true>(a, q);
+#elif defined(ECL_WALK_MASK)
+  mask_flush(a, q);
 #elif defined(ECL_WALK_PREFIX)
   prefix_flush(a, q);
 #elif !defined(ECL_WALK_TR)

@@ -80,6 +80,15 @@ __global__ void k_diag_prefix(prefix_t p, const u32* h160, u8* hit, u32 n) {
   for (int w = 0; w < 5; ++w) h[w] = h160[(size_t)i * 5 + w];
   hit[i] = prefix_has(p, h) ? 1 : 0;
 }
+// ... and for a mask context: the mask filter (mask.h)
+__global__ void k_diag_mask(mask_t m, const u32* h160, u8* hit, u32 n) {
+  u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u32 h[5];
+#pragma unroll
+  for (int w = 0; w < 5; ++w) h[w] = h160[(size_t)i * 5 + w];
+  hit[i] = mask_has(m, h) ? 1 : 0;
+}
 
 // bloom_mod alone, for any filter size (no bit array needed): pins the reciprocal modulo of both width classes
 __global__ void k_diag_bloom_mod(bloom_t b, const u64* x, u64* r, u32 n) {

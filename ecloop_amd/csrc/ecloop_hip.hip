@@ -68,6 +68,7 @@ struct ecl_hip {
   bool ctab_valid = false;
   devbuf<uint4> d_scr; devbuf<u32> d_scr2;     // prefix-product chains (ensure_scratch)
   devbuf<u64> d_bloom; u64 bloom_words = 0;
+  u32 mask_n = 0;    // ECL_MASK: d_bloom holds the table of mask_n entries (five 64-bit words each) and nothing else
   u32 prefix_n = 0;  // ECL_PREFIX: d_bloom holds the stage-1 bitmap (PREFIX_BITMAP_WORDS64 words) and behind it the table of prefix_n ranges
   // `mul`: scalars travel in pieces through MUL_NBUF device buffers (and as many pinned staging buffers for pageable callers), the copy
   // engine running up to MUL_NBUF - 1 pieces ahead of the kernel
@@ -162,14 +163,16 @@ const char* ecl_hip_last_error(const ecl_hip* h) { return h ? h->err.c_str() : "
 int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   const u32 types = ECL_ADDR33 | ECL_ADDR65 | ECL_P2SH;
   if (!out || ord_offs > 255 || !(flags & (types | ECL_ETH | ECL_TR | ECL_PUB)) ||
-      (flags & ~(types | ECL_ETH | ECL_TR | ECL_PUB | ECL_ENDO | ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX)))
+      (flags & ~(types | ECL_ETH | ECL_TR | ECL_PUB | ECL_ENDO | ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX | ECL_MASK)))
     return ECL_E_ARG;
+  // the mask filter: beside eth alone, with or without the endomorphism and, for a split-key search, from an origin
+  if ((flags & ECL_MASK) && (!(flags & ECL_ETH) || (flags & ~(ECL_MASK | ECL_ETH | ECL_ENDO | ECL_ORIGIN)))) return ECL_E_ARG;
   // the prefix filter: beside addr33 / addr65 or beside eth, with or without the endomorphism
   // (and, for a split-key search, from an origin: ECL_PREFIX | ECL_ORIGIN beside the same types)
   if ((flags & ECL_PREFIX) && (flags & ~(ECL_PREFIX | ECL_ORIGIN | ECL_ADDR33 | ECL_ADDR65 | ECL_ETH | ECL_ENDO))) return ECL_E_ARG;
   // the two walks of `bsgs`: each valid only as ECL_PUB | ECL_ORIGIN / ECL_PUB | ECL_INSERT (no endomorphism, no other type, not both);
-  // the origin of a hashing walk only on a prefix context
-  if ((flags & ECL_ORIGIN) && !(flags & ECL_PREFIX) && flags != (ECL_PUB | ECL_ORIGIN)) return ECL_E_ARG;
+  // the origin of a hashing walk only on a prefix or a mask context
+  if ((flags & ECL_ORIGIN) && !(flags & (ECL_PREFIX | ECL_MASK)) && flags != (ECL_PUB | ECL_ORIGIN)) return ECL_E_ARG;
   if ((flags & ECL_INSERT) && flags != (ECL_PUB | ECL_INSERT)) return ECL_E_ARG;
   // the herd of `kangaroo`: valid only as ECL_PUB | ECL_HERD; ord_offs is the number of distinguished-point bits
   if ((flags & ECL_HERD) && (flags != (ECL_PUB | ECL_HERD) || ord_offs > 32)) return ECL_E_ARG;
@@ -197,7 +200,7 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   static std::mutex mu;
   static std::set<u32> passed;
   const char* skip = getenv("ECL_HIP_SKIP_SELFTEST");
-  const u32 key = (u32)device * 8192u + flags;  // flags < 8192
+  const u32 key = (u32)device * 16384u + flags;  // flags < 16384
   {
     std::lock_guard<std::mutex> lk(mu);
     if ((skip && skip[0] == '1') || passed.count(key)) return ECL_OK;
@@ -256,10 +259,33 @@ static int prefix_set_table(ecl_hip* h, const u32* table, uint64_t nwords) {
   h->bloom_words = img.size(), h->prefix_n = n;
   return ECL_OK;
 }
+// ECL_MASK: the filter words are the mask table (ten 32-bit words per entry) and go to the device as they are.  A refused table leaves the
+// context with none
+static mask_t mask_of(const ecl_hip* h) {
+  mask_t m;
+  memset(&m, 0, sizeof m);
+  m.table = (const u32*)h->d_bloom.p, m.n = h->mask_n;
+  return m;
+}
+static int mask_set_table(ecl_hip* h, const u32* table, uint64_t nwords) {
+  HIPCHK(h, hipSetDevice(h->dev));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->d_bloom.reset(), h->bloom_words = 0, h->mask_n = 0;
+  if (nwords % 5 != 0 || !mask_table_ok(table, nwords / 5)) {
+    h->err = "ecl_hip_set_bloom: a mask table is 1 ... 16 entries m[5], v[5] with no bit of v outside m and no entry twice";
+    return ECL_E_ARG;
+  }
+  HIPCHK(h, h->d_bloom.grow(nwords));
+  HIPCHK(h, hipMemcpyAsync(h->d_bloom.p, table, nwords * sizeof(u64), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->bloom_words = nwords, h->mask_n = (u32)(nwords / 5);
+  return ECL_OK;
+}
 extern "C" {
 int ecl_hip_set_bloom(ecl_hip* h, const uint64_t* bits, uint64_t nwords) {
   if (!h || !bits || nwords == 0 || nwords >= (1ull << 58)) return ECL_E_ARG;
   if (h->flags & ECL_PREFIX) return prefix_set_table(h, (const u32*)bits, nwords);
+  if (h->flags & ECL_MASK) return mask_set_table(h, (const u32*)bits, nwords);
   HIPCHK(h, hipSetDevice(h->dev));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   la_leave(h), h->la_key_valid = false;
@@ -290,7 +316,7 @@ void ecl_hip_free_host(void* p) {
 }
 
 int ecl_hip_set_list(ecl_hip* h, const uint32_t (*h160)[5], uint64_t n) {
-  if (!h || (n && !h160) || (h->flags & ECL_PREFIX)) return ECL_E_ARG;
+  if (!h || (n && !h160) || (h->flags & (ECL_PREFIX | ECL_MASK))) return ECL_E_ARG;
   for (uint64_t i = 1; i < n; ++i) {  // strictly increasing in compare_160 order (addr.c:18-26)
     int c = 0;
     for (int k = 0; k < 5 && c == 0; ++k) c = h160[i - 1][k] < h160[i][k] ? -1 : (h160[i - 1][k] > h160[i][k] ? 1 : 0);
@@ -452,6 +478,7 @@ typedef void (*add_kernel_t)(const add_args);
 // every non-empty set of address types (ecl_hip_open refuses the empty one) x endo
 static add_kernel_t pick_add_kernel(u32 flags) {
   const bool endo = flags & ECL_ENDO;
+  if (flags & ECL_MASK) return endo ? k_add_msk_eth<true> : k_add_msk_eth<false>;  // beside eth alone (ecl_hip_open): the mask filter
   if (flags & ECL_PREFIX) {  // beside addr33 / addr65 or eth (ecl_hip_open): the prefix filter in place of the bloom
     if (flags & ECL_ETH) return endo ? k_add_pfx_eth<true> : k_add_pfx_eth<false>;
     switch (flags & (ECL_ADDR33 | ECL_ADDR65)) {
@@ -881,6 +908,7 @@ static add_launched add_launch(ecl_hip* h, const call_frame& f, const u256& k0, 
   memcpy(a.jump, h->jump_host, sizeof a.jump);
   a.cxy = h->d_cxy.p, a.scratch = h->d_scr.p, a.scratch2 = h->d_scr2.p;
   if (h->flags & ECL_PREFIX) a.prefix = prefix_of(h);
+  if (h->flags & ECL_MASK) a.mask = mask_of(h);
   if (slab) a.slab = slab, a.epoch = h->tr_epoch;
   a.B = B, a.T = T, a.nb = nb, a.nkeys = nkeys;
   if (h->diag_drop) h->diag_drop = false, a.nb = nb - 1;  // (test hook: lane 0's last group is in the range, so keys go missing)
@@ -976,8 +1004,8 @@ extern "C" int ecl_hip_add_range(ecl_hip* h, const uint64_t start[4], uint64_t n
     }
     memcpy(h->origin_w, ow, sizeof ow);
   }
-  // the walks of `bsgs` and prefix contexts never take part in the look-ahead
-  if (h->flags & (ECL_ORIGIN | ECL_INSERT | ECL_PREFIX)) return count_call(h, nkeys, add_core(h, k0, nkeys, out, cap, nout));
+  // the walks of `bsgs`, prefix and mask contexts never take part in the look-ahead
+  if (h->flags & (ECL_ORIGIN | ECL_INSERT | ECL_PREFIX | ECL_MASK)) return count_call(h, nkeys, add_core(h, k0, nkeys, out, cap, nout));
   return count_call(h, nkeys, la_dispatch(h, k0, nkeys, out, cap, nout));
 }
 

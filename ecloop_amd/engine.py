@@ -239,7 +239,7 @@ class KeySearch:
     """ctx_t + cmd_add / cmd_mul for one GPU."""
 
     def __init__(self, flt, device=0, a33=True, a65=False, endo=False, ord_offs=0, verify=True, launch_keys=1 << 32,
-                 half_group=0, max_lanes=0, device_cls=None, p2sh=False, eth=False, tr=False, pub=False, prefix=False, origin=None):
+                 half_group=0, max_lanes=0, device_cls=None, p2sh=False, eth=False, tr=False, pub=False, prefix=False, origin=None, mask=False):
         if pub:
             a33 = False  # public keys are searched alone (with or without the endomorphism)
         elif tr:
@@ -264,16 +264,20 @@ class KeySearch:
             kw["pub"] = True
         if prefix:  # flt: a PrefixFilter - the range table stands where the bloom words stand (prefix_search)
             kw["prefix"] = True
+        if mask:  # flt: a MaskFilter - the mask table stands where the bloom words stand (prefix_search with a ? or * pattern)
+            kw["mask"] = True
         self.origin = None  # split-key search (prefix_search(origin=)): the walk is O + k G, the records' keys are partial keys
         if origin is not None:
-            if not prefix:
+            if not (prefix or mask):
                 raise ValueError("an origin goes with the prefix search only (prefix_search(origin=(x, y)))")
             self.origin = (int(origin[0]), int(origin[1]))
             kw["origin"] = True
         self.dev = (device_cls or Device)(device, a33=a33, a65=a65, endo=endo, ord_offs=ord_offs, **kw)
         if half_group or max_lanes:
             self.dev.set_geometry(half_group, max_lanes)
-        if prefix:
+        if mask:
+            self.dev.set_masks(flt.table)
+        elif prefix:
             self.dev.set_prefixes(flt.table)
         else:
             self.dev.set_bloom(flt.words)
@@ -582,14 +586,94 @@ def address_eth(h160):
     return "0x" + _h160_bytes(h160).hex()
 
 
+# ---- Ethereum patterns with wildcards and suffixes (0xdead*beef): the mirror of ecloop_amd/host/mask_plan.h (the grammar is written there)
+MASK_MAX_ENTRIES = 16
+
+
+def mask_is_masked(s):
+    """a 0x pattern with ? or *: what sends a whole list to the mask table"""
+    return _prefix_form(s) == "hex" and ("?" in s[2:] or "*" in s[2:])
+
+
+def mask_pattern_entry(s, eth=True):
+    """one pattern of a masked list -> (mask, value, digits): 160-bit integers and the number of hex digits the pattern fixes"""
+    def fail(reason):
+        raise PrefixError("pattern '%s': %s" % (s, reason))
+
+    if not s or len(s) > 44:
+        fail("no address can start with it (empty or too long)")
+    if _prefix_form(s) != "hex":
+        _pattern_ranges(s, False, False, eth)  # (the other forms fail the type check of -a e, or the line below)
+        fail("a list with ? or * holds 0x patterns only")
+    if not eth:
+        fail("a 0x pattern needs -a e")
+    d = s[2:]
+    stars = 0
+    for c in d:
+        if c == "*":
+            stars += 1
+            if stars > 1:
+                fail("more than one * (a pattern has one run of free digits at most)")
+        elif c != "?" and c not in "0123456789abcdefABCDEF":
+            fail("a character that is no hex digit")
+    head, tail = d.split("*") if stars else (d, "")
+    if not stars and not head:
+        fail("no address can start with it (1 ... 40 hex digits after 0x)")
+    if len(head) + len(tail) > 40:
+        fail("no address can match it (too long: an address has 40 digits)")
+    m = v = digits = 0
+    for k, c in [(i, c) for i, c in enumerate(head)] + [(40 - len(tail) + j, c) for j, c in enumerate(tail)]:
+        if c != "?":
+            m |= 0xF << (4 * (39 - k))
+            v |= int(c, 16) << (4 * (39 - k))
+            digits += 1
+    if not digits:
+        fail("no hex digit at all: every address matches it")
+    return m, v, digits
+
+
+def mask_table(patterns, eth=True):
+    """-> (table, serves): the (n, 10) uint32 mask table of Device.set_masks - m[5], v[5], most significant word first, the distinct entries
+    in the order of their first pattern - and per entry the ascending list of the indices of the patterns it serves.  Raises PrefixError
+    for a refused pattern, for more than 16 distinct entries and for a list whose entries together may cover more than 2^-16 of the space"""
+    from fractions import Fraction
+    patterns = list(patterns)
+    if not patterns:
+        raise PrefixError("no patterns given")
+    entries, serves, total = [], [], Fraction(0)
+    for i, p in enumerate(patterns):
+        m, v, digits = mask_pattern_entry(p, eth)
+        if (m, v) in entries:
+            serves[entries.index((m, v))].append(i)
+            continue
+        if len(entries) == MASK_MAX_ENTRIES:
+            raise PrefixError("the patterns ('%s', ...) need more than 16 mask entries: split the list" % patterns[0])
+        entries.append((m, v))
+        serves.append([i])
+        total += Fraction(1, 16 ** digits)
+    if total > Fraction(2) ** PREFIX_MAX_FRACTION_LOG2:
+        raise PrefixError("the patterns ('%s'%s) cover more than 2^-16 of all addresses: one launch would report more records than the device keeps; lengthen the pattern"
+                          % (patterns[0], ", ..." if len(patterns) > 1 else ""))
+    table = np.array([_words5(m) + _words5(v) for m, v in entries], dtype=np.uint32).reshape(-1, 10)
+    return table, serves
+
+
+def _hex_pattern_matches(p, a):
+    """does the lower-case text a = 0x + 40 digits match the 0x pattern p: by the text, ? any digit, the part after a * at the end"""
+    d = p[2:].lower()
+    head, tail = d.split("*") if "*" in d else (d, "")
+    body = a[2:]
+    return len(head) + len(tail) <= 40 and all(c in ("?", body[i]) for i, c in enumerate(head)) and all(c in ("?", body[40 - len(tail) + j]) for j, c in enumerate(tail))
+
+
 def prefix_match(patterns, h160, label):
-    """the address text of a record in the form of the first pattern, in list order, that it starts with; None if there is none (a range's
-    end value whose checksum does not fit).  label: the record's (addr33, addr65, eth)"""
+    """the address text of a record in the form of the first pattern, in list order, that it starts with (a 0x pattern with ? or *: that
+    it matches); None if there is none (a range's end value whose checksum does not fit).  label: the record's (addr33, addr65, eth)"""
     for p in patterns:
         form = _prefix_form(p)
         if form == "hex" and label == "eth":
             a = address_eth(h160)
-            if a.startswith(p.lower()):
+            if _hex_pattern_matches(p, a):
                 return a
         elif form == "bech32" and label == "addr33":
             a = address_bech32(h160)
@@ -601,6 +685,16 @@ def prefix_match(patterns, h160, label):
             if a.startswith(p):
                 return a
     return None
+
+
+class MaskFilter:
+    """what KeySearch takes in place of a Filter for a search of masked Ethereum patterns: the mask table"""
+
+    def __init__(self, table):
+        self.table, self.words, self.hashes = table, None, None
+
+    def confirm(self, h160):
+        return True
 
 
 class PrefixFilter:
@@ -635,13 +729,19 @@ def prefix_search(patterns, range_s, range_e, a33=True, a65=False, eth=False, en
     patterns = list(patterns)
     if eth:
         a33 = a65 = False
-    table, _ = prefix_ranges(patterns, a33, a65, eth)
-    ks = KeySearch(PrefixFilter(table), device=device, a33=a33, a65=a65, endo=endo, eth=eth, verify=verify, device_cls=device_cls, prefix=True,
+    masked = any(mask_is_masked(p) for p in patterns)  # a list with a ? or * pattern becomes one mask table; any other is planned as ever
+    if masked:
+        flt, how = MaskFilter(mask_table(patterns, eth)[0]), {"mask": True}
+    else:
+        flt, how = PrefixFilter(prefix_ranges(patterns, a33, a65, eth)[0]), {"prefix": True}
+    ks = KeySearch(flt, device=device, a33=a33, a65=a65, endo=endo, eth=eth, verify=verify, device_cls=device_cls, **how,
                    **({"origin": bsgs_point(origin)} if origin is not None else {}), **kw)
     try:
         out, edge = [], 0
         for r in ks.cmd_add(range_s, range_e):
             r.address = prefix_match(patterns, r.h160, r.label)
+            if r.address is None and masked:  # the mask test is exact: no edges
+                raise EclError("[!] error: the record %s matches no pattern" % address_eth(r.h160))
             if r.address is None:
                 edge += 1
             else:

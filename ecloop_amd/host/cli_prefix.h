@@ -3,7 +3,8 @@
    Part of the one translation unit ecloop_hip_cli.c (included there, in this order). */
 /* -p <pattern | file of patterns>: a name that opens as a file is a list, one pattern per line (blank lines skipped); anything else is
    the pattern itself.  The planned table stands where the bloom words of -f stand (run->flt.words: ten 32-bit words per range), so the
-   bring-up hands it to ecl_hip_set_bloom of a context opened with ECL_PREFIX. */
+   bring-up hands it to ecl_hip_set_bloom of a context opened with ECL_PREFIX.  A list with a 0x pattern that has ? or * (a suffix, both
+   ends, holes) is planned by mask_plan.h instead: its mask table stands in the same place and the context is opened with ECL_MASK. */
 static void prefix_open(run_t *run, const char *arg) {
   char **pats = NULL;
   u32 n = 0;
@@ -26,6 +27,22 @@ static void prefix_open(run_t *run, const char *arg) {
   }
   static pfx_plan plan;
   char why[320];
+  if (msk_list_is_masked((const char *const *)pats, n)) {
+    static msk_plan mplan;
+    if (msk_plan_make(&mplan, (const char *const *)pats, n, run->eth, why, sizeof why) != PFX_OK) {
+      fprintf(stderr, "%s\n", why);
+      exit(1);
+    }
+    free(pats);
+    memset(&plan, 0, sizeof plan);
+    plan.pat = mplan.pat, plan.npat = mplan.npat; /* (the patterns alone: a run with -p has run->pfx set) */
+    run->pfx = &plan, run->msk = &mplan;
+    memset(&run->flt, 0, sizeof run->flt);
+    run->flt.nwords = 5ull * mplan.nentry;
+    run->flt.words = malloc(run->flt.nwords * 8);
+    memcpy(run->flt.words, mplan.entry, run->flt.nwords * 8); /* msk_entry is m[5], v[5]: the table's layout */
+    return;
+  }
   if (pfx_plan_make(&plan, (const char *const *)pats, n, run->a33, run->a65, run->eth, why, sizeof why) != PFX_OK) {
     fprintf(stderr, "%s\n", why);
     exit(1);
@@ -55,7 +72,12 @@ static void prefix_report(run_t *run, const ecl_found *hits, const sc *keys, u32
   report_t *r = &run->rep;
   for (u32 i = 0; i < n; ++i) {
     char addr[48], hh[41], kk[65], sp[16] = "", spf[16] = "";
-    if (pfx_match(run->pfx, hits[i].h160, hits[i].compressed, addr) < 0) {
+    if (run->msk) { /* the mask test is exact: a record that matches no pattern is an error, not an edge */
+      if (msk_match(run->msk, hits[i].h160, addr) < 0) {
+        fprintf(stderr, "[!] error: the record %s matches no pattern\n", addr);
+        exit(1);
+      }
+    } else if (pfx_match(run->pfx, hits[i].h160, hits[i].compressed, addr) < 0) {
       pthread_mutex_lock(&r->mu);
       r->edge++;
       pthread_mutex_unlock(&r->mu);

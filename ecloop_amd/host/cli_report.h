@@ -114,6 +114,7 @@ typedef struct run_t {
   sc range_s, range_e, stride_k;
   u32 ord_offs, ord_size;
   pfx_plan *pfx; /* -p: the plan of the patterns (cli_prefix.h), NULL otherwise */
+  msk_plan *msk; /* -p with a 0x pattern that has ? or *: the mask plan; pfx then holds the patterns alone, no ranges */
   bool split;    /* -p with -k: the walk starts from the requester's public key (cli_splitkey.h); the keys reported are partial keys */
   u64 origin[8]; /* ... its x and y, the last eight of the twelve limbs of every add_range call */
   char split_hex[67];

@@ -250,7 +250,9 @@ static void usage(const char *prog) { /* the reference's help text (main.c:750-7
       "  -p <pattern>    - add, rnd: search addresses that START with the pattern, or with any pattern of a file (one per line), in\n",
       "                    place of -f: 1... (base58 P2PKH; -a c, u or cu), bc1q... (bech32 P2WPKH; -a c) or 0x... (Ethereum; -a e, case is\n",
       "                    ignored: EIP-55 case is not matched).  Patterns that cover more than 2^-16 of all addresses are refused:\n",
-      "                    lengthen them.  A found line ends with the address\n",
+      "                    lengthen them.  A found line ends with the address.  A 0x pattern may hold ? (any one digit) and one * (any run\n",
+      "                    of digits; what follows it is matched at the END of the address): -p '0xdead*beef', '0x*c0ffee', '0xde?d*' -\n",
+      "                    in quotes, or the shell expands them; at most 16 such patterns in a list\n",
       "  -k <pubkey>     - add, rnd with -p: split-key search on another person's behalf.  The walk starts from their public key (66 hex digits\n",
       "                    02.. / 03.., or 130 digits 04..; one key), the keys printed are PARTIAL keys, worthless without the owner's private\n",
       "                    key, and a found line ends with split:<e>.  The owner runs combine\n",

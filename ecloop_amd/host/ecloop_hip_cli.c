@@ -52,6 +52,7 @@ typedef uint8_t u8;
 typedef struct { u64 w[4]; } sc; /* 256-bit scalar, little-endian limbs (the reference's fe) */
 
 #include "prefix_plan.h"
+#include "mask_plan.h"
 #include "splitkey.h"
 #include "cli_base.h"
 #include "cli_filter.h"
@@ -121,7 +122,7 @@ static double bring_up(run_t *run, int shown, int real) {
     if (!(keys.w[1] | keys.w[2] | keys.w[3]) && keys.w[0] < largest_call) largest_call = keys.w[0];
   }
   const u32 flags = (run->a33 ? ECL_ADDR33 : 0) | (run->a65 ? ECL_ADDR65 : 0) | (run->p2sh ? ECL_P2SH : 0) | (run->eth ? ECL_ETH : 0) |
-                    (run->tr ? ECL_TR : 0) | (run->pub ? ECL_PUB : 0) | (run->endo ? ECL_ENDO : 0) | (run->pfx ? ECL_PREFIX : 0) |
+                    (run->tr ? ECL_TR : 0) | (run->pub ? ECL_PUB : 0) | (run->endo ? ECL_ENDO : 0) | (run->msk ? ECL_MASK : run->pfx ? ECL_PREFIX : 0) |
                     (run->split ? ECL_ORIGIN : 0);
   pthread_t th[MAX_GPUS];
   bringup_t job[MAX_GPUS];
@@ -270,7 +271,8 @@ int main(int argc, const char **argv) {
 
   printf("gpus: %d ~ addr33: %d ~ addr65: %d ~ endo: %d%s | filter: ", shown, run.a33, run.a65, run.endo,
          run.p2sh ? " ~ p2sh: 1" : run.eth ? " ~ eth: 1" : run.tr ? " ~ p2tr: 1" : run.pub ? " ~ pub: 1" : "");
-  if (run.pfx) printf("prefix (%u pattern%s, %u range%s)\n", run.pfx->npat, run.pfx->npat == 1 ? "" : "s", run.pfx->nrange, run.pfx->nrange == 1 ? "" : "s");
+  if (run.msk) printf("prefix (%u pattern%s, %u mask entr%s)\n", run.msk->npat, run.msk->npat == 1 ? "" : "s", run.msk->nentry, run.msk->nentry == 1 ? "y" : "ies");
+  else if (run.pfx) printf("prefix (%u pattern%s, %u range%s)\n", run.pfx->npat, run.pfx->npat == 1 ? "" : "s", run.pfx->nrange, run.pfx->nrange == 1 ? "" : "s");
   else if (run.flt.list) printf("list (%'llu)\n", (unsigned long long)run.flt.nlist);
   else printf("bloom\n");
   if (run.split) printf("split key: the keys printed are PARTIAL keys for %s (its owner adds their own: combine -part <key> -split <e>)\n", run.split_hex);

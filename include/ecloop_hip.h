@@ -138,7 +138,21 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
    no look-ahead; ecl_hip_mul_batch(_raw) ECL_E_ARG), and the call reports the keys j whose point O + (start + j 2^ord_offs) G has a hash
    inside a range - records, key_offset (from the call's scalar), endo (the six images of that point) and compressed as on the plain
    prefix context.  The scalars say nothing about the points' keys: whoever knows the origin's key k_O adds it (host/splitkey.h).  On such
-   a context each entry of `k` of ecl_hip_verify / ecl_hip_verify_eth is TWELVE limbs, too - see there. */
+   a context each entry of `k` of ecl_hip_verify / ecl_hip_verify_eth is TWELVE limbs, too - see there.
+   ECL_MASK (no reference counterpart): the mask filter, for Ethereum addresses with fixed digits anywhere - a suffix, both ends, holes
+   (`-p 0xdead*beef`; ecloop_amd/host/mask_plan.h turns patterns into entries).  In place of a bloom filter the context holds a table of n
+   entries, each a mask m and a value v over the 160-bit address, words in the record's order (h160[0] most significant), and reports a
+   key iff some entry has (address ^ v) & m == 0: exact, and one record per key and image however many entries match.  Valid only as
+   ECL_ETH | ECL_MASK, with or without ECL_ENDO and / or ECL_ORIGIN; beside ECL_PREFIX, ECL_ADDR33, ECL_ADDR65, ECL_P2SH, ECL_TR, ECL_PUB,
+   ECL_INSERT or ECL_HERD, or without ECL_ETH, it is ECL_E_ARG.  On such a context
+     ecl_hip_set_bloom(h, words, nwords) takes the TABLE: nwords = 5 n, each entry ten uint32 - m[5], v[5] - with 1 <= n <= 16, no bit of
+       v outside m and no two identical entries; anything else is ECL_E_ARG and leaves the context without a table.  An all-zero mask is
+       legal and matches every address: how much of the space a table may cover is the caller's business (the planner bounds it);
+     ecl_hip_add_range, ecl_hip_set_list, ecl_hip_bloom_insert(_count), ecl_hip_get_bloom and ecl_hip_mul_batch(_raw) behave as on a prefix
+       context (ECL_E_NOBLOOM before a table is set; the others ECL_E_ARG; no look-ahead);
+     ecl_hip_diag_bloom runs the device's mask test on the given values.
+   ECL_MASK | ECL_ORIGIN is the split-key search of such patterns and behaves as ECL_PREFIX | ECL_ORIGIN beside ECL_ETH does: twelve limbs
+   per `start` and per entry of ecl_hip_verify_eth. */
 #define ECL_ADDR33 1u
 #define ECL_ADDR65 2u
 #define ECL_ENDO 4u
@@ -150,6 +164,7 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
 #define ECL_INSERT 1024u
 #define ECL_HERD 2048u
 #define ECL_PREFIX 4096u
+#define ECL_MASK 0x2000u /* 8192 */
 
 /* return codes */
 #define ECL_OK 0
@@ -254,7 +269,7 @@ int ecl_hip_set_list(ecl_hip *h, const uint32_t (*h160)[5], uint64_t n);
    table also give the base centre of a non-contiguous walk, and a hit shares its high digits with that centre, so
    the context self-test checks the window sum against the double-and-add kernel on full-width scalars.  ok[i] = 0
    for k = 0 (mod n).  The caller compares with the hit's h160 and treats a mismatch as fatal, like the reference.
-   On a context opened with ECL_PREFIX | ECL_ORIGIN each entry of `k` is TWELVE limbs, like the `start` of its ecl_hip_add_range: the
+   On a context opened with ECL_PREFIX | ECL_ORIGIN (or ECL_MASK | ECL_ORIGIN) each entry of `k` is TWELVE limbs, like the `start` of its ecl_hip_add_range: the
    scalar, then x and y of an origin O (a point of the curve, checked on the host: ECL_E_ARG otherwise; all eight limbs zero: the point at
    infinity), one origin per entry, and the hashes are those of O + k G - the window-table sum, one more complete mixed addition, an
    inversion of the kernel's own (k_verify_origin; ecl_hip_verify_eth: k_verify_origin_eth): not the walk.  ok[i] = 0 where O + k G is

@@ -5,6 +5,11 @@
       random hashes in it: the unchanged addr33 kernel of this build, its stage 1 one cached probe like the prefix kernel's bitmap load;
   o   `p` from an origin (ECL_ADDR33 | ECL_PREFIX | ECL_ORIGIN, the split-key search of DESIGN.md §7 (f12)): the same kernel, the same table and
       the same scalars, walked from the point Q = 0xdc2a04 G - the expected ratio o / p is 1 within the spread of the runs;
+and for -a e, on the same range:
+  e    ECL_ETH | ECL_PREFIX with the table of one long pattern (0xdeadbeefc0ffee): the yardstick of the two mask rows;
+  m1   ECL_ETH | ECL_MASK with a table of one entry (0xdeadbeef*c0ffee);
+  m16  ECL_ETH | ECL_MASK with a table of sixteen entries (0x<seven digits>*<three digits>, sixteen of them) - the most a table holds;
+what is to be read off is m1 / e and m16 / e beside the run-to-run spread of e;
 warm, `runs` alternating rounds, medians and their ratio reported.  Look-ahead off, 2^20 lanes per context (the half group stays automatic).
 
 usage: bench_prefix.py rates [runs = 3] [log2 keys = 32] [pattern = 1BgGZ9tcN4]"""
@@ -31,6 +36,28 @@ def timed_add(d, start, n, origin=None):
     return (d.timing()[0] - ms0) * 1e-3, wall, total
 
 
+def measure(ctx, origin, runs, n):
+    """legs of one group: warm each, then `runs` alternating rounds -> leg -> [(event s, wall s, hits)]"""
+    for leg, d in ctx.items():
+        d.set_geometry(0, 1 << 20)
+        timed_add(d, START - (1 << 28), 1 << 28, origin.get(leg))  # warm: tables, buffers, code objects
+    rows = {leg: [] for leg in ctx}
+    for r in range(runs):
+        for leg in ctx:
+            rows[leg].append(timed_add(ctx[leg], START + r * n, n, origin.get(leg)))
+    return rows
+
+
+def summary(rows, n):
+    return {"event_M_per_s": [round(n / e / 1e6, 1) for e, _, _ in rows], "wall_M_per_s": [round(n / w / 1e6, 1) for _, w, _ in rows],
+            "event_median_M_per_s": round(statistics.median(n / e / 1e6 for e, _, _ in rows), 1),
+            "wall_median_M_per_s": round(statistics.median(n / w / 1e6 for _, w, _ in rows), 1), "hits": [h for _, _, h in rows]}
+
+
+def spread(leg):
+    return round(max(leg["event_M_per_s"]) / min(leg["event_M_per_s"]), 3)
+
+
 def rates(runs, log2, pattern):
     n = 1 << log2
     table, _ = engine.prefix_ranges([pattern], True, False, False)
@@ -44,27 +71,36 @@ def rates(runs, log2, pattern):
     o = capi.Device(0, a33=True, prefix=True, origin=True)
     o.set_prefixes(table)
     xs, ys, ok = c.diag_mulg([0xDC2A04])
-    origin = {"p": None, "c": None, "o": (xs[0], ys[0])}
     ctx = {"p": p, "o": o, "c": c}
-    for leg, d in ctx.items():
-        d.set_geometry(0, 1 << 20)
-        timed_add(d, START - (1 << 28), 1 << 28, origin[leg])  # warm: tables, buffers, code objects
-    rows = {"p": [], "o": [], "c": []}
-    for r in range(runs):
-        for leg in ("p", "o", "c"):
-            rows[leg].append(timed_add(ctx[leg], START + r * n, n, origin[leg]))
+    rows = measure(ctx, {"o": (xs[0], ys[0])}, runs, n)
     res = {"runs": runs, "keys": n, "pattern": pattern, "ranges": len(table), "blf_bytes": len(words) * 8,
            "geometry": {k: ctx[k].plan_geometry(n) for k in ctx}}
-    for leg in ("p", "o", "c"):
-        res[leg] = {"event_M_per_s": [round(n / e / 1e6, 1) for e, _, _ in rows[leg]], "wall_M_per_s": [round(n / w / 1e6, 1) for _, w, _ in rows[leg]],
-                    "event_median_M_per_s": round(statistics.median(n / e / 1e6 for e, _, _ in rows[leg]), 1),
-                    "wall_median_M_per_s": round(statistics.median(n / w / 1e6 for _, w, _ in rows[leg]), 1), "hits": [h for _, _, h in rows[leg]]}
+    for leg in ctx:
+        res[leg] = summary(rows[leg], n)
     res["p_over_c_event"] = round(res["p"]["event_median_M_per_s"] / res["c"]["event_median_M_per_s"], 3)
     res["o_over_p_event"] = round(res["o"]["event_median_M_per_s"] / res["p"]["event_median_M_per_s"], 3)
-    res["p_spread_event"] = round(max(res["p"]["event_M_per_s"]) / min(res["p"]["event_M_per_s"]), 3)
-    res["o_spread_event"] = round(max(res["o"]["event_M_per_s"]) / min(res["o"]["event_M_per_s"]), 3)
+    res["p_spread_event"], res["o_spread_event"] = spread(res["p"]), spread(res["o"])
     res["coverage_p"] = p.coverage()
     res["coverage_o"] = o.coverage()
+    for d in ctx.values():
+        d.close()
+    # the -a e rows, a group of their own (the first group's contexts and their walk buffers are gone)
+    e = capi.Device(0, a33=False, eth=True, prefix=True)
+    e.set_prefixes(engine.prefix_ranges(["0xdeadbeefc0ffee"], False, False, True)[0])
+    m1 = capi.Device(0, a33=False, eth=True, mask=True)
+    m1.set_masks(engine.mask_table(["0xdeadbeef*c0ffee"])[0])
+    m16 = capi.Device(0, a33=False, eth=True, mask=True)
+    m16.set_masks(engine.mask_table(["0x%07x*%03x" % (0xDEAD000 + 7 * i, 0xBE0 + i) for i in range(16)])[0])
+    ctx = {"e": e, "m1": m1, "m16": m16}
+    rows = measure(ctx, {}, runs, n)
+    res["geometry"].update({k: ctx[k].plan_geometry(n) for k in ctx})
+    for leg in ctx:
+        res[leg] = summary(rows[leg], n)
+    for leg in ("m1", "m16"):
+        res[leg + "_over_e_event"] = round(res[leg]["event_median_M_per_s"] / res["e"]["event_median_M_per_s"], 3)
+        res["coverage_" + leg] = ctx[leg].coverage()
+    res["e_spread_event"] = spread(res["e"])
+    res["mask_entries"] = {"m1": 1, "m16": 16}
     for d in ctx.values():
         d.close()
     print(json.dumps(res))

@@ -271,6 +271,29 @@ def analyse_prefix(path=ASM):
     return out
 
 
+# the mask kernels (-p 0xdead*beef -a e): the walk and Keccak of k_add_pfx_eth with the mask filter (csrc/mask.h); beside each the prefix kernel
+# it mirrors, from the same assembly
+MASK_KERNELS = {"-p mask -a e": "_Z13k_add_msk_ethILb0EEv8add_args", "-p mask -a e -endo": "_Z13k_add_msk_ethILb1EEv8add_args"}
+MASK_MIRRORS = {"-p mask -a e": "_Z13k_add_pfx_ethILb0EEv8add_args", "-p mask -a e -endo": "_Z13k_add_pfx_ethILb1EEv8add_args"}
+
+
+def analyse_mask(path=ASM):
+    """the two mask kernels and the prefix kernels they mirror: metadata (registers, spills, scratch, LDS), fingerprint, loops"""
+    meta = kernel_meta(path)
+    out = {}
+    for label, k in MASK_KERNELS.items():
+        r = {}
+        for tag, name in (("kernel", k), ("mirror", MASK_MIRRORS[label])):
+            a = analyse(path, name)
+            r[tag] = {"name": name, "registers": meta.get(name), "fingerprint": a["fingerprint"], "total": a["total"],
+                      "scratch_in_loops": {"which": a["which_loop"]["scratch"], "table": a["table_loop"]["scratch"], "prefix": a["prefix_loop"]["scratch"],
+                                           "launch": a["launch_loop"]["scratch"]},
+                      "loops": [{x: l[x] for x in ("header", "depth", "parent", "valu", "salu", "smem", "vmem", "lds", "scratch")} for l in a["loops"]],
+                      "per_key_static": {x: round(v, 1) for x, v in a["per_key_static"].items()}}
+        out[label] = r
+    return out
+
+
 # the Taproot kernels (-a t, searched alone): stage A (the emit kernels from the walk and from `mul`'s window sums) and stage B (k_tr_check;
 # <true>: ecl_hip_diag_tr's instantiation, which writes whole output keys instead of probing)
 TR_KERNELS = {"-a t emit": "_Z8k_add_tr8add_args", "mul -a t emit": "_Z15k_mul_points_trPKjjj4wtab8add_argsPjjj",
@@ -480,6 +503,10 @@ def main():
     if "--prefix" in sys.argv:
         rest = [a for a in sys.argv[1:] if not a.startswith("--")]
         print(json.dumps(analyse_prefix(rest[0] if rest else ASM), indent=1))
+        return
+    if "--mask" in sys.argv:
+        rest = [a for a in sys.argv[1:] if not a.startswith("--")]
+        print(json.dumps(analyse_mask(rest[0] if rest else ASM), indent=1))
         return
     if "--tr" in sys.argv:
         rest = [a for a in sys.argv[1:] if not a.startswith("--")]
