@@ -14,6 +14,9 @@ ORIGIN, INSERT = 512, 1024  # the two walks of `bsgs`, each valid only beside PU
 HERD = 2048  # the herd of `kangaroo`, valid only beside PUB alone; ord_offs is then the number of distinguished-point bits
 PREFIX = 4096  # the prefix filter in place of the bloom: beside ADDR33 / ADDR65 or ETH, with or without ENDO (include/ecloop_hip.h)
 MASK = 8192  # the mask filter in place of the bloom: beside ETH alone, with or without ENDO / ORIGIN (include/ecloop_hip.h)
+# the key derivation function of mul_batch_raw, a two-bit field (include/ecloop_hip.h): none = SHA-256; valid beside every context that has a `mul`
+KDF_KECCAK, KDF_SHA3, KDF_CAMP2 = 0x4000, 0x8000, 0xC000
+KDF_FLAGS = {None: 0, "sha256": 0, "keccak": KDF_KECCAK, "sha3": KDF_SHA3, "camp2": KDF_CAMP2}
 E_ARG = -1
 E_NOBLOOM = -5
 E_RANGE = -6
@@ -138,7 +141,12 @@ class Device:
     """One GPU context (ecl_hip handle)."""
 
     def __init__(self, device=0, a33=True, a65=False, endo=False, ord_offs=0, p2sh=False, eth=False, tr=False, pub=False, origin=False,
-                 insert=False, herd=False, prefix=False, mask=False):
+                 insert=False, herd=False, prefix=False, mask=False, kdf=None):
+        if kdf not in KDF_FLAGS:
+            raise ValueError("kdf is None (SHA-256), 'keccak', 'sha3' or 'camp2'")
+        if KDF_FLAGS[kdf] and (origin or insert or herd or prefix or mask):
+            raise ValueError("a kdf goes with the contexts that have a `mul`: not with origin, insert, herd, prefix or mask")
+        self.kdf = kdf if KDF_FLAGS[kdf] else None
         if prefix and (p2sh or tr or pub or insert or herd or not (a33 or a65 or eth)):
             raise ValueError("the prefix filter goes with a33 / a65 or with eth: Device(prefix=True), Device(a33=False, eth=True, prefix=True)")
         if mask and (prefix or a33 or a65 or p2sh or tr or pub or insert or herd or not eth):
@@ -161,7 +169,7 @@ class Device:
         if tr and (a33 or a65 or p2sh or eth or endo):
             raise ValueError("Taproot is searched alone and without the endomorphism: Device(a33=False, tr=True)")
         flags = (ADDR33 if a33 else 0) | (ADDR65 if a65 else 0) | (P2SH if p2sh else 0) | (ETH if eth else 0) | (TR if tr else 0) | (PUB if pub else 0) | (ENDO if endo else 0) | \
-                (ORIGIN if origin else 0) | (INSERT if insert else 0) | (HERD if herd else 0) | (PREFIX if prefix else 0) | (MASK if mask else 0)
+                (ORIGIN if origin else 0) | (INSERT if insert else 0) | (HERD if herd else 0) | (PREFIX if prefix else 0) | (MASK if mask else 0) | KDF_FLAGS[kdf]
         rc = self.lib.ecl_hip_open(C.byref(self.h), device, flags, ord_offs)
         if rc != 0:
             msg = self.lib.ecl_hip_last_error(self.h).decode() if self.h else ""
@@ -294,7 +302,8 @@ class Device:
         return out[: min(n.value, cap)], n.value
 
     def mul_batch_raw(self, lines, cap=4096):
-        """`mul -raw`: lines = list of bytes objects; their SHA-256 digests are the scalars (hashed on the device)"""
+        """`mul -raw`: lines = list of bytes objects; their digests are the scalars (hashed on the device) - SHA-256, or on a
+        Device(kdf="keccak" | "sha3" | "camp2") Keccak-256, SHA3-256 or Keccak-256 applied 2031 times (engine.kdf_digest is the definition)"""
         text = b"".join(lines)
         table = np.zeros(len(lines), dtype=np.uint64)
         at = 0

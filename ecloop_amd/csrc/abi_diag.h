@@ -195,8 +195,58 @@ extern "C" int ecl_hip_diag_drop_round(ecl_hip* h) {
 
 // ------------------------------------------------------------------------------------------------ self-test
 
+// a context with ECL_KDF_* bits: its hashing kernel on known answers (computed elsewhere: FIPS 202's SHA3-256 vectors, Keccak-256 and the
+// 2031-fold form from an independent implementation), through the launch ecl_hip_mul_batch_raw makes.  The three lines share one text:
+// "" and "abc" at offset 0, "password" at offset 3 (a start that is not word-aligned).
+static int kdf_selftest(ecl_hip* h) {
+  static const char TEXT[] = "abcpassword";
+  static const u64 LINES[3] = {0ull, 3ull << 32, 3ull | 8ull << 32};
+  static const char* const KAT[3][3] = {
+      {"c5d2460186f7233c927e7db2dcc703c0e500b653ca82273b7bfad8045d85a470", "4e03657aea45a94fc7d47ba826c8d667c0d1e6e33a64a036ec44f58fa12d6c45", nullptr},
+      {"a7ffc6f8bf1ed76651c14756a061d662f580ff4de43b49fa82d80a4b80f8434a", "3a985da74fe225b2045c172d6bd390bd855f086e3e9d525b46bfe24511431532", nullptr},
+      {"26d412aa8b9fea49149a7dbf8b19672d8813f741842ac1847571d335908cbe65", "7a44789ed3cd85861c0bbf9693c7e1de1862dd4396c390147ecf1275099c6e6f",
+       "5e225b381fcf02bd5577885f19b9472234c117dc44df6b59aca6690471dea0a0"}};
+  const char* const* want = KAT[h->kdf == ECL_KDF_KECCAK ? 0 : h->kdf == ECL_KDF_SHA3 ? 1 : 2];
+  const u32 text_bytes = sizeof TEXT - 1;
+  u32 words[5] = {};  // three words of text and the two spare ones
+  memcpy(words, TEXT, text_bytes);
+  devbuf<u32> dtext, dout;
+  devbuf<u64> dlines;
+  HIPCHK(h, hipSetDevice(h->dev));
+  HIPCHK(h, dtext.grow(5));
+  HIPCHK(h, dlines.grow(3));
+  HIPCHK(h, dout.grow(3 * 8 + 2));  // three scalars, then the two flags of the kernel
+  HIPCHK(h, hipMemcpy(dtext.p, words, sizeof words, hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemcpy(dlines.p, LINES, sizeof LINES, hipMemcpyHostToDevice));
+  HIPCHK(h, hipMemsetAsync(dout.p, 0, (3 * 8 + 2) * sizeof(u32), h->stream));
+  raw_scalars_launch(h->kdf, h->stream, dtext.p, text_bytes, text_bytes, dlines.p, 3, dout.p, dout.p + 24);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  u32 got[3 * 8 + 2];
+  HIPCHK(h, hipMemcpy(got, dout.p, sizeof got, hipMemcpyDeviceToHost));
+  bool good = got[24] == 0 && got[25] == 0;
+  for (int i = 0; i < 3 && good; ++i) {
+    if (!want[i]) continue;
+    char hex[65];
+    for (int w = 0; w < 8; ++w) snprintf(hex + 8 * w, 9, "%08x", got[i * 8 + 7 - w]);  // the scalar's words, most significant first
+    good = memcmp(hex, want[i], 64) == 0;
+  }
+  if (!good) {
+    h->err = "known-answer test of the key derivation function (ECL_KDF_*) failed";
+    return ECL_E_SELFTEST;
+  }
+  return ECL_OK;
+}
+
 extern "C" int ecl_hip_selftest(ecl_hip* h) {
   if (!h) return ECL_E_ARG;
+  if (h->kdf) {  // the context's own self-test as without the bits, then the hash of its ecl_hip_mul_batch_raw
+    const u32 kdf = h->kdf;
+    h->kdf = 0;
+    const int rc = ecl_hip_selftest(h);
+    h->kdf = kdf;
+    return rc != ECL_OK ? rc : kdf_selftest(h);
+  }
   if (h->flags & ECL_HERD) {  // a herd context tests the device code a public-key context tests (the known answers, the x-only walk, the
     // window sum); the herd kernel has no second path on the device to be checked against: tests/test_gpu_kangaroo.py checks it
     const u32 offs = h->offs;

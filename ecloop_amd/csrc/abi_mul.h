@@ -370,7 +370,19 @@ extern "C" int ecl_hip_mul_batch(ecl_hip* h, const uint64_t (*scalars)[4], uint3
   return count_call(h, n, f.finish());  // (the counts of all pieces, summed on the device)
 }
 
-// `mul -raw`: lines of text in, SHA-256 on the device, then the `mul` body on the digests (n <= 2^26 lines a call): the pieces of
+// the hash of `mul -raw` over m lines of the table: SHA-256, or what the context was opened with (ECL_KDF_*: kdf.h)
+static void raw_scalars_launch(u32 kdf, hipStream_t st, const u32* d_text, u32 text_bytes, u32 have, const u64* d_lines, u32 m, u32* d_out, u32* d_flags) {
+  if (kdf == ECL_KDF_CAMP2)
+    hipLaunchKernelGGL(k_raw_scalars_camp2, dim3((m + 63) / 64), dim3(64), 0, st, d_text, text_bytes, have, d_lines, m, d_out, d_flags);
+  else if (kdf == ECL_KDF_KECCAK)
+    hipLaunchKernelGGL(k_raw_scalars_keccak<KDF_PAD_KECCAK>, dim3((m + 255) / 256), dim3(256), 0, st, d_text, text_bytes, have, d_lines, m, d_out, d_flags);
+  else if (kdf == ECL_KDF_SHA3)
+    hipLaunchKernelGGL(k_raw_scalars_keccak<KDF_PAD_SHA3>, dim3((m + 255) / 256), dim3(256), 0, st, d_text, text_bytes, have, d_lines, m, d_out, d_flags);
+  else
+    hipLaunchKernelGGL(k_raw_scalars, dim3((m + 255) / 256), dim3(256), 0, st, d_text, text_bytes, have, d_lines, m, d_out, d_flags);
+}
+
+// `mul -raw`: lines of text in, SHA-256 (or the context's ECL_KDF_* hash) on the device, then the `mul` body on the digests (n <= 2^26 lines a call): the pieces of
 // ecl_hip_mul_batch, with 8 bytes of table + the line instead of 32 bytes of scalar on the copy stream, and every piece's lines hashed
 // into its staging buffer ahead of its window sums (details at the two lambdas below).  Until round 6 a call was ONE piece of at most
 // 2^22 lines on one stream and the host program made ~2 M-line calls: 0.79-0.87 G lines/s over 2^30 pass phrases; as pieces with the
@@ -453,7 +465,7 @@ extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t t
           // The hashing has a stream of its own, of higher priority than the compute streams, and runs up to MUL_NBUF - 1 pieces ahead like
           // the copies: on the piece's compute stream it would sit between two k_mul_check launches that each fill the chip.
           HIPCHK(h, hipStreamWaitEvent(h->prep_stream, h->ev_copied[b], 0));
-          hipLaunchKernelGGL(k_raw_scalars, dim3((m + 255) / 256), dim3(256), 0, h->prep_stream, d_text, text_bytes, have, d_lines + at, m, h->d_kbuf[b].p, d_flags);
+          raw_scalars_launch(h->kdf, h->prep_stream, d_text, text_bytes, have, d_lines + at, m, h->d_kbuf[b].p, d_flags);
           HIPCHK(h, hipEventRecord(h->ev_hashed[b], h->prep_stream));
           *ready = h->ev_hashed[b];
           return ECL_OK;

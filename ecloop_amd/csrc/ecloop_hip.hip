@@ -24,6 +24,7 @@
 #include "abi_lookahead_ctx.h"
 #include "setup_kernels.h"
 #include "mul_kernels.h"
+#include "kdf.h"
 #include "tr_kernels.h"
 #include "aux_kernels.h"
 #include "herd_kernel.h"
@@ -53,6 +54,7 @@ template <typename T> using pinbuf = growbuf<T, pin_mem>;
 struct ecl_hip {
   int dev = 0;
   u32 flags = 0, offs = 0;
+  u32 kdf = 0;        // ECL_KDF_* of ecl_hip_open (not part of `flags`): the hash of ecl_hip_mul_batch_raw, 0 = SHA-256
   u32 B = 1024;       // table points per group
   u32 Tmax = 0;       // lanes walked concurrently (0 = derive from occupancy)
   hipStream_t stream = nullptr;
@@ -162,6 +164,11 @@ const char* ecl_hip_last_error(const ecl_hip* h) { return h ? h->err.c_str() : "
 
 int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   const u32 types = ECL_ADDR33 | ECL_ADDR65 | ECL_P2SH;
+  // the hash of `mul -raw` (ECL_KDF_*): beside every context that has a `mul`; it is kept apart from the other flags, which are then
+  // checked, and later read, as on a context without it
+  const u32 kdf = flags & ECL_KDF_CAMP2;
+  if (kdf && (flags & (ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX | ECL_MASK))) return ECL_E_ARG;
+  flags &= ~ECL_KDF_CAMP2;
   if (!out || ord_offs > 255 || !(flags & (types | ECL_ETH | ECL_TR | ECL_PUB)) ||
       (flags & ~(types | ECL_ETH | ECL_TR | ECL_PUB | ECL_ENDO | ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX | ECL_MASK)))
     return ECL_E_ARG;
@@ -182,7 +189,7 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   int n = ecl_hip_device_count();
   if (device < 0 || device >= n) return ECL_E_NODEV;
   ecl_hip* h = new ecl_hip();
-  h->dev = device, h->flags = flags, h->offs = ord_offs, h->la_max = la_default_max();
+  h->dev = device, h->flags = flags, h->kdf = kdf, h->offs = ord_offs, h->la_max = la_default_max();
   *out = h;
   HIPCHK(h, hipSetDevice(device));
   HIPCHK(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
@@ -200,7 +207,7 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   static std::mutex mu;
   static std::set<u32> passed;
   const char* skip = getenv("ECL_HIP_SKIP_SELFTEST");
-  const u32 key = (u32)device * 16384u + flags;  // flags < 16384
+  const u32 key = (u32)device * 65536u + (flags | kdf);  // flags | kdf < 65536
   {
     std::lock_guard<std::mutex> lk(mu);
     if ((skip && skip[0] == '1') || passed.count(key)) return ECL_OK;

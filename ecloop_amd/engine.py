@@ -5,6 +5,7 @@ sorted-list confirm, calc_priv, the pk_verify_hash self-check, the found sink, r
 All curve / hash work goes to the device (ecloop_amd.capi.Device); nothing here can compute a hash160 on the CPU.
 Names follow the reference: load_filter, cmd_add, cmd_mul, calc_priv, pk_verify_hash, ctx_write_found.
 """
+import hashlib
 import math
 import os
 import struct
@@ -215,6 +216,69 @@ def max_over_ranks(seconds, dist=None):
 # ----------------------------------------------------------------------------------------------- command drivers
 
 
+# ----------------------------------------------------------------------------------------------- key derivation (mul -raw -kdf)
+# The definition of the four functions, in plain Python (FIPS 202: the sponge with rate 136 and capacity 512 over Keccak-f[1600]): the key of
+# a line is its digest read as a big-endian number.  sha256: the Bitcoin brain-wallet convention (the reference's -raw); keccak: Keccak-256,
+# first pad byte 0x01 (old ethaddress, early ethercamp); sha3: SHA3-256, first pad byte 0x06; camp2: Keccak-256 applied 2031 times, each
+# time to the 32 bytes of the digest before (the later ethercamp wallet).
+KDF_NAMES = ("sha256", "keccak", "sha3", "camp2")
+KDF_CAMP2_HASHES = 2031
+_M64 = (1 << 64) - 1
+_KECCAK_ROT = ((0, 36, 3, 41, 18), (1, 44, 10, 45, 2), (62, 6, 43, 15, 61), (28, 55, 25, 21, 56), (27, 20, 39, 8, 14))  # [x][y], FIPS 202 table 2
+_KECCAK_RC = (0x0000000000000001, 0x0000000000008082, 0x800000000000808A, 0x8000000080008000, 0x000000000000808B, 0x0000000080000001,
+              0x8000000080008081, 0x8000000000008009, 0x000000000000008A, 0x0000000000000088, 0x0000000080008009, 0x000000008000000A,
+              0x000000008000808B, 0x800000000000008B, 0x8000000000008089, 0x8000000000008003, 0x8000000000008002, 0x8000000000000080,
+              0x000000000000800A, 0x800000008000000A, 0x8000000080008081, 0x8000000000008080, 0x0000000080000001, 0x8000000080008008)
+
+
+def _keccak_f(a):
+    """a[x][y], permuted in place"""
+    rol = lambda v, n: ((v << n) | (v >> (64 - n))) & _M64 if n else v
+    for rc in _KECCAK_RC:
+        c = [a[x][0] ^ a[x][1] ^ a[x][2] ^ a[x][3] ^ a[x][4] for x in range(5)]
+        for x in range(5):
+            d = c[(x - 1) % 5] ^ rol(c[(x + 1) % 5], 1)
+            for y in range(5):
+                a[x][y] ^= d
+        b = [[0] * 5 for _ in range(5)]
+        for x in range(5):
+            for y in range(5):
+                b[y][(2 * x + 3 * y) % 5] = rol(a[x][y], _KECCAK_ROT[x][y])
+        for x in range(5):
+            for y in range(5):
+                a[x][y] = b[x][y] ^ (~b[(x + 1) % 5][y] & b[(x + 2) % 5][y])
+        a[0][0] ^= rc
+
+
+def _sponge256(msg, pad):
+    a = [[0] * 5 for _ in range(5)]
+    tail = bytearray(msg[len(msg) - len(msg) % 136:]) + bytes(136 - len(msg) % 136)
+    tail[len(msg) % 136] ^= pad
+    tail[135] ^= 0x80
+    data = bytes(msg[: len(msg) - len(msg) % 136]) + bytes(tail)
+    for at in range(0, len(data), 136):
+        for i in range(17):
+            a[i % 5][i // 5] ^= int.from_bytes(data[at + 8 * i: at + 8 * i + 8], "little")
+        _keccak_f(a)
+    return b"".join(a[i][0].to_bytes(8, "little") for i in range(4))
+
+
+def kdf_digest(name, line):
+    """the 32-byte digest that `mul -raw -kdf name` takes as the key of `line` (bytes)"""
+    if name == "sha256":
+        return hashlib.sha256(line).digest()
+    if name == "keccak":
+        return _sponge256(line, 0x01)
+    if name == "sha3":
+        return _sponge256(line, 0x06)
+    if name == "camp2":
+        d = _sponge256(line, 0x01)
+        for _ in range(KDF_CAMP2_HASHES - 1):
+            d = _sponge256(d, 0x01)
+        return d
+    raise ValueError("kdf is one of sha256, keccak, sha3, camp2")
+
+
 class FoundRecord:
     __slots__ = ("label", "h160", "pk", "prefix", "address", "split")
 
@@ -239,7 +303,7 @@ class KeySearch:
     """ctx_t + cmd_add / cmd_mul for one GPU."""
 
     def __init__(self, flt, device=0, a33=True, a65=False, endo=False, ord_offs=0, verify=True, launch_keys=1 << 32,
-                 half_group=0, max_lanes=0, device_cls=None, p2sh=False, eth=False, tr=False, pub=False, prefix=False, origin=None, mask=False):
+                 half_group=0, max_lanes=0, device_cls=None, p2sh=False, eth=False, tr=False, pub=False, prefix=False, origin=None, mask=False, kdf=None):
         if pub:
             a33 = False  # public keys are searched alone (with or without the endomorphism)
         elif tr:
@@ -266,6 +330,11 @@ class KeySearch:
             kw["prefix"] = True
         if mask:  # flt: a MaskFilter - the mask table stands where the bloom words stand (prefix_search with a ? or * pattern)
             kw["mask"] = True
+        if kdf not in (None,) + KDF_NAMES:
+            raise ValueError("kdf is None, 'sha256', 'keccak', 'sha3' or 'camp2'")
+        self.kdf = None if kdf == "sha256" else kdf  # the hash of cmd_mul_raw (kdf_digest); None: SHA-256
+        if self.kdf:
+            kw["kdf"] = self.kdf
         self.origin = None  # split-key search (prefix_search(origin=)): the walk is O + k G, the records' keys are partial keys
         if origin is not None:
             if not (prefix or mask):
@@ -420,6 +489,35 @@ class KeySearch:
                 self._verify(new)  # (a p2tr / pub record gets its whole key from the verification)
             self.found.extend(new)
             self.k_checked += len(ks)
+        return self.found
+
+    def cmd_mul_raw(self, lines, cap=4096):
+        """`mul -raw [-kdf ...]` for lines of text (bytes objects): the device hashes them (Device.mul_batch_raw, with the hash the context
+        was opened with); the key of a found line is its digest (kdf_digest, recomputed here), and every hit is re-derived from that key
+        through the device - a device hash that disagrees with kdf_digest raises the hash mismatch error instead of reporting a wrong key"""
+        chunk = 1 << 16
+        for at in range(0, len(lines), chunk):
+            part = lines[at : at + chunk]
+            c = max(cap, 2 * len(part))
+            while True:
+                raw, total = self.dev.mul_batch_raw(part, cap=c)
+                if total <= c:
+                    break
+                rest = self.dev.fetch_found(c, total - c)  # (as in cmd_mul)
+                if len(rest) == total - c:
+                    raw = np.concatenate([raw, rest])
+                    break
+                c = total
+            new = []
+            for r in raw:
+                if self.flt.confirm(r["h160"]):
+                    pk = int.from_bytes(kdf_digest(self.kdf or "sha256", part[int(r["key_offset"])]), "big")
+                    new.append(FoundRecord(label_of(r["compressed"]), [int(v) for v in r["h160"]], pk))
+                    self.k_found += 1
+            if self.verify:
+                self._verify(new)
+            self.found.extend(new)
+            self.k_checked += len(part)
         return self.found
 
 

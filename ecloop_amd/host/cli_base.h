@@ -188,6 +188,7 @@ typedef struct {
   const char *herd, *dp, *maxf;      /* kangaroo: -herd, -dp, -max (and -k, -seed) */
   const char *prefix;                /* add / rnd: -p */
   const char *part, *split;          /* combine: -part, -split (and, with -p, -k: the split-key search) */
+  const char *kdf;                   /* mul -raw: -kdf sha256 | keccak | sha3 | camp2 (keccak_host.h) */
   bool quiet, endo, raw, bin, version, host_only, rnd_jobs, as_mul;
 } opts_t;
 typedef struct { const char *flag; size_t at; bool takes_value; } optdef_t;
@@ -201,6 +202,7 @@ static const optdef_t OPTDEFS[] = {
     {"-k", offsetof(opts_t, pubkey), true},       {"-b", offsetof(opts_t, baby), true},     {"-m", offsetof(opts_t, words), true},
     {"-p", offsetof(opts_t, prefix), true},      {"-part", offsetof(opts_t, part), true},  {"-split", offsetof(opts_t, split), true},
     {"-herd", offsetof(opts_t, herd), true},      {"-dp", offsetof(opts_t, dp), true},      {"-max", offsetof(opts_t, maxf), true},
+    {"-kdf", offsetof(opts_t, kdf), true},
 };
 static void opts_parse(opts_t *o, int argc, const char **argv) {
   memset(o, 0, sizeof *o);

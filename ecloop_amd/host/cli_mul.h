@@ -96,6 +96,13 @@ static void sha256_stream(u32 st[8], const u8 *msg, size_t len) {
   sha256_block(st, tail);
   if (total == 128) sha256_block(st, tail + 64);
 }
+/* the digest of a -raw line as the device computes it, eight big-endian words: SHA-256, or the function of -kdf (keccak_host.h) */
+static void raw_line_digest(const run_t *run, u32 st[8], const u8 *msg, size_t len) {
+  if (run->kdf == KDF_SHA256) { sha256_stream(st, msg, len); return; }
+  u8 d[32];
+  kdf_host_digest(run->kdf, d, msg, len);
+  for (int i = 0; i < 8; ++i) st[i] = (u32)d[4 * i] << 24 | (u32)d[4 * i + 1] << 16 | (u32)d[4 * i + 2] << 8 | d[4 * i + 3];
+}
 
 /* hit records of one device call: the buffer starts with room for MUL_HITS_CAP of them.  A call that reports more (ECL_E_OVERFLOW: a dense
    filter) has kept up to max(cap, 2^20) of them on the device, and they are fetched here.  A call with more hits than the device keeps -
@@ -131,7 +138,11 @@ static void mul_flush(run_t *run, int g, u64 (*ks)[4], u32 n) {
   free(buf);
   report_progress(&run->rep, n);
 }
-/* -raw: lines [at, at + n) of a chunk, hashed on the device; a hit's private key is that line's SHA-256, recomputed here */
+static bool kdf_test_disagree(void) {
+  const char *e = getenv("ECLOOP_HIP_TEST_KDF_DISAGREE");
+  return e && e[0] == '1';
+}
+/* -raw: lines [at, at + n) of a chunk, hashed on the device; a hit's private key is that line's SHA-256 (-kdf: its digest), recomputed here */
 static void mul_flush_raw(run_t *run, int g, const u8 *text, size_t text_len, const u64 *lines, u32 n) {
   if (!n) return;
   u32 cap = n * 2 + 16 < MUL_HITS_CAP ? n * 2 + 16 : MUL_HITS_CAP, cnt = 0;
@@ -143,10 +154,16 @@ static void mul_flush_raw(run_t *run, int g, const u8 *text, size_t text_len, co
     if (!filter_confirms(&run->flt, buf[i].h160)) continue;
     const u64 ln = lines[buf[i].key_offset];
     u32 st[8];
-    sha256_stream(st, text + (u32)ln, (size_t)(ln >> 32));
+    raw_line_digest(run, st, text + (u32)ln, (size_t)(ln >> 32));
     sc pk = {{(u64)st[6] << 32 | st[7], (u64)st[4] << 32 | st[5], (u64)st[2] << 32 | st[3], (u64)st[0] << 32 | st[1]}};
+    /* test hook: ECLOOP_HIP_TEST_KDF_DISAGREE=1 flips the lowest bit of the host's -kdf digest of every hit - what a device hash that
+       disagrees with the host's looks like from here - so that the verification below has to stop the run (tests/test_gpu_kdf.py) */
+    if (run->kdf != KDF_SHA256 && kdf_test_disagree()) pk.w[0] ^= 1;
     u32 qx[1][FULL_WORDS];
-    if (run->eth || run->tr || run->pub) verify_hits(run, g, &pk, &buf[i], 1, qx);
+    /* plain -raw keeps the reference's behaviour for the Bitcoin types (no verify: main.c:469,474); under -kdf every hit of every type is
+       re-derived on the device from the host's digest: the device's hash and the host's are two implementations, and a key is printed
+       only where they agree */
+    if (run->eth || run->tr || run->pub || run->kdf != KDF_SHA256) verify_hits(run, g, &pk, &buf[i], 1, qx);
     report_hit(&run->rep, buf[i].compressed, run->tr || run->pub ? qx[0] : buf[i].h160, &pk);
   }
   free(buf);
@@ -647,9 +664,9 @@ static void *mul_device_worker(void *arg) {
       if (quiet < 0) { const char *e = getenv("ECLOOP_HIP_PARSE_QUIET"); quiet = e && e[0] == '1'; }
       const bool raw = q->run->opt.raw && !q->run->bin;
       for (size_t k = 0; k < ar->n && !quiet; ++k) {
-        if (raw) { /* what the device computes from the line table: the line's SHA-256 */
+        if (raw) { /* what the device computes from the line table: the line's SHA-256, or its -kdf digest */
           u32 st[8];
-          sha256_stream(st, ar->text + (u32)ar->lines[k], (size_t)(ar->lines[k] >> 32));
+          raw_line_digest(q->run, st, ar->text + (u32)ar->lines[k], (size_t)(ar->lines[k] >> 32));
           printf("%08x%08x%08x%08x%08x%08x%08x%08x\n", st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7]);
         } else
           printf("%016llx%016llx%016llx%016llx\n", (unsigned long long)ar->ks[k][3], (unsigned long long)ar->ks[k][2],

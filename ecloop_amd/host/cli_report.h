@@ -111,6 +111,7 @@ typedef struct run_t {
   int ngpus; /* device contexts (threads); `mul` opens two per GPU */
   ecl_hip *dev[MAX_GPUS];
   bool a33, a65, p2sh, eth, tr, pub, endo, colour, bin, parse_only, seeded;
+  int kdf; /* mul -raw: KDF_* of -kdf (keccak_host.h), 0 = SHA-256 */
   sc range_s, range_e, stride_k;
   u32 ord_offs, ord_size;
   pfx_plan *pfx; /* -p: the plan of the patterns (cli_prefix.h), NULL otherwise */

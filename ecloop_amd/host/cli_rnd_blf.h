@@ -269,6 +269,7 @@ static void usage(const char *prog) { /* the reference's help text (main.c:750-7
       "  -q              - quiet mode (no output to stdout; -o required)\n",
       "  -endo           - use endomorphism (default: false)\n",
       "  -raw            - mul: the private key is the SHA-256 of the line (hashed on the GPU)\n",
+      "  -kdf <name>     - mul -raw: the hash that makes the key - sha256 (default), keccak, sha3, or camp2 (Keccak-256 2031 times: ethercamp)\n",
       "  -bin            - mul: stdin carries 32-byte little-endian scalars instead of hex lines\n",
       "\nbsgs options:\n",
       "  -k <pubkey>     - the public key (66 hex digits 02.. / 03.., or 130 digits 04..), or a file of them, one per line\n",

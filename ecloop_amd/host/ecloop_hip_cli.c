@@ -1,6 +1,6 @@
 /*
  * ecloop-hip — host program with ecloop's command-line surface (add / mul / rnd, blf-gen / blf-check,
- * -f -o -t -a -r -d -q -endo -seed -raw), driving MI355X GPUs through the C ABI of include/ecloop_hip.h.
+ * -f -o -t -a -r -d -q -endo -seed -raw; -kdf beside -raw), driving MI355X GPUs through the C ABI of include/ecloop_hip.h.
  *
  * Plain C, links only libecloop_hip.so.  What lives here is what the reference keeps on the host side of the
  * boundary (citations into /root/reference): reading the filter (main.c:71-131), range / window
@@ -58,6 +58,7 @@ typedef struct { u64 w[4]; } sc; /* 256-bit scalar, little-endian limbs (the ref
 #include "cli_filter.h"
 #include "cli_report.h"
 #include "cli_add.h"
+#include "keccak_host.h"
 #include "cli_mul.h"
 #include "cli_rnd_blf.h"
 #include "cli_prefix.h"
@@ -123,7 +124,8 @@ static double bring_up(run_t *run, int shown, int real) {
   }
   const u32 flags = (run->a33 ? ECL_ADDR33 : 0) | (run->a65 ? ECL_ADDR65 : 0) | (run->p2sh ? ECL_P2SH : 0) | (run->eth ? ECL_ETH : 0) |
                     (run->tr ? ECL_TR : 0) | (run->pub ? ECL_PUB : 0) | (run->endo ? ECL_ENDO : 0) | (run->msk ? ECL_MASK : run->pfx ? ECL_PREFIX : 0) |
-                    (run->split ? ECL_ORIGIN : 0);
+                    (run->split ? ECL_ORIGIN : 0) |
+                    (run->cmd != CMD_MUL ? 0 : run->kdf == KDF_KECCAK ? ECL_KDF_KECCAK : run->kdf == KDF_SHA3 ? ECL_KDF_SHA3 : run->kdf == KDF_CAMP2 ? ECL_KDF_CAMP2 : 0);
   pthread_t th[MAX_GPUS];
   bringup_t job[MAX_GPUS];
   for (int g = 0; g < run->ngpus; ++g) {
@@ -153,6 +155,7 @@ static void print_scalar_row(const char *name, const sc *v) {
 int main(int argc, const char **argv) {
   setlocale(LC_NUMERIC, "");
   hexval_init();
+  khost_init();
 #if defined(__x86_64__)
   have_ssse3 = __builtin_cpu_supports("ssse3") && !getenv("ECLOOP_HIP_NO_SSSE3"); /* (the variable: tests run the scalar hex decoder) */
   have_avx512 = __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512bw") && __builtin_cpu_supports("avx512vl") && !getenv("ECLOOP_HIP_NO_AVX512");
@@ -191,6 +194,17 @@ int main(int argc, const char **argv) {
   list_skip_0x = run.eth;
   /* -p (no reference counterpart): addresses that START with given characters, add / rnd only, no filter file (cli_prefix.h) */
   /* -k with add / rnd / mul (no reference counterpart): the split-key form of -p, nowhere else (cli_splitkey.h) */
+  /* -kdf (no reference counterpart): the hash that turns a line of `mul -raw` into a key - sha256 (the default: -raw as it always was), or
+     what Ethereum brain wallets use: keccak, sha3, camp2 (keccak_host.h).  Checked before anything is opened */
+  if (o->kdf) {
+    run.kdf = kdf_from_name(o->kdf);
+    if (run.kdf < 0) { fprintf(stderr, "invalid -kdf '%s': one of sha256, keccak, sha3, camp2\n", o->kdf); exit(1); }
+    if ((strcmp(verb, "mul") && strcmp(verb, "parse")) || !o->raw) {
+      fprintf(stderr, "-kdf goes with mul -raw only: it chooses the hash that turns a line of text into a key\n");
+      exit(1);
+    }
+    if (o->bin) { fprintf(stderr, "-kdf and -bin exclude each other: binary input holds the keys themselves, nothing is hashed\n"); exit(1); }
+  }
   if (o->pubkey) splitkey_check_options(o, verb);
   if (o->prefix) prefix_check_options(o, verb);
   /* commands that need no search context */

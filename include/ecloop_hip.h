@@ -152,7 +152,20 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
        context (ECL_E_NOBLOOM before a table is set; the others ECL_E_ARG; no look-ahead);
      ecl_hip_diag_bloom runs the device's mask test on the given values.
    ECL_MASK | ECL_ORIGIN is the split-key search of such patterns and behaves as ECL_PREFIX | ECL_ORIGIN beside ECL_ETH does: twelve limbs
-   per `start` and per entry of ecl_hip_verify_eth. */
+   per `start` and per entry of ecl_hip_verify_eth.
+   ECL_KDF_KECCAK, ECL_KDF_SHA3, ECL_KDF_CAMP2 (no reference counterpart): the key derivation function of ecl_hip_mul_batch_raw, a two-bit
+   field - none of them: SHA-256 of the line, the Bitcoin brain-wallet convention and the reference's `-raw`.  Ethereum brain wallets
+   hash otherwise, and with these bits the device does: the digest of the line's bytes m, read as a big-endian 256-bit number, is
+     ECL_KDF_KECCAK  Keccak-256(m): rate 136, capacity 512, first pad byte 0x01, last pad byte 0x80 (old ethaddress, early ethercamp);
+     ECL_KDF_SHA3    SHA3-256(m): the same sponge with the first pad byte 0x06 (FIPS 202);
+     ECL_KDF_CAMP2   (both bits) d_1 = Keccak-256(m), d_(i+1) = Keccak-256(the 32 bytes of d_i), the digest is d_2031: 2031 hashes in all
+                     (the later ethercamp wallet; brainflayer's `camp2`).
+   (A length = 135 mod 136 puts both pad bytes into one, 0x81 / 0x86; a length = 0 mod 136 adds a block of padding.)  Valid beside every
+   context that has a `mul` - any set of ECL_ADDR33, ECL_ADDR65, ECL_P2SH; ECL_ETH; ECL_TR; ECL_PUB; with ECL_ENDO wherever that context
+   allows it - and ECL_E_ARG beside ECL_ORIGIN, ECL_INSERT, ECL_HERD, ECL_PREFIX or ECL_MASK.  ONLY ecl_hip_mul_batch_raw changes: it hashes
+   the lines with the chosen function where it hashes them with SHA-256, everything around that (pieces, the text sent along, the repeat
+   pass, coverage, overflow, ecl_hip_fetch_found) as it is; ecl_hip_add_range, ecl_hip_mul_batch and every other call behave as on the
+   same context without the bits.  ecl_hip_selftest of such a context also runs its hash on known answers (ECL_E_SELFTEST). */
 #define ECL_ADDR33 1u
 #define ECL_ADDR65 2u
 #define ECL_ENDO 4u
@@ -165,6 +178,9 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
 #define ECL_HERD 2048u
 #define ECL_PREFIX 4096u
 #define ECL_MASK 0x2000u /* 8192 */
+#define ECL_KDF_KECCAK 0x4000u /* 16384 */
+#define ECL_KDF_SHA3 0x8000u   /* 32768 */
+#define ECL_KDF_CAMP2 0xC000u  /* both: the two bits are one field */
 
 /* return codes */
 #define ECL_OK 0
@@ -297,7 +313,8 @@ int ecl_hip_verify_tr(ecl_hip *h, const uint64_t (*k)[4], uint32_t n, uint32_t (
    and text_bytes < 2^32 - 16 per call, every line inside the text (ECL_E_ARG otherwise).  key_offset of a hit = line
    index; the caller re-derives that line's private key (one SHA-256) for the found record.  Page-locked `text` / `lines`
    arrays are read by DMA directly; a call is pipelined like ecl_hip_mul_batch's (the table and the hashing piece by piece), so large
-   calls (2^24 lines) run at the rate of large ecl_hip_mul_batch calls. */
+   calls (2^24 lines) run at the rate of large ecl_hip_mul_batch calls.  On a context opened with ECL_KDF_KECCAK, ECL_KDF_SHA3 or
+   ECL_KDF_CAMP2 the digest is that function's instead of SHA-256's (see the flags), and so is the key the caller re-derives. */
 int ecl_hip_mul_batch_raw(ecl_hip *h, const uint8_t *text, uint32_t text_bytes, const uint64_t *lines, uint32_t n, ecl_found *out,
                           uint32_t cap, uint32_t *nout);
 
