@@ -16,6 +16,7 @@ PREFIX = 4096  # the prefix filter in place of the bloom: beside ADDR33 / ADDR65
 MASK = 8192  # the mask filter in place of the bloom: beside ETH alone, with or without ENDO / ORIGIN (include/ecloop_hip.h)
 # the key derivation function of mul_batch_raw, a two-bit field (include/ecloop_hip.h): none = SHA-256; valid beside every context that has a `mul`
 KDF_KECCAK, KDF_SHA3, KDF_CAMP2 = 0x4000, 0x8000, 0xC000
+BIP39 = 0x10000  # the lines of mul_batch_raw are BIP39 phrases, lines[0] the derivation record (include/ecloop_hip.h: ECL_KDF_BIP39); not beside a KDF_* bit
 KDF_FLAGS = {None: 0, "sha256": 0, "keccak": KDF_KECCAK, "sha3": KDF_SHA3, "camp2": KDF_CAMP2}
 E_ARG = -1
 E_NOBLOOM = -5
@@ -141,9 +142,12 @@ class Device:
     """One GPU context (ecl_hip handle)."""
 
     def __init__(self, device=0, a33=True, a65=False, endo=False, ord_offs=0, p2sh=False, eth=False, tr=False, pub=False, origin=False,
-                 insert=False, herd=False, prefix=False, mask=False, kdf=None):
+                 insert=False, herd=False, prefix=False, mask=False, kdf=None, bip39=False):
         if kdf not in KDF_FLAGS:
             raise ValueError("kdf is None (SHA-256), 'keccak', 'sha3' or 'camp2'")
+        if bip39 and (KDF_FLAGS[kdf] or origin or insert or herd or prefix or mask):
+            raise ValueError("bip39 goes with the contexts that have a `mul`, and not with a kdf: not with origin, insert, herd, prefix or mask")
+        self.bip39 = bool(bip39)
         if KDF_FLAGS[kdf] and (origin or insert or herd or prefix or mask):
             raise ValueError("a kdf goes with the contexts that have a `mul`: not with origin, insert, herd, prefix or mask")
         self.kdf = kdf if KDF_FLAGS[kdf] else None
@@ -169,7 +173,7 @@ class Device:
         if tr and (a33 or a65 or p2sh or eth or endo):
             raise ValueError("Taproot is searched alone and without the endomorphism: Device(a33=False, tr=True)")
         flags = (ADDR33 if a33 else 0) | (ADDR65 if a65 else 0) | (P2SH if p2sh else 0) | (ETH if eth else 0) | (TR if tr else 0) | (PUB if pub else 0) | (ENDO if endo else 0) | \
-                (ORIGIN if origin else 0) | (INSERT if insert else 0) | (HERD if herd else 0) | (PREFIX if prefix else 0) | (MASK if mask else 0) | KDF_FLAGS[kdf]
+                (ORIGIN if origin else 0) | (INSERT if insert else 0) | (HERD if herd else 0) | (PREFIX if prefix else 0) | (MASK if mask else 0) | KDF_FLAGS[kdf] | (BIP39 if bip39 else 0)
         rc = self.lib.ecl_hip_open(C.byref(self.h), device, flags, ord_offs)
         if rc != 0:
             msg = self.lib.ecl_hip_last_error(self.h).decode() if self.h else ""
@@ -316,6 +320,22 @@ class Device:
         rc = self.lib.ecl_hip_mul_batch_raw(self.h, buf.ctypes.data, len(text), table.ctypes.data, len(lines), out.ctypes.data, cap, C.byref(n))
         self._chk(rc, allow=(E_OVERFLOW,))
         return out[: min(n.value, cap)], n.value
+
+    @staticmethod
+    def seed_record(path, passphrase=b"", reuse=False):
+        """the derivation record of a Device(bip39=True) call (include/ecloop_hip.h: ECL_KDF_BIP39): magic, reuse, depth, pass_len, zero;
+        the path's elements as little-endian u32; the passphrase"""
+        return b"B39\0" + bytes([1 if reuse else 0, len(path), len(passphrase), 0]) + b"".join(int(e).to_bytes(4, "little") for e in path) + bytes(passphrase)
+
+    def seed_batch(self, phrases, path, passphrase=b"", reuse=False, cap=4096):
+        """phrases (bytes objects) -> (records, total) for the keys at `path` (a list of 32-bit elements, bit 31 = hardened): lines[0] is the
+        record, key_offset of a record the index into `phrases`.  reuse=True: the phrases are those of the call before, only the path is
+        walked again from the kept master nodes"""
+        if not self.bip39:
+            raise ValueError("seed_batch goes with Device(bip39=True)")
+        if len(path) > 255 or len(passphrase) > 255:
+            raise ValueError("a path of more than 255 elements or a passphrase of more than 255 bytes does not fit the record")
+        return self.mul_batch_raw([self.seed_record(path, passphrase, reuse)] + list(phrases), cap=cap)
 
     def set_mul_window(self, bits):
         """window width of this context's `mul` table (8..29 bits; 0 = automatic: 22, then 26 after 2^30 scalars)"""

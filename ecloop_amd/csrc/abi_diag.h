@@ -247,6 +247,12 @@ extern "C" int ecl_hip_selftest(ecl_hip* h) {
     h->kdf = kdf;
     return rc != ECL_OK ? rc : kdf_selftest(h);
   }
+  if (h->bip39) {  // likewise, then both derivation kernels on BIP39's test phrase (abi_seed.h)
+    h->bip39 = false;
+    const int rc = ecl_hip_selftest(h);
+    h->bip39 = true;
+    return rc != ECL_OK ? rc : seed_selftest(h);
+  }
   if (h->flags & ECL_HERD) {  // a herd context tests the device code a public-key context tests (the known answers, the x-only walk, the
     // window sum); the herd kernel has no second path on the device to be checked against: tests/test_gpu_kangaroo.py checks it
     const u32 offs = h->offs;

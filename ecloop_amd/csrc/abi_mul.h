@@ -382,27 +382,8 @@ static void raw_scalars_launch(u32 kdf, hipStream_t st, const u32* d_text, u32 t
     hipLaunchKernelGGL(k_raw_scalars, dim3((m + 255) / 256), dim3(256), 0, st, d_text, text_bytes, have, d_lines, m, d_out, d_flags);
 }
 
-// `mul -raw`: lines of text in, SHA-256 (or the context's ECL_KDF_* hash) on the device, then the `mul` body on the digests (n <= 2^26 lines a call): the pieces of
-// ecl_hip_mul_batch, with 8 bytes of table + the line instead of 32 bytes of scalar on the copy stream, and every piece's lines hashed
-// into its staging buffer ahead of its window sums (details at the two lambdas below).  Until round 6 a call was ONE piece of at most
-// 2^22 lines on one stream and the host program made ~2 M-line calls: 0.79-0.87 G lines/s over 2^30 pass phrases; as pieces with the
-// hashing between the window sums of one stream and the whole text sent first, 2^24-line calls took 20.2 ms against 14.0 for 2^24
-// scalars; now 14.5-15.1 ms, 1.09-1.16 G lines/s through the host program (profiles/r06_mul_raw.txt).
-extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t text_bytes, const uint64_t* lines, uint32_t n, ecl_found* out,
-                                     uint32_t cap, uint32_t* nout) {
-  if (!h || (!text && text_bytes) || (!lines && n) || (!out && cap) || !nout || n > MUL_RAW_MAX || text_bytes > 0xFFFFFFF0u || cap > ECL_CAP_MAX) return ECL_E_ARG;
-  if (h->flags & (ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX | ECL_MASK)) return ECL_E_ARG;
-  *nout = 0;
-  if (!h->d_bloom.p) return ECL_E_NOBLOOM;
-  if (n == 0) return ECL_OK;
-  HIPCHK(h, hipSetDevice(h->dev));
-  call_frame f = {h, "mul_batch_raw", (h->flags & ECL_TR) ? "mul_batch_raw" : nullptr, n, out, cap, nout, true, false};
-  int rc;
-  if ((rc = f.begin()) != ECL_OK) return rc;
-  u32 W;
-  if ((rc = mul_setup_auto(h, n, &W)) != ECL_OK) return rc;
-  const wtab gtab = wtab_make(h->d_multab, W);
-  h->mul_seen += n;
+// the device text and line table of a `mul -raw` call of n lines over text_bytes bytes, and the stream its lines are hashed on
+static int raw_buffers(ecl_hip* h, u32 text_bytes, u32 n) {
   const size_t text_words = ((size_t)text_bytes + 3) / 4 + 2;  // two spare words: the gather reads one word past the last byte
   if (text_words > h->d_rawtext.n || n > h->d_rawlines.n) {
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -429,6 +410,33 @@ extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t t
     HIPCHK(h, hipStreamCreateWithPriority(&h->prep_stream, hipStreamNonBlocking, hi));  // (lowest priority instead: no difference measured)
     for (int i = 0; i < MUL_NBUF; ++i) HIPCHK(h, hipEventCreateWithFlags(&h->ev_hashed[i], hipEventDisableTiming));
   }
+  return ECL_OK;
+}
+
+static int seed_batch(ecl_hip* h, const uint8_t* text, uint32_t text_bytes, const uint64_t* lines, uint32_t n, ecl_found* out, uint32_t cap, uint32_t* nout);
+// `mul -raw`: lines of text in, SHA-256 (or the context's ECL_KDF_* hash) on the device, then the `mul` body on the digests (n <= 2^26 lines a call): the pieces of
+// ecl_hip_mul_batch, with 8 bytes of table + the line instead of 32 bytes of scalar on the copy stream, and every piece's lines hashed
+// into its staging buffer ahead of its window sums (details at the two lambdas below).  Until round 6 a call was ONE piece of at most
+// 2^22 lines on one stream and the host program made ~2 M-line calls: 0.79-0.87 G lines/s over 2^30 pass phrases; as pieces with the
+// hashing between the window sums of one stream and the whole text sent first, 2^24-line calls took 20.2 ms against 14.0 for 2^24
+// scalars; now 14.5-15.1 ms, 1.09-1.16 G lines/s through the host program (profiles/r06_mul_raw.txt).
+extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t text_bytes, const uint64_t* lines, uint32_t n, ecl_found* out,
+                                     uint32_t cap, uint32_t* nout) {
+  if (!h || (!text && text_bytes) || (!lines && n) || (!out && cap) || !nout || n > MUL_RAW_MAX || text_bytes > 0xFFFFFFF0u || cap > ECL_CAP_MAX) return ECL_E_ARG;
+  if (h->flags & (ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX | ECL_MASK)) return ECL_E_ARG;
+  *nout = 0;
+  if (!h->d_bloom.p) return ECL_E_NOBLOOM;
+  if (n == 0) return ECL_OK;
+  HIPCHK(h, hipSetDevice(h->dev));
+  if (h->bip39) return seed_batch(h, text, text_bytes, lines, n, out, cap, nout);  // lines[0] is the derivation record (abi_seed.h)
+  call_frame f = {h, "mul_batch_raw", (h->flags & ECL_TR) ? "mul_batch_raw" : nullptr, n, out, cap, nout, true, false};
+  int rc;
+  if ((rc = f.begin()) != ECL_OK) return rc;
+  u32 W;
+  if ((rc = mul_setup_auto(h, n, &W)) != ECL_OK) return rc;
+  const wtab gtab = wtab_make(h->d_multab, W);
+  h->mul_seen += n;
+  if ((rc = raw_buffers(h, text_bytes, n)) != ECL_OK) return rc;
   u64* d_lines = h->d_rawlines.p;
   u32* d_flags = h->d_counter.p + CW_RAW_OUTSIDE;  // [0] a line outside the text, [1] CW_RAW_LATE: a line beyond the part of the text that was on the device when it was hashed
   u32* d_text = h->d_rawtext.p;

@@ -28,6 +28,7 @@
 #include "tr_kernels.h"
 #include "aux_kernels.h"
 #include "herd_kernel.h"
+#include "bip39.h"
 #include "devbuf.h"
 #include "callstate.h"
 
@@ -55,6 +56,7 @@ struct ecl_hip {
   int dev = 0;
   u32 flags = 0, offs = 0;
   u32 kdf = 0;        // ECL_KDF_* of ecl_hip_open (not part of `flags`): the hash of ecl_hip_mul_batch_raw, 0 = SHA-256
+  bool bip39 = false; // ECL_KDF_BIP39 of ecl_hip_open (not part of `flags` either): ecl_hip_mul_batch_raw derives BIP32 keys from phrases (abi_seed.h)
   u32 B = 1024;       // table points per group
   u32 Tmax = 0;       // lanes walked concurrently (0 = derive from occupancy)
   hipStream_t stream = nullptr;
@@ -86,6 +88,10 @@ struct ecl_hip {
   devbuf<u32> d_trslab, d_trtmp[2], d_trslab_mul[2];
   u32 tr_epoch = 0, tr_epoch_mul[2] = {};
   devbuf<u32> d_rawtext; devbuf<u64> d_rawlines;  // `mul -raw`: text and line table of one call
+  // ECL_KDF_BIP39: the master nodes of the last reuse = 0 call (64 bytes per phrase), how many, their passphrase, and whether the call
+  // before this one returned ECL_OK or ECL_E_OVERFLOW - what a reuse = 1 call is checked against
+  devbuf<u32> d_nodes; u32 seed_n = 0, seed_pass_len = 0; uint8_t seed_pass[BIP39_PASS_MAX] = {};
+  bool seed_have = false, seed_last_ok = false;
   hipStream_t copy_stream = nullptr, stream2 = nullptr;  // `mul`: the copy engine's stream; the second compute stream (pieces alternate)
   hipEvent_t ev_copied[MUL_NBUF] = {}, ev_free[MUL_NBUF] = {}, ev_fork = nullptr, ev_join = nullptr;
   hipStream_t prep_stream = nullptr; hipEvent_t ev_hashed[MUL_NBUF] = {};  // `mul -raw`: the lines are hashed on a stream of their own, ahead of the pieces
@@ -169,6 +175,10 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   const u32 kdf = flags & ECL_KDF_CAMP2;
   if (kdf && (flags & (ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX | ECL_MASK))) return ECL_E_ARG;
   flags &= ~ECL_KDF_CAMP2;
+  // BIP39 phrases in place of hashed lines (ECL_KDF_BIP39): beside the same contexts, and not beside an ECL_KDF_* bit
+  const u32 bip39 = flags & ECL_KDF_BIP39;
+  if (bip39 && (kdf || (flags & (ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX | ECL_MASK)))) return ECL_E_ARG;
+  flags &= ~ECL_KDF_BIP39;
   if (!out || ord_offs > 255 || !(flags & (types | ECL_ETH | ECL_TR | ECL_PUB)) ||
       (flags & ~(types | ECL_ETH | ECL_TR | ECL_PUB | ECL_ENDO | ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX | ECL_MASK)))
     return ECL_E_ARG;
@@ -189,7 +199,7 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   int n = ecl_hip_device_count();
   if (device < 0 || device >= n) return ECL_E_NODEV;
   ecl_hip* h = new ecl_hip();
-  h->dev = device, h->flags = flags, h->kdf = kdf, h->offs = ord_offs, h->la_max = la_default_max();
+  h->dev = device, h->flags = flags, h->kdf = kdf, h->bip39 = bip39 != 0, h->offs = ord_offs, h->la_max = la_default_max();
   *out = h;
   HIPCHK(h, hipSetDevice(device));
   HIPCHK(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
@@ -205,9 +215,9 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   // the self-test checks the CODE (known answers, walk kernel against the double-and-add kernel): once per process
   // for every (device, kernel selection) is enough - eight handles for eight shards of one scan do not repeat it
   static std::mutex mu;
-  static std::set<u32> passed;
+  static std::set<u64> passed;
   const char* skip = getenv("ECL_HIP_SKIP_SELFTEST");
-  const u32 key = (u32)device * 65536u + (flags | kdf);  // flags | kdf < 65536
+  const u64 key = (u64)device << 32 | (flags | kdf | bip39);
   {
     std::lock_guard<std::mutex> lk(mu);
     if ((skip && skip[0] == '1') || passed.count(key)) return ECL_OK;
@@ -1017,5 +1027,6 @@ extern "C" int ecl_hip_add_range(ecl_hip* h, const uint64_t start[4], uint64_t n
 }
 
 #include "abi_mul.h"
+#include "abi_seed.h"
 #include "abi_tr.h"
 #include "abi_diag.h"

@@ -6,6 +6,7 @@ All curve / hash work goes to the device (ecloop_amd.capi.Device); nothing here 
 Names follow the reference: load_filter, cmd_add, cmd_mul, calc_priv, pk_verify_hash, ctx_write_found.
 """
 import hashlib
+import hmac
 import math
 import os
 import struct
@@ -279,31 +280,105 @@ def kdf_digest(name, line):
     raise ValueError("kdf is one of sha256, keccak, sha3, camp2")
 
 
+# ----------------------------------------------------------------------------------------------- BIP39 phrases (seed)
+# The definition of what a Device(bip39=True) derives, in plain Python: BIP39's seed of the phrase bytes as given (no NFKD, no word list, no
+# checksum test), BIP32's master node and CKDpriv down the path.  A node BIP32 calls invalid gives the key 0.
+BIP32_HARDENED = 1 << 31
+BIP32_DEPTH_MAX = 10
+BIP39_PASS_MAX = 99
+SEED_COUNT_MAX = 1024
+SEED_BATCH = 1 << 20
+_G = (0x79BE667EF9DCBBAC55A06295CE870B07029BFCDB2DCE28D959F2815B16F81798, 0x483ADA7726A3C4655DA4FBFC0E1108A8FD17B448A68554199C47D08FFB10D4B8)
+
+
+def parse_path(text):
+    """m/44'/0'/0'/0/0 (' or h: hardened) -> the list of 32-bit path elements, bit 31 = hardened; at most 10 of them"""
+    parts = text.split("/")
+    if parts[0] != "m" or len(parts) - 1 > BIP32_DEPTH_MAX:
+        raise ValueError("a path is m, or m/ followed by at most 10 elements: %r" % text)
+    out = []
+    for p in parts[1:]:
+        hard = p[-1:] in ("'", "h")
+        digits = p[:-1] if hard else p
+        if not digits.isdigit() or not digits.isascii() or int(digits) >= BIP32_HARDENED:
+            raise ValueError("a path element is a number below 2^31, with ' or h for hardened: %r" % text)
+        out.append(int(digits) | (BIP32_HARDENED if hard else 0))
+    return out
+
+
+def format_path(path):
+    return "/".join(["m"] + ["%d'" % (e & (BIP32_HARDENED - 1)) if e & BIP32_HARDENED else "%d" % e for e in path])
+
+
+def _pt_add(a, b):
+    if a is None or b is None:
+        return a if b is None else b
+    if a[0] == b[0]:
+        if (a[1] + b[1]) % P == 0:
+            return None
+        lam = 3 * a[0] * a[0] * pow(2 * a[1], -1, P) % P
+    else:
+        lam = (b[1] - a[1]) * pow(b[0] - a[0], -1, P) % P
+    x = (lam * lam - a[0] - b[0]) % P
+    return x, (lam * (a[0] - x) - a[1]) % P
+
+
+def _ser_pub(k):
+    acc, q = None, _G
+    while k:
+        if k & 1:
+            acc = _pt_add(acc, q)
+        q = _pt_add(q, q)
+        k >>= 1
+    return bytes([2 | (acc[1] & 1)]) + acc[0].to_bytes(32, "big")
+
+
+def bip39_key(phrase, path, passphrase=b""):
+    """the private key (int) a Device(bip39=True) derives for the phrase (bytes) at `path` (a list of elements, or text for parse_path);
+    0 for a node BIP32 calls invalid"""
+    if isinstance(path, str):
+        path = parse_path(path)
+    seed = hashlib.pbkdf2_hmac("sha512", bytes(phrase), b"mnemonic" + bytes(passphrase), 2048, 64)
+    I = hmac.new(b"Bitcoin seed", seed, hashlib.sha512).digest()
+    k, c = int.from_bytes(I[:32], "big"), I[32:]
+    if not 0 < k < N:
+        return 0
+    for e in path:
+        data = (b"\0" + k.to_bytes(32, "big") if e & BIP32_HARDENED else _ser_pub(k)) + e.to_bytes(4, "big")
+        I = hmac.new(c, data, hashlib.sha512).digest()
+        il = int.from_bytes(I[:32], "big")
+        if il >= N or (il + k) % N == 0:
+            return 0
+        k, c = (il + k) % N, I[32:]
+    return k
+
+
 class FoundRecord:
-    __slots__ = ("label", "h160", "pk", "prefix", "address", "split")
+    __slots__ = ("label", "h160", "pk", "prefix", "address", "split", "path", "phrase")
 
     def __init__(self, label, h160, pk):
         self.label, self.h160, self.pk = label, h160, pk
         self.split = None  # a record of a split-key search: the image e; pk is then the PARTIAL key (splitkey_combine), its lines end with split:<e>
         self.address = ""  # a record of prefix_search: the address text, appended to its lines
         self.prefix = ""  # a verified pub record: "02" / "03", the first byte of the compressed key its line prints
+        self.path, self.phrase = None, None  # a record of cmd_seed: the path's text and the phrase (bytes), appended to its lines
 
     def line(self):
         """outfile format of ctx_write_found (main.c:193-195)"""
         return "%s\t%s\t%064x" % (self.label, self.prefix + "".join("%08x" % int(w) for w in self.h160), self.pk) + ("\t" + self.address if self.address else "") + \
-            ("" if self.split is None else "\tsplit:%d" % self.split)
+            ("" if self.split is None else "\tsplit:%d" % self.split) + ("" if self.path is None else "\t%s\t%s" % (self.path, self.phrase.decode("latin-1")))
 
     def stdout_line(self):
         """stdout format (main.c:187-189)"""
         return "%s: %s <- %064x" % (self.label, self.prefix + "".join("%08x" % int(w) for w in self.h160), self.pk) + (" " + self.address if self.address else "") + \
-            ("" if self.split is None else " split:%d" % self.split)
+            ("" if self.split is None else " split:%d" % self.split) + ("" if self.path is None else " %s %s" % (self.path, self.phrase.decode("latin-1")))
 
 
 class KeySearch:
     """ctx_t + cmd_add / cmd_mul for one GPU."""
 
     def __init__(self, flt, device=0, a33=True, a65=False, endo=False, ord_offs=0, verify=True, launch_keys=1 << 32,
-                 half_group=0, max_lanes=0, device_cls=None, p2sh=False, eth=False, tr=False, pub=False, prefix=False, origin=None, mask=False, kdf=None):
+                 half_group=0, max_lanes=0, device_cls=None, p2sh=False, eth=False, tr=False, pub=False, prefix=False, origin=None, mask=False, kdf=None, bip39=False):
         if pub:
             a33 = False  # public keys are searched alone (with or without the endomorphism)
         elif tr:
@@ -335,6 +410,11 @@ class KeySearch:
         self.kdf = None if kdf == "sha256" else kdf  # the hash of cmd_mul_raw (kdf_digest); None: SHA-256
         if self.kdf:
             kw["kdf"] = self.kdf
+        self.bip39 = bool(bip39)  # the context of cmd_seed: the lines of mul_batch_raw are BIP39 phrases
+        if bip39:
+            if self.kdf:  # ("sha256" is no kdf: None by now)
+                raise ValueError("bip39 does not go with a kdf")
+            kw["bip39"] = True
         self.origin = None  # split-key search (prefix_search(origin=)): the walk is O + k G, the records' keys are partial keys
         if origin is not None:
             if not (prefix or mask):
@@ -518,6 +598,50 @@ class KeySearch:
                 self._verify(new)
             self.found.extend(new)
             self.k_checked += len(part)
+        return self.found
+
+
+    def cmd_seed(self, phrases, paths, count=1, passphrase=b"", cap=4096):
+        """`seed`: BIP39 phrases (bytes objects) x BIP32 paths (lists of elements or text), `count` consecutive values of each path's last
+        element - on a KeySearch(bip39=True).  Per batch of 2^20 phrases one reuse = 0 call hashes the phrases, every further (path, index)
+        walks from the kept master nodes.  The key of a found line is bip39_key's, recomputed here, and every hit is re-derived from it
+        through the device: a device derivation that disagrees raises the hash mismatch error.  Records carry .path and .phrase."""
+        if not self.bip39:
+            raise ValueError("cmd_seed goes with KeySearch(bip39=True)")
+        paths = [parse_path(p) if isinstance(p, str) else list(p) for p in paths]
+        if not paths or not 1 <= count <= SEED_COUNT_MAX or (count > 1 and any(not p for p in paths)):
+            raise ValueError("cmd_seed takes at least one path and a count of 1 ... 1024 (above 1: no path of depth 0)")
+        todo = []
+        for p in paths:
+            last = p[-1] if p else 0
+            if count > 1 and (last & (BIP32_HARDENED - 1)) + count > BIP32_HARDENED:
+                raise ValueError("the last element of a path plus the count passes 2^31")
+            todo += [p[:-1] + [last + j] for j in range(count)] if p else [p]
+        for at in range(0, len(phrases), SEED_BATCH):
+            part = phrases[at : at + SEED_BATCH]
+            for i, path in enumerate(todo):
+                c = max(cap, 2 * len(part))
+                while True:
+                    raw, total = self.dev.seed_batch(part, path, passphrase=passphrase, reuse=i > 0, cap=c)
+                    if total <= c:
+                        break
+                    rest = self.dev.fetch_found(c, total - c)  # (as in cmd_mul)
+                    if len(rest) == total - c:
+                        raw = np.concatenate([raw, rest])
+                        break
+                    c = total
+                new = []
+                for r in raw:
+                    if self.flt.confirm(r["h160"]):
+                        phrase = part[int(r["key_offset"])]
+                        rec = FoundRecord(label_of(r["compressed"]), [int(v) for v in r["h160"]], bip39_key(phrase, path, passphrase))
+                        rec.path, rec.phrase = format_path(path), phrase
+                        new.append(rec)
+                        self.k_found += 1
+                if self.verify:
+                    self._verify(new)
+                self.found.extend(new)
+                self.k_checked += len(part)
         return self.found
 
 

@@ -189,7 +189,11 @@ typedef struct {
   const char *prefix;                /* add / rnd: -p */
   const char *part, *split;          /* combine: -part, -split (and, with -p, -k: the split-key search) */
   const char *kdf;                   /* mul -raw: -kdf sha256 | keccak | sha3 | camp2 (keccak_host.h) */
+  const char *pass;                  /* seed: -pass */
+  const char *paths[9]; int npaths;  /* seed: every -path in order (a ninth is kept so that cli_seed.h can refuse it by name); path_missing: a last -path without a value */
+  bool path_missing;
   bool quiet, endo, raw, bin, version, host_only, rnd_jobs, as_mul;
+  bool keys;                         /* seed -keys (hidden): the host's own derivation alone, no GPU */
 } opts_t;
 typedef struct { const char *flag; size_t at; bool takes_value; } optdef_t;
 static const optdef_t OPTDEFS[] = {
@@ -202,11 +206,18 @@ static const optdef_t OPTDEFS[] = {
     {"-k", offsetof(opts_t, pubkey), true},       {"-b", offsetof(opts_t, baby), true},     {"-m", offsetof(opts_t, words), true},
     {"-p", offsetof(opts_t, prefix), true},      {"-part", offsetof(opts_t, part), true},  {"-split", offsetof(opts_t, split), true},
     {"-herd", offsetof(opts_t, herd), true},      {"-dp", offsetof(opts_t, dp), true},      {"-max", offsetof(opts_t, maxf), true},
-    {"-kdf", offsetof(opts_t, kdf), true},
+    {"-kdf", offsetof(opts_t, kdf), true},        {"-pass", offsetof(opts_t, pass), true},
+    {"-keys", offsetof(opts_t, keys), false},
 };
 static void opts_parse(opts_t *o, int argc, const char **argv) {
   memset(o, 0, sizeof *o);
-  for (int i = 1; i < argc; ++i)
+  for (int i = 1; i < argc; ++i) {
+    if (!strcmp(argv[i], "-path")) { /* the one option that may be given more than once: every value is kept */
+      if (i + 1 >= argc) o->path_missing = true;
+      else if (o->npaths < 9) o->paths[o->npaths++] = argv[++i];
+      else ++i;
+      continue;
+    }
     for (size_t d = 0; d < sizeof OPTDEFS / sizeof OPTDEFS[0]; ++d) {
       if (strcmp(argv[i], OPTDEFS[d].flag) != 0) continue;
       char *field = (char *)o + OPTDEFS[d].at;
@@ -214,5 +225,6 @@ static void opts_parse(opts_t *o, int argc, const char **argv) {
       else if (i + 1 < argc && !*(const char **)field) *(const char **)field = argv[++i];
       break;
     }
+  }
 }
 static u64 opt_number(const char *text, u64 fallback) { return text ? strtoull(text, NULL, 10) : fallback; }

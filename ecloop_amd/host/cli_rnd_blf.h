@@ -245,6 +245,7 @@ static void usage(const char *prog) { /* the reference's help text (main.c:750-7
       "  rnd             - search random range of bits in given range\n",
       "  bsgs            - find the private key of a known public key in given range (baby-step giant-step, one GPU)\n",
       "  kangaroo        - the same for ranges too wide for bsgs (Pollard's lambda method, one GPU)\n",
+      "  seed            - search the BIP32 keys of BIP39 phrases (from stdin, one per line; derived on the GPU, one GPU)\n",
       "\nCompute options:\n",
       "  -f <file>       - filter file to search (list of hashes or bloom fitler)\n",
       "  -p <pattern>    - add, rnd: search addresses that START with the pattern, or with any pattern of a file (one per line), in\n",
@@ -271,6 +272,13 @@ static void usage(const char *prog) { /* the reference's help text (main.c:750-7
       "  -raw            - mul: the private key is the SHA-256 of the line (hashed on the GPU)\n",
       "  -kdf <name>     - mul -raw: the hash that makes the key - sha256 (default), keccak, sha3, or camp2 (Keccak-256 2031 times: ethercamp)\n",
       "  -bin            - mul: stdin carries 32-byte little-endian scalars instead of hex lines\n",
+      "\nseed options:\n",
+      "  -f, -a, -o, -q  - as above; a found line ends with the path and the phrase.  Phrases are taken as given: no word list, no\n",
+      "                    checksum test, no NFKD\n",
+      "  -path <path>    - the key's path, up to 8 times: m/44'/0'/0'/0/0, ' or h for hardened, at most 10 elements (default by -a: c, u, x\n",
+      "                    m/44'/0'/0'/0/0; s m/49'/0'/0'/0/0; t m/86'/0'/0'/0/0; e m/44'/60'/0'/0/0)\n",
+      "  -n <count>      - also search the next count - 1 values of each path's last element (1 ... 1024, default: 1)\n",
+      "  -pass <text>    - the BIP39 passphrase (at most 99 bytes, default: none)\n",
       "\nbsgs options:\n",
       "  -k <pubkey>     - the public key (66 hex digits 02.. / 03.., or 130 digits 04..), or a file of them, one per line\n",
       "  -r <range>      - the range a:b that holds the key, in hex, both ends included (example: 8000:ffffff)\n",

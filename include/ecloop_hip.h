@@ -165,7 +165,28 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
    allows it - and ECL_E_ARG beside ECL_ORIGIN, ECL_INSERT, ECL_HERD, ECL_PREFIX or ECL_MASK.  ONLY ecl_hip_mul_batch_raw changes: it hashes
    the lines with the chosen function where it hashes them with SHA-256, everything around that (pieces, the text sent along, the repeat
    pass, coverage, overflow, ecl_hip_fetch_found) as it is; ecl_hip_add_range, ecl_hip_mul_batch and every other call behave as on the
-   same context without the bits.  ecl_hip_selftest of such a context also runs its hash on known answers (ECL_E_SELFTEST). */
+   same context without the bits.  ecl_hip_selftest of such a context also runs its hash on known answers (ECL_E_SELFTEST).
+   ECL_KDF_BIP39 (no reference counterpart): the lines of ecl_hip_mul_batch_raw are BIP39 phrases and the scalar of a line is a BIP32
+   private key of its seed.  Valid beside the contexts the ECL_KDF_* field is valid beside; ECL_E_ARG together with any ECL_KDF_* bit and
+   beside ECL_ORIGIN, ECL_INSERT, ECL_HERD, ECL_PREFIX or ECL_MASK.  ONLY ecl_hip_mul_batch_raw changes.  Its parameters travel in band:
+   lines[0] of EVERY call is not a phrase but the derivation record, lines[1 .. n - 1] are the phrases, key_offset of a hit is the phrase
+   index (lines[1] is phrase 0), and the call asks for n - 1 scalars (coverage counts against that).  The record, packed, little-endian:
+       u8 magic[4] = "B39\0";  u8 reuse;  u8 depth (0 .. 10);  u8 pass_len (0 .. 99);  u8 zero;
+       u32 path[depth]   (bit 31 = hardened);   u8 pass[pass_len]
+   A line length other than 8 + 4 depth + pass_len, a wrong magic, depth > 10, pass_len > 99, a reuse byte other than 0 or 1, a zero byte
+   that is not zero, a record or a phrase that lies outside the text, or more than 2^22 phrases are ECL_E_ARG with a message in
+   ecl_hip_last_error, and nothing is launched; n = 1 (the record alone) is ECL_OK with no records.  For the phrase bytes m,
+   taken as given (no NFKD, no word list, no checksum test):
+       seed = PBKDF2-HMAC-SHA512(m, "mnemonic" || pass, 2048 iterations, 64 bytes);  (k, c) = HMAC-SHA512("Bitcoin seed", seed);
+       per path element i, CKDpriv: I = HMAC-SHA512(c, 0x00 || ser256(k) || ser32(i)) if hardened, else of serP(k G) || ser32(i);
+       k <- I_L + k mod n, c <- I_R;  the scalar is the last k (depth 0: the master key).
+   A node BIP32 calls invalid (master I_L = 0 or >= n, a child's I_L >= n, a child key 0) gives the scalar 0, which is counted and not
+   probed.  reuse = 0: the phrases are hashed and every phrase's master node (64 bytes) is kept by the context.  reuse = 1: the phrases
+   are taken to be those of the call before and are not read; the path is walked from the kept nodes - another index or path costs a few
+   HMACs per phrase, not 4096 compressions.  reuse = 1 is ECL_E_ARG when no nodes are kept, when n or pass differs from the kept nodes',
+   or when the previous ecl_hip_mul_batch_raw call on the context returned neither ECL_OK nor ECL_E_OVERFLOW (calls of other functions in
+   between are not looked at: none of them touches the kept nodes).  ecl_hip_selftest of such a context also runs
+   both derivation kernels on BIP39's test phrase (ECL_E_SELFTEST). */
 #define ECL_ADDR33 1u
 #define ECL_ADDR65 2u
 #define ECL_ENDO 4u
@@ -181,6 +202,7 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
 #define ECL_KDF_KECCAK 0x4000u /* 16384 */
 #define ECL_KDF_SHA3 0x8000u   /* 32768 */
 #define ECL_KDF_CAMP2 0xC000u  /* both: the two bits are one field */
+#define ECL_KDF_BIP39 0x10000u /* 65536 */
 
 /* return codes */
 #define ECL_OK 0

@@ -26,6 +26,7 @@ usage: tools/isa_mix.py [file.s] [mangled kernel name] [--json]     |     tools/
        tools/isa_mix.py --bsgs  (the kernels `bsgs` adds: the insert walk beside -a x's from the same assembly, the origin set-up kernel)
        tools/isa_mix.py --kangaroo  (the herd walk of `kangaroo`: registers, the two per-kangaroo loops, a jump's static count and the inversion's share by M)
        tools/isa_mix.py --splitkey  (the two verification kernels of the split-key search: registers, spills, static VALU count, scratch in the window loop)
+       tools/isa_mix.py --seed  (the two kernels of `seed`: registers, the PBKDF2 iteration loop's static mix, code size, scratch and issue-cycle floor)
        tools/isa_mix.py --compare other.s [file.s]  (every kernel of both assemblies: instruction mix, registers, spills, LDS, scratch, kernarg size; which differ, which are new)"""
 import json
 import os
@@ -421,6 +422,49 @@ SPLITKEY_KERNELS = {"verify origin": "_Z15k_verify_originPKjjS0_PjS1_Ph", "verif
 SPLITKEY_MIRRORS = {"verify origin": "_Z8k_verifyPKjjS0_PjS1_Ph", "verify origin eth": "_Z12k_verify_ethPKjjS0_PjPh"}
 
 
+# the kernels `seed` adds (ECL_KDF_BIP39): the master stage (PBKDF2-HMAC-SHA512 + the master node) and the path stage (CKDpriv)
+SEED_KERNELS = {"master": "_Z14k_bip39_masterPKjjPKmj10bip39_saltPj", "path": "_Z12k_bip32_pathPKjj10bip32_pathS0_Pj"}
+SEED_ROUND_PASSES = 4      # a compression's rounds 16..79: four passes over the body of 16
+SEED_ITERATIONS = 2047     # of the loop (PBKDF2's 2048 minus U_1)
+SEED_CLOCKS = {"fast": 2.4, "other": 4.1}  # DESIGN section 4's measured issue clocks per wave instruction
+SEED_SIMDS, SEED_HZ = 1024, 2.4e9
+
+
+def analyse_seed(path=ASM):
+    """k_bip39_master's iteration loop - the depth-1 loop that holds two round loops, one per compression of an HMAC - and what an iteration
+    executes: its own body once and each round loop four times.  Its instructions are at most 8 bytes each (gfx950 has no literal in VOP3), which
+    bounds the loop's code size.  The issue-cycle floor as DESIGN (f14) computed camp2's: the loop's VALU mix at 2.4 / 4.1 clocks, 64
+    phrases a wave, 1024 SIMDs at 2.4 GHz.  Beside it the registers of both kernels."""
+    meta = kernel_meta(path)
+    k = SEED_KERNELS["master"]
+    bl, _ = blocks(path, k)
+    parent, depth = loop_tree(path, k)
+    excl = {h: zero() for h in parent}
+    ninstr = {h: 0 for h in parent}
+    for b in bl:
+        if b["header"] in excl:
+            for key in KEYS:
+                excl[b["header"]][key] += b["c"][key]
+            ninstr[b["header"]] += sum(b["c"][x] for x in ("valu", "salu", "smem", "vmem", "lds", "scratch"))
+    kids = {h: [c for c in parent if parent[c] == h] for h in parent}
+    cands = [h for h in parent if depth[h] == 1 and len(kids[h]) == 2 and not excl[h]["vmem"]]
+    r = {"master": {"kernel": k, "registers": meta.get(k), "loops": len(parent)}, "path": {"kernel": SEED_KERNELS["path"], "registers": meta.get(SEED_KERNELS["path"])}}
+    if len(cands) == 1:
+        L = cands[0]
+        dyn = {x: excl[L][x] + SEED_ROUND_PASSES * sum(excl[c][x] for c in kids[L]) for x in ("valu", "fast", "other", "mad64", "salu", "smem")}
+        clocks = dyn["fast"] * SEED_CLOCKS["fast"] + (dyn["other"] + dyn["mad64"]) * SEED_CLOCKS["other"]
+        per_phrase = clocks * SEED_ITERATIONS / 64.0
+        r["master"]["iteration_loop"] = {
+            "header": L, "own": {x: excl[L][x] for x in ("valu", "fast", "other", "scratch", "vmem", "lds")},
+            "round_loops": [{x: excl[c][x] for x in ("valu", "fast", "other", "scratch", "vmem", "lds", "smem")} for c in sorted(kids[L])],
+            "scratch": excl[L]["scratch"] + excl[L]["scratch_at_calls"] + sum(excl[c]["scratch"] + excl[c]["scratch_at_calls"] for c in kids[L]),
+            "calls": excl[L]["call"] + sum(excl[c]["call"] for c in kids[L]),
+            "instructions": ninstr[L] + sum(ninstr[c] for c in kids[L]), "code_bytes_max": 8 * (ninstr[L] + sum(ninstr[c] for c in kids[L])),
+            "per_iteration": dyn, "valu_per_compression": dyn["valu"] / 2.0, "clocks_per_iteration": round(clocks, 1),
+            "floor_phrases_per_s": round(SEED_SIMDS * SEED_HZ / per_phrase)}
+    return r
+
+
 def kernel_meta(path=ASM):
     """name -> the code object's metadata of every kernel: register counts, spill counts, scratch, LDS and kernarg sizes"""
     s = open(path).read()
@@ -527,6 +571,10 @@ def main():
     if "--splitkey" in sys.argv:
         rest = [a for a in sys.argv[1:] if not a.startswith("--")]
         print(json.dumps(analyse_splitkey(rest[0] if rest else ASM), indent=1))
+        return
+    if "--seed" in sys.argv:
+        rest = [a for a in sys.argv[1:] if not a.startswith("--")]
+        print(json.dumps(analyse_seed(rest[0] if rest else ASM), indent=1))
         return
     if "--compare" in sys.argv:
         rest = [a for a in sys.argv[1:] if not a.startswith("--")]
