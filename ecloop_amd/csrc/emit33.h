@@ -18,14 +18,32 @@
 //     words: one v_perm_b32 and one and-or per half, instead of four byte swaps and the 64-bit shifts.  The h160_t byte order is applied
 //     where a record is parked in the ring (cand_push), not before;
 //   * y of a walked point is lam b - Y (b = X - x3), and of that product the parity formula above reads bit 0 of limb 0, the top five
-//     bits of limb 7 and limb 8.  emit33_ypar runs fe_mul's two streams for those alone: the d stream (columns 8..16) whole, the c stream
-//     from column 6 on, started at u_5 R1 - what column 5 hands up less its carry x = c_5 >> 29.  No product of columns 0..5 (21), no
-//     u_k R0 for k <= 5, no u_k R1 for k <= 4, nothing of the tail past limb 8.
-//       - Every column sum of fe_mul is below 2^64 (fe256.h), so x < 2^35.  Column 6 comes out low by x, its carry into column 7 low by
-//         e, 0 <= e <= (x >> 29) + 1 <= 64, and so does c7, the sum of column 7 before it is masked.  Of c7 only bits >= 24 are read
+//     bits of limb 7 and limb 8.  emit33_ypar runs fe_mul's two streams for those alone.  Of the d stream: column 8 for its digit t8
+//     (it has no carry-in, and its carry-out is not used), then columns 13..16 (k = K0 = 4 .. 7) started with no carry-in; of their
+//     digits u_4 is thrown away, u_5, u_6, u_7 and the last carry dd are used.  Of the c stream: column 6 on, started at u_5 R1 - what
+//     column 5 hands up less its carry x = c_5 >> 29.  No product of columns 9..12 (26) nor of columns 0..5 (21), no u_k R0 for
+//     k <= 5, no u_k R1 for k <= 4, nothing of the tail past limb 8.  The operands are the walk's: a = lam of magnitude 1, b of
+//     magnitude <= 6 (fe256.h: a_i <= A = 2^29 + 449, a_8 <= T = 2^24 + 449, b_i <= 6 A, b_8 <= 6 T); every column sum grows with
+//     every limb, so its ceiling is its value with all limbs at theirs.
+//       - The late start of the d stream.  Column 12 is five products, three of them <= 6 A^2 and two <= 6 A T, and the carry it takes
+//         from column 11 (six products) is below 24.4 * 2^29: its sum is below 18.376 * 2^58 + 2^34, and what it hands to column 13 is
+//         x13 < 18.4 * 2^29.  That is all the truncated column 13 lacks, so the carry it hands to column 14 is low by f,
+//         0 <= f <= (x13 >> 29) + 1 <= 19, and column 14's sum D_5 is low by f and by nothing else.  Its digit u_5 = D_5 mod 2^29 comes
+//         out as u_5 - f, and the carry into column 15 - with it u_6, u_7 and dd - is the true one, unless u_5 < f; and then the
+//         truncated digit is u_5 - f + 2^29 >= 2^29 - 19.  One compare of the truncated digit, >= 2^29 - F with F = 32 >= 19, selects
+//         the exact product (2^-24 per key); below it u_6, u_7 and dd are the true ones and u_5 is the true one less f.  No error goes
+//         unguarded: u_6 and u_7 reach limb 8 through R1, and only the compare stands between a borrowed column 14 and a wrong parity.
+//         (A start one column earlier, K0 = 3, lacks x12 < 24.4 * 2^29 in column 12, at most 25 in column 13 and at most 1 in column
+//         14: a guard two values wide, but five more products per key.  A start one column later leaves u_5 itself without its
+//         carry-in, x14 up to 12.4 * 2^29: no digit of it would be known.  K0 = 4 is the latest start that closes.)
+//       - The late start of the c stream.  The low u_5 enters column 6 alone, as u_5 R1 = 256 (u_5 - f), beside the x that column
+//         lacks already.  c_5 is six products <= 6 A^2 each, u_4 R1 + u_5 R0 < 2^45 and a carry below 2^35: c_5 < 36.001 * 2^58 and
+//         x < 36.001 * 2^29.  Column 6 comes out low by x' = x + 256 f < 36.001 * 2^29 + 4864, its carry into column 7 low by e,
+//         0 <= e <= (x' >> 29) + 1 <= 37 (64 is the bound the host program refuses to see exceeded), and so does c7, the sum of column
+//         7 before it is masked.  Of c7 only bits >= 24 are read
 //         (limb 7's top five bits, and the carry into limb 8 with all that follows from it: limb 8, and ct = c >> 24 of the tail), and
 //         those are the true ones unless (c7 mod 2^24) + e reaches 2^24: (c7 mod 2^24) >= 2^24 - G with G = 256 >= 65 selects the exact
-//         product (2^-16 per key); below it the low 24 bits of c7 are the true ones less e, no more.
+//         product (2^-16 per key); below it the low 24 bits of c7 are the true ones less e, no more.  G stays as it was.
 //       - Bit 0 of the product's limb 0, ((a0 b0 + u_0 R0) mod 2^29 + (ct + d 2^13) 977) mod 2^29, is (a0 & b0 ^ ct) & 1: R0 and d 2^13
 //         are even, 977 is odd.  y = product + 2p - Y limb-wise (fe_sub): bit 0 flips with Y's, limbs 7 and 8 get 2 p_i - Y_i.
 //       - Limb 7 of y is low by e as well, so the estimate A of the item above is floor(S / 2^227) less 0, 1 or 2 here: k = A >> 29
@@ -91,10 +109,13 @@ FE_FN u32 emit33_parity(const fe& y) {
   return (y.n[0] ^ (A >> 29)) & 1u;
 }
 // parity of the canonical residue of a b - Y by the short way alone (a: magnitude 1, b: magnitude <= 6, Y: magnitude 1), and in `rare`
-// whether it may be relied on: 0, or 1 where the guard or the test on A asks for the exact product.  fe_mul's schedule with the c stream
-// started at column 6; c7_out (if asked for) gets the low word of column 7's truncated sum, for the tests
+// whether it may be relied on: 0, or 1 where one of the two guards or the test on A asks for the exact product.  fe_mul's schedule with
+// the d stream started at column 13 and the c stream at column 6; c7_out and u5_out (if asked for) get the low word of column 7's
+// truncated sum and column 14's truncated digit, for the tests
 #define EMIT33_YPAR_G 256u
-FE_FN u32 emit33_ypar_short(const fe& a, const fe& b, const fe& Y, u32& rare, u32* c7_out = nullptr) {
+#define EMIT33_YPAR_K0 4   /* the d stream starts at column 9 + K0 = 13 */
+#define EMIT33_YPAR_F 32u  /* guard on column 14's truncated digit: >= 19, the most its carry-in can lack */
+FE_FN u32 emit33_ypar_short(const fe& a, const fe& b, const fe& Y, u32& rare, u32* c7_out = nullptr, u32* u5_out = nullptr) {
   u64 c = 0, d = 0;
   const u32 R1 = fe_opaque(FE_R1);
 #pragma unroll
@@ -102,19 +123,20 @@ FE_FN u32 emit33_ypar_short(const fe& a, const fe& b, const fe& Y, u32& rare, u3
     FE_PIN64(d);
     d += (u64)a.n[i] * b.n[8 - i];
   }
-  const u32 t8 = (u32)d & FE_M;
-  d >>= 29;
-  u32 c7 = 0;
+  const u32 t8 = (u32)d & FE_M;  // column 8 has no carry-in: its digit is exact, its carry goes with the skipped columns
+  u32 c7 = 0, u5 = 0;
 #pragma unroll
-  for (int k = 0; k < 8; ++k) {
+  for (int k = EMIT33_YPAR_K0; k < 8; ++k) {
+    if (k == EMIT33_YPAR_K0) d = (u64)a.n[k + 1] * b.n[8];  // (no carry-in)
 #pragma unroll
-    for (int i = k + 1; i < 9; ++i) {
+    for (int i = k + 1 + (k == EMIT33_YPAR_K0); i < 9; ++i) {
       FE_PIN64(d);
       d += (u64)a.n[i] * b.n[9 + k - i];
     }
     const u32 u = (u32)d & FE_M;
     d >>= 29;
-    if (k < 5) continue;  // u_0..u_4: shifted out, not used
+    if (k < 5) continue;  // u_4: shifted out, not used
+    if (k == 5) u5 = u;
     if (k > 5) {
 #pragma unroll
       for (int i = 0; i <= k; ++i) {
@@ -137,7 +159,8 @@ FE_FN u32 emit33_ypar_short(const fe& a, const fe& b, const fe& Y, u32& rare, u3
   const u32 y8 = ((u32)c & FE_TOP) + (2u * FE_P8 - Y.n[8]);
   const u32 A = (y8 << 5) + (y7 >> 24);
   if (c7_out) *c7_out = c7;
-  rare = ((c7 & FE_TOP) >= (1u << 24) - EMIT33_YPAR_G) | ((A & FE_M) >= FE_M - 2u);
+  if (u5_out) *u5_out = u5;
+  rare = (u5 >= (1u << 29) - EMIT33_YPAR_F) | ((c7 & FE_TOP) >= (1u << 24) - EMIT33_YPAR_G) | ((A & FE_M) >= FE_M - 2u);
   return ((a.n[0] & b.n[0]) ^ ct ^ Y.n[0] ^ (A >> 29)) & 1u;
 }
 // parity of the canonical residue of y = lam b - Y for a walked point: lam a product (magnitude 1), b = X - x3 (magnitude <= 6), Y

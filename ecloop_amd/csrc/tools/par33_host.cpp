@@ -4,6 +4,7 @@
 // Not part of the product library.  It has its own main, so a sanitizer build of the device headers goes here as well:
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all par33_host.cpp -o par33_host && ./par33_host
 // usage: par33_host [cases.bin [log2 of the random cases, default 22]]
+//        par33_host -late [cases.bin [log2 of the random cases, default 22]]   (the late start of the d stream: sets 11..14 below)
 // Operands at the magnitudes of the walk (add_walk.inc): lam magnitude 1, b magnitude 6, Y magnitude 1, ceilings as fe256.h defines them
 // (2^29 + 449 per unit, limb 8: 2^24 + 449).  Four sets:
 //   1  seeded random operand sets (a quarter of them with b's limbs at 0 or the ceiling);
@@ -15,8 +16,22 @@
 //      guarded function the right one;
 //   5  four sets whose dropped carry crosses a multiple of 2^29 in column 7 with A far from any boundary: the guard alone sends them the
 //      exact way (see search_cross29 for what the short way gives there).
-// The search for sets 3 and 4 walks lam's limb 0 over a model of the truncated column 7 (column sums kept, three products per step);
-// every case it keeps is confirmed on emit33_ypar_short itself.
+// The search for sets 3 and 4 walks lam's limb 0 over a model of the truncated column 7 (column sums kept, three products per step; the
+// d stream from column 13 on, as emit33_ypar_short runs it); every case it keeps is confirmed on emit33_ypar_short itself.
+// -late checks the start of the d stream at column 13 (EMIT33_YPAR_K0 = 4) and its guard on column 14's truncated digit u5, with sets
+// of its own, lines of its own ("par33_host: late: ...") and records of its own:
+//   11 seeded random operand sets (another seed), the share by the exact path and by the new guard reported;
+//   12 limbs 4..8 of both factors at 0 or the ceiling in every one of the 1024 patterns (the skipped columns 9..12 at their largest),
+//      two fillings of the lower limbs each;
+//   13 at least 256 sets whose truncated digit lies in [2^29 - F, 2^29) (all must take the exact path) and at least 256 in
+//      [2^29 - 2 F, 2^29 - F) (none may);
+//   14 at least 64 sets on which the late start gives a wrong u_6 (checked: column 14 borrows from column 15); the guarded function
+//      is right on them.
+//   On every set of 11..14: the carry the late start lacks in column 14 is f <= 19; where the guard does not fire the digit is the true
+//   one less f, u_6, u_7 and the last carry are the true ones, and column 7 comes out low by e <= 64.
+//   Limbs 0 and 1 do not reach columns 13 and 14, so there is no walk over them to the new guard.  Sets 13 and 14 are solved for instead:
+//   one limb of the three products of column 14 is the unknown (lam_7, b_7 or b_6), the limb that would carry it into column 13 is zero
+//   (b_6, lam_6 or lam_7), so column 14's sum is linear in it mod 2^29, and the other factor is odd: one modular inverse per set.
 // Exit status 0 and a line "par33_host: <n> cases ok ..." with the number of cases by path; the first mismatch is printed, status 1.
 // cases.bin gets u32 n, then n x (lam[9], b[9], Y[9], parity, path, set): sets 2..5 whole and the first 4096 of set 1, for the device test.
 #include "../emit33.h"
@@ -159,12 +174,11 @@ static bool check(const fe& lam, const fe& b, const fe& Y, u32 set, bool keep, u
 
 // ---- sets 3 and 4: the search.  Column sums of lam b without lam's limb 0 (the products it enters, a0 b6, a0 b7, a0 b8, are added per step)
 struct colsums {
-  u64 s8, s[8], c6, c7;  // column 8, columns 9..16, columns 6 and 7
+  u64 s[8], c6, c7;  // columns 9..16 (lam's limb 0 enters none of them), columns 6 and 7
 };
 static colsums sums_without_a0(const fe& a, const fe& b) {
   colsums r;
   memset(&r, 0, sizeof r);
-  for (int i = 1; i < 9; ++i) r.s8 += (u64)a.n[i] * b.n[8 - i];
   for (int k = 0; k < 8; ++k)
     for (int i = k + 1; i < 9; ++i) r.s[k] += (u64)a.n[i] * b.n[9 + k - i];
   for (int i = 1; i <= 6; ++i) r.c6 += (u64)a.n[i] * b.n[6 - i];
@@ -172,9 +186,9 @@ static colsums sums_without_a0(const fe& a, const fe& b) {
   return r;
 }
 static u32 model_c7(const colsums& s, u32 a0, const fe& b) {
-  u64 d = (s.s8 + (u64)a0 * b.n[8]) >> 29, c = 0;
+  u64 d = 0, c = 0;
   u32 u[8];
-  for (int k = 0; k < 8; ++k) {
+  for (int k = EMIT33_YPAR_K0; k < 8; ++k) {  // the late start: no carry-in
     d += s.s[k];
     u[k] = (u32)d & FE_M;
     d >>= 29;
@@ -203,6 +217,12 @@ static u64 full_c7(const fe& a, const fe& b) {
   }
   return 0;
 }
+// does the guard on column 14's truncated digit fire?  (lam's limb 0 has no part in it.)  Column 7's error bound holds only below it
+static bool late_guard(const fe& lam, const fe& b) {
+  u32 rare, u5 = 0;
+  emit33_ypar_short(lam, b, fe_zero(), rare, nullptr, &u5);
+  return u5 >= (1u << 29) - EMIT33_YPAR_F;
+}
 static fe magnitude1_y() {
   fe Y = element(1, 0);
   return Y;
@@ -213,6 +233,7 @@ static bool search_sets() {
     if (round >= (1u << 18)) return printf("par33_host: the search found %zu inside, %zu below, %zu wrong cases only\n", inside, under, wrong), false;
     fe lam = element(1, 0);
     const fe b = element(6, round & 1 ? 2 : 0);  // every other round: b at its ceiling, the largest dropped carries
+    if (late_guard(lam, b)) continue;  // (2^-24)
     const colsums s = sums_without_a0(lam, b);
     const u32 a0 = below((1u << 29) - 1024);
     for (u32 step = 0; step < 1024; ++step) {
@@ -270,6 +291,7 @@ static bool search_cross29() {
     if (round >= (1u << 16)) return printf("par33_host: the search found %zu sets that cross 2^29 only\n", found), false;
     fe lam = element(1, 0);
     const fe b = element(6, 2);
+    if (late_guard(lam, b)) continue;
     const colsums s = sums_without_a0(lam, b);
     const u32 a0 = below((1u << 29) - (1u << 16));
     for (u32 step = 0; step < (1u << 16) && found < 4; ++step) {
@@ -301,7 +323,138 @@ static bool search_cross29() {
   return true;
 }
 
+// ---- -late: the d stream from column 13 on and the guard on column 14's truncated digit (sets 11..14)
+static const u32 F = EMIT33_YPAR_F, F_MOST = 19;  // the guard's width; the most the carry into column 14 may lack (emit33.h)
+struct dstream {
+  u32 u[8];      // the digits of columns 9..16
+  u64 carry[8];  // what each hands up
+};
+// fe_mul's d stream from column 9 + k0 on with no carry-in (k0 < 0: the whole stream, with column 8's carry)
+static dstream d_digits(const fe& a, const fe& b, int k0) {
+  dstream r;
+  memset(&r, 0, sizeof r);
+  u64 d = 0;
+  if (k0 < 0) {
+    for (int i = 0; i < 9; ++i) d += (u64)a.n[i] * b.n[8 - i];
+    d >>= 29;
+  }
+  for (int k = k0 < 0 ? 0 : k0; k < 8; ++k) {
+    for (int i = k + 1; i < 9; ++i) d += (u64)a.n[i] * b.n[9 + k - i];
+    r.u[k] = (u32)d & FE_M;
+    d >>= 29;
+    r.carry[k] = d;
+  }
+  return r;
+}
+static size_t late_guarded = 0, late_largest_f = 0, late_largest_e = 0, late_borrows = 0;
+// one operand set of the late mode: what emit33.h derives for the late start, then the three parities.  borrowed (if asked for): whether
+// the late start alone gives a wrong u_6
+static bool late_check(const fe& lam, const fe& b, const fe& Y, u32 set, bool keep, u32* path_out = nullptr, bool* borrowed = nullptr) {
+  const dstream t = d_digits(lam, b, -1), s = d_digits(lam, b, EMIT33_YPAR_K0);
+  const u64 f = t.carry[4] - s.carry[4];
+  if (f > F_MOST) return show("column 14 lacks more than 19", lam, b, Y), false;
+  if (f > late_largest_f) late_largest_f = f;
+  u32 rare, c7 = 0, u5 = 0;
+  emit33_ypar_short(lam, b, Y, rare, &c7, &u5);
+  if (u5 != s.u[5]) return show("the model of the late start disagrees with emit33_ypar_short", lam, b, Y), false;
+  const bool fires = u5 >= (1u << 29) - F, wrong6 = s.u[6] != t.u[6];
+  if (fires && !rare) return show("inside the guard on column 14, but not flagged", lam, b, Y), false;
+  if (wrong6 && (!fires || t.u[5] >= f || s.u[5] != t.u[5] + (1u << 29) - (u32)f || s.carry[5] + 1 != t.carry[5]))
+    return show("a wrong u_6 that is no borrow of column 14 under the guard", lam, b, Y), false;
+  if (!wrong6) {
+    if (s.u[5] + (u32)f != t.u[5] || s.u[7] != t.u[7] || s.carry[7] != t.carry[7]) return show("the late start is wrong past u_5 - f", lam, b, Y), false;
+    const u32 e = (u32)full_c7(lam, b) - c7;
+    if (e > 64) return show("the carry error of column 7 is outside [0, 64]", lam, b, Y), false;
+    if (e > late_largest_e) late_largest_e = e;
+  }
+  late_guarded += fires, late_borrows += wrong6;
+  if (borrowed) *borrowed = wrong6;
+  return check(lam, b, Y, set, keep, path_out);
+}
+static u32 inverse29(u32 x) {  // of an odd x mod 2^29
+  u32 r = x;
+  for (int i = 0; i < 5; ++i) r *= 2u - x * r;
+  return r & FE_M;
+}
+// sets 13 and 14: operand sets whose truncated digit of column 14 is `target`
+static bool late_solve(fe& lam, fe& b, u32 target, int knob) {
+  u32 *zero = knob == 0 ? &b.n[6] : knob == 1 ? &lam.n[6] : &lam.n[7], *x = knob == 0 ? &lam.n[7] : knob == 1 ? &b.n[7] : &b.n[6];
+  u32* by = knob == 0 ? &b.n[7] : knob == 1 ? &lam.n[7] : &lam.n[8];
+  *zero = 0, *x = 0;
+  if (!(*by & 1u)) *by = *by ? *by - 1 : 1u;  // odd, and still under its ceiling
+  const u32 now = d_digits(lam, b, EMIT33_YPAR_K0).u[5];
+  *x = (u32)(((u64)((target - now) & FE_M) * inverse29(*by)) & FE_M);
+  if (knob) *x += below(6) << 29;  // b's limbs: magnitude 6
+  return d_digits(lam, b, EMIT33_YPAR_K0).u[5] == target;
+}
+static bool late_sets() {
+  size_t inside = 0, under = 0, wrong = 0;
+  for (u64 round = 0; inside < 256 || under < 256 || wrong < 64; ++round) {
+    if (round >= (1u << 16)) return printf("par33_host: late: the search found %zu inside, %zu below, %zu wrong cases only\n", inside, under, wrong), false;
+    fe lam = element(1, 0), b = element(6, round & 1 ? 2 : 0);  // every other round: b at its ceiling, the largest missing carries
+    const int want = (int)(round % 3);                          // 0: inside, 1: just below, 2: the top two values of the digit (a borrow where f > 1)
+    const u32 target = want == 2 ? FE_M - below(2) : (1u << 29) - (want ? 2 * F : F) + below(F);
+    if (!late_solve(lam, b, target, (int)((round / 3) % 3))) return show("late_solve missed its target", lam, b, fe_zero()), false;
+    const fe Y = element(1, 0);
+    u32 rare, u5 = 0, path;
+    emit33_ypar_short(lam, b, Y, rare, nullptr, &u5);
+    if (u5 != target) return show("the model of the late start disagrees with emit33_ypar_short", lam, b, Y), false;
+    if (want == 1 && rare) continue;  // (another test fired beside the guard: 2^-16)
+    bool borrowed;
+    if (want == 2) {
+      if (wrong >= 128) continue;
+      if (d_digits(lam, b, -1).u[6] == d_digits(lam, b, EMIT33_YPAR_K0).u[6]) continue;  // (f was 0 or 1: no borrow)
+      if (!late_check(lam, b, Y, 14, true, &path, &borrowed)) return false;
+      if (!borrowed || path != 1) return show("set 14, but no wrong u_6 or not the exact path", lam, b, Y), false;
+      ++wrong;
+      continue;
+    }
+    if (!late_check(lam, b, Y, 13, true, &path, &borrowed)) return false;
+    if (path != (want ? 0u : 1u)) return show(want ? "below the guard on column 14, but the exact path" : "inside the guard on column 14, but not the exact path", lam, b, Y), false;
+    want ? ++under : ++inside;
+  }
+  printf("par33_host: late: search: %zu inside the guard, %zu just below, %zu where the late start alone gives a wrong u_6\n", inside, under, wrong);
+  return true;
+}
+static int late_main(const char* out, int lg) {
+  rng_state = 0x1A7E57A87ull;
+  // set 11
+  const size_t n1 = (size_t)1 << lg;
+  for (size_t i = 0; i < n1; ++i)
+    if (!late_check(element(1, 0), element(6, (i & 3) == 3 ? 1 : 0), element(1, 0), 11, i < 1024)) return 1;
+  printf("par33_host: late: set 11: %zu random cases, %zu by the exact path, %zu of them inside the guard on column 14\n", n1, n_path[1], late_guarded);
+  if (n_path[1] * 4096 > n1) return printf("par33_host: late: more than one case in 2^12 by the exact path\n"), 1;
+  // set 12
+  for (u32 pat = 0; pat < 1024; ++pat)
+    for (int rep = 0; rep < 2; ++rep) {
+      fe lam = element(1, rep ? 2 : 0), b = element(6, rep ? 2 : 0);
+      for (int i = 0; i < 5; ++i) {
+        lam.n[4 + i] = (pat >> i) & 1u ? ceil_of(4 + i, 1) : 0u;
+        b.n[4 + i] = (pat >> (5 + i)) & 1u ? ceil_of(4 + i, 6) : 0u;
+      }
+      if (!late_check(lam, b, element(1, rep ? 0 : 2), 12, true)) return 1;
+    }
+  printf("par33_host: late: set 12: 1024 patterns of limbs 4..8; column 14 lacks at most %zu so far, column 7 at most %zu\n", late_largest_f, late_largest_e);
+  if (late_largest_f + 1 < F_MOST) return printf("par33_host: late: the patterns do not reach the ceiling in column 14 (18 or 19)\n"), 1;
+  // sets 13 and 14
+  if (!late_sets()) return 1;
+  if (out) {
+    FILE* f = fopen(out, "wb");
+    const u32 n = (u32)kept.size();
+    if (!f || fwrite(&n, 4, 1, f) != 1 || fwrite(kept.data(), sizeof(rec), n, f) != n) return printf("par33_host: cannot write %s\n", out), 2;
+    fclose(f);
+  }
+  printf("par33_host: late: largest carry lacking in column 14 %zu, in column 7 %zu; %zu sets with a wrong u_6 by the late start alone\n", late_largest_f, late_largest_e, late_borrows);
+  printf("par33_host: late: %zu cases ok, %zu by the short way, %zu by the exact path\n", n_cases, n_path[0], n_path[1]);
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc >= 2 && !strcmp(argv[1], "-late")) {
+    const int lg = argc == 4 ? atoi(argv[3]) : 22;
+    if (argc > 4 || lg < 12 || lg > 30) return printf("usage: par33_host -late [cases.bin [log2 of the random cases, 12 .. 30]]\n"), 2;
+    return late_main(argc >= 3 ? argv[2] : nullptr, lg);
+  }
   if (argc > 3) return printf("usage: par33_host [cases.bin [log2 of the random cases]]\n"), 2;
   const int lg = argc == 3 ? atoi(argv[2]) : 22;
   if (lg < 12 || lg > 30) return printf("par33_host: log2 of the random cases: 12 .. 30\n"), 2;
