@@ -374,6 +374,23 @@ class FoundRecord:
             ("" if self.split is None else " split:%d" % self.split) + ("" if self.path is None else " %s %s" % (self.path, self.phrase.decode("latin-1")))
 
 
+def collect_records(call, dev, cap, short=None):
+    """All records of one device call: the caller's half of the overflow protocol (include/ecloop_hip.h).  call(cap) makes the call with a
+    buffer of `cap` records -> (records, total).  Where total > cap (dense filters only) the device kept up to max(cap, 2^20) records of
+    the call and the rest is read from there; only if it kept fewer than the call produced is the call made again with a buffer that fits -
+    or, for a caller that cannot repeat its call, EclError(short) raised."""
+    while True:
+        raw, total = call(cap)
+        if total <= cap:
+            return raw
+        rest = dev.fetch_found(cap, total - cap)
+        if len(rest) == total - cap:
+            return np.concatenate([raw, rest])
+        if short:
+            raise EclError(short)
+        cap = total
+
+
 class KeySearch:
     """ctx_t + cmd_add / cmd_mul for one GPU."""
 
@@ -393,34 +410,21 @@ class KeySearch:
         self.tr = tr  # Taproot output keys (BIP341 / BIP86 key path): records labelled "p2tr", h160 = the leading 20 bytes of the key
         self.pub = pub  # public keys by x: records labelled "pub", h160 = the leading 20 bytes of x
         self.stride = 1 << ord_offs
-        # device_cls: the GPU context (capi.Device); the CPU tests of the host logic pass a stand-in with the same surface
-        kw = {"p2sh": True} if p2sh else {}  # (a stand-in without the P2SH type keeps working for the other types)
-        if eth:
-            kw["eth"] = True
-        if tr:
-            kw["tr"] = True
-        if pub:
-            kw["pub"] = True
-        if prefix:  # flt: a PrefixFilter - the range table stands where the bloom words stand (prefix_search)
-            kw["prefix"] = True
-        if mask:  # flt: a MaskFilter - the mask table stands where the bloom words stand (prefix_search with a ? or * pattern)
-            kw["mask"] = True
         if kdf not in (None,) + KDF_NAMES:
             raise ValueError("kdf is None, 'sha256', 'keccak', 'sha3' or 'camp2'")
         self.kdf = None if kdf == "sha256" else kdf  # the hash of cmd_mul_raw (kdf_digest); None: SHA-256
-        if self.kdf:
-            kw["kdf"] = self.kdf
         self.bip39 = bool(bip39)  # the context of cmd_seed: the lines of mul_batch_raw are BIP39 phrases
-        if bip39:
-            if self.kdf:  # ("sha256" is no kdf: None by now)
-                raise ValueError("bip39 does not go with a kdf")
-            kw["bip39"] = True
-        self.origin = None  # split-key search (prefix_search(origin=)): the walk is O + k G, the records' keys are partial keys
-        if origin is not None:
-            if not (prefix or mask):
-                raise ValueError("an origin goes with the prefix search only (prefix_search(origin=(x, y)))")
-            self.origin = (int(origin[0]), int(origin[1]))
-            kw["origin"] = True
+        if bip39 and self.kdf:  # ("sha256" is no kdf: None by now)
+            raise ValueError("bip39 does not go with a kdf")
+        if origin is not None and not (prefix or mask):
+            raise ValueError("an origin goes with the prefix search only (prefix_search(origin=(x, y)))")
+        # split-key search (prefix_search(origin=)): the walk is O + k G, the records' keys are partial keys
+        self.origin = None if origin is None else (int(origin[0]), int(origin[1]))
+        # device_cls: the GPU context (capi.Device); the CPU tests of the host logic pass a stand-in with the same surface, which need not know
+        # the types it is not asked for: a flag is passed only when set.  prefix / mask: flt is a PrefixFilter / MaskFilter, whose table
+        # stands where the bloom words stand (prefix_search)
+        kw = {name: value for name, value in dict(p2sh=bool(p2sh), eth=bool(eth), tr=bool(tr), pub=bool(pub), prefix=bool(prefix), mask=bool(mask),
+                                                  kdf=self.kdf, bip39=self.bip39, origin=origin is not None).items() if value}
         self.dev = (device_cls or Device)(device, a33=a33, a65=a65, endo=endo, ord_offs=ord_offs, **kw)
         if half_group or max_lanes:
             self.dev.set_geometry(half_group, max_lanes)
@@ -440,98 +444,67 @@ class KeySearch:
     def close(self):
         self.dev.close()
 
-    # pk_verify_hash (main.c:248-263): re-derive the hit from its scalar by the window-table sum (not the walk kernel;
-    # the self-test of the context pins that sum against the double-and-add kernel)
-    def _verify(self, recs):
-        if not recs:
-            return
-        if self.origin is not None:  # image e of O + k G is O' + k' G: k' = the record's partial key, O' the same image of O
-            orgs = [splitkey_image_origin(self.origin, r.split) for r in recs]
-            if self.eth:
-                h33, ok = self.dev.verify_eth([r.pk for r in recs], origin=orgs)
-                h65 = h33
-            else:
-                h33, h65, ok = self.dev.verify([r.pk for r in recs], origin=orgs)
-            for i, r in enumerate(recs):
-                h = h65[i] if r.label == "addr65" else h33[i]
-                if not ok[i] or [int(v) for v in h] != [int(v) for v in r.h160]:
-                    raise EclError("[!] error: hash mismatch (%s) pk: %064x" % (r.label, r.pk))
-            return
-        tr = [r for r in recs if r.label == "p2tr"]
-        if tr:  # the first 20 bytes of the re-derived output key against the record, which then carries all 32
-            qx, ok = self.dev.verify_tr([r.pk for r in tr])
-            for i, r in enumerate(tr):
-                if not ok[i] or [int(v) for v in qx[i][:5]] != [int(v) for v in r.h160[:5]]:
-                    raise EclError("[!] error: hash mismatch (%s) pk: %064x" % (r.label, r.pk))
-                r.h160 = [int(v) for v in qx[i]]
-            recs = [r for r in recs if r.label != "p2tr"]
-            if not recs:
-                return
-        pub = [r for r in recs if r.label == "pub"]
-        if pub:  # the first 20 bytes of the x of the key's point (double-and-add kernel) against the record, which then carries the whole key
-            x, par, ok = self.dev.verify_pub([r.pk for r in pub])
-            for i, r in enumerate(pub):
-                if not ok[i] or [int(v) for v in x[i][:5]] != [int(v) for v in r.h160[:5]]:
-                    raise EclError("[!] error: hash mismatch (%s) pk: %064x" % (r.label, r.pk))
-                r.h160, r.prefix = [int(v) for v in x[i]], "%02x" % (2 | int(par[i]))
-            recs = [r for r in recs if r.label != "pub"]
-            if not recs:
-                return
-        eth = [r for r in recs if r.label == "eth"]
-        if eth:
-            addr, ok = self.dev.verify_eth([r.pk for r in eth])
-            for i, r in enumerate(eth):
-                if not ok[i] or [int(v) for v in addr[i]] != [int(v) for v in r.h160]:
-                    raise EclError("[!] error: hash mismatch (%s) pk: %064x" % (r.label, r.pk))
-            recs = [r for r in recs if r.label != "eth"]
-            if not recs:
-                return
-        h33, h65, ok = self.dev.verify([r.pk for r in recs])
-        hsh = self.dev.p2sh_hash(h33) if any(r.label == "p2sh" for r in recs) else None
-        for i, r in enumerate(recs):
-            h = hsh[i] if r.label == "p2sh" else h33[i] if r.label == "addr33" else h65[i]
-            if not ok[i] or [int(v) for v in h] != [int(v) for v in r.h160]:
-                raise EclError("[!] error: hash mismatch (%s) pk: %064x" % (r.label, r.pk))
+    # label of a record -> the device method that re-derives its words from the key, and which of the method's results holds them
+    # (p2sh: the script hash of that addr33 hash)
+    _REDERIVE = {"addr33": ("verify", 0), "addr65": ("verify", 1), "p2sh": ("verify", 0), "eth": ("verify_eth", 0), "p2tr": ("verify_tr", 0),
+                 "pub": ("verify_pub", 0)}
 
-    def _collect(self, raw, start):
+    def _verify(self, recs):
+        """pk_verify_hash (main.c:248-263): re-derive the hits from their scalars - the hashes by the window-table sum, a public key by the
+        double-and-add kernel, never the walk kernel (the self-test of the context pins the one against the other) - and compare the words.
+        A p2tr / pub record holds the first 20 bytes of its key and leaves with all eight words of it, a pub record also with .prefix.
+        With an origin (split-key search) image e of O + k G is O' + k' G: k' = the record's partial key, O' the same image of O."""
+        groups = {}
+        for r in recs:
+            groups.setdefault(self._REDERIVE[r.label][0], []).append(r)
+        for method, rs in groups.items():
+            kw = {} if self.origin is None else {"origin": [splitkey_image_origin(self.origin, r.split) for r in rs]}
+            *words, ok = getattr(self.dev, method)([r.pk for r in rs], **kw)
+            hsh = self.dev.p2sh_hash(words[0]) if any(r.label == "p2sh" for r in rs) else None
+            for i, r in enumerate(rs):
+                want = [int(v) for v in (hsh[i] if r.label == "p2sh" else words[self._REDERIVE[r.label][1]][i])]
+                if not ok[i] or want[:5] != [int(v) for v in r.h160[:5]]:
+                    raise EclError("[!] error: hash mismatch (%s) pk: %064x" % (r.label, r.pk))
+                if r.label in ("p2tr", "pub"):
+                    r.h160 = want
+                if r.label == "pub":
+                    r.prefix = "%02x" % (2 | int(words[1][i]))
+
+    def _collect(self, raw, key_of, verify, more=None):
+        """the records of one device call that the list confirms -> FoundRecords with the key key_of(record) (more(found, record) sets a
+        command's own fields), verified if `verify`, counted and added to .found"""
         recs = []
         for r in raw:
-            if not self.flt.confirm(r["h160"]):
-                continue
-            pk = calc_priv(start, self.stride, int(r["key_offset"]), int(r["endo"]))
-            recs.append(FoundRecord(label_of(r["compressed"]), [int(v) for v in r["h160"]], pk))
-            if self.origin is not None:
-                recs[-1].split = int(r["endo"])
-        if self.verify:
+            if self.flt.confirm(r["h160"]):
+                recs.append(FoundRecord(label_of(r["compressed"]), [int(v) for v in r["h160"]], key_of(r)))
+                if more:
+                    more(recs[-1], r)
+        if verify:
             self._verify(recs)
         self.found.extend(recs)
         self.k_found += len(recs)
         return recs
+
+    def _search_lines(self, call, n, cap, key_of, verify, more=None):
+        """one device call of cmd_mul / cmd_mul_raw / cmd_seed over n lines (a dense filter, three types per line: the buffer may overflow)"""
+        self._collect(collect_records(call, self.dev, max(cap, 2 * n)), key_of, verify, more)
+        self.k_checked += n
 
     def add_keys(self, start, nkeys, cap=4096):
         """hash exactly nkeys keys from `start`, in launches of at most launch_keys keys"""
         b, lanes = self.dev.geometry()
         sweep = lanes * 2 * b  # launches that are whole sweeps keep every lane busy and continue without re-init
         per = max(sweep, self.launch_keys // sweep * sweep)
+        kw = {} if self.origin is None else {"origin": self.origin}
+        split = None if self.origin is None else lambda rec, r: setattr(rec, "split", int(r["endo"]))
         done = 0
         while done < nkeys:
             n = nkeys - done
             if n > self.launch_keys:  # what fits one launch goes as one call: the library then sizes the lanes to it
                 n = min(n, per)
             s = (start + done * self.stride) % N
-            c = cap
-            while True:
-                raw, total = self.dev.add_range(s, n, cap=c) if self.origin is None else self.dev.add_range(s, n, cap=c, origin=self.origin)
-                if total <= c:
-                    break
-                # overflow (dense filters only): the device kept up to max(cap, 2^20) records of the call - read the rest; only
-                # if there were more than that is the launch repeated with a buffer that fits
-                rest = self.dev.fetch_found(c, total - c)
-                if len(rest) == total - c:
-                    raw = np.concatenate([raw, rest])
-                    break
-                c = total
-            self._collect(raw, s)
+            raw = collect_records(lambda c: self.dev.add_range(s, n, cap=c, **kw), self.dev, cap)
+            self._collect(raw, lambda r: calc_priv(s, self.stride, int(r["key_offset"]), int(r["endo"])), self.verify, split)
             done += n
 
     def cmd_add(self, range_s, range_e, rank=0, world=1):
@@ -548,27 +521,8 @@ class KeySearch:
         chunk = 1 << 16
         for at in range(0, len(scalars), chunk):
             ks = scalars[at : at + chunk]
-            c = max(cap, 2 * len(ks))
-            while True:
-                raw, total = self.dev.mul_batch(ks, cap=c)
-                if total <= c:
-                    break
-                # more records than the buffer holds (a dense filter, three types per scalar): as in add_keys - read what the device
-                # kept, and repeat the call with a buffer that fits only if it kept less than the call produced
-                rest = self.dev.fetch_found(c, total - c)
-                if len(rest) == total - c:
-                    raw = np.concatenate([raw, rest])
-                    break
-                c = total
-            new = []
-            for r in raw:
-                if self.flt.confirm(r["h160"]):
-                    new.append(FoundRecord(label_of(r["compressed"]), [int(v) for v in r["h160"]], ks[int(r["key_offset"])]))
-                    self.k_found += 1
-            if (self.tr or self.pub) and self.verify:
-                self._verify(new)  # (a p2tr / pub record gets its whole key from the verification)
-            self.found.extend(new)
-            self.k_checked += len(ks)
+            # no verify: main.c:469,474 (a p2tr / pub record gets its whole key from the verification)
+            self._search_lines(lambda c: self.dev.mul_batch(ks, cap=c), len(ks), cap, lambda r: ks[int(r["key_offset"])], (self.tr or self.pub) and self.verify)
         return self.found
 
     def cmd_mul_raw(self, lines, cap=4096):
@@ -578,28 +532,9 @@ class KeySearch:
         chunk = 1 << 16
         for at in range(0, len(lines), chunk):
             part = lines[at : at + chunk]
-            c = max(cap, 2 * len(part))
-            while True:
-                raw, total = self.dev.mul_batch_raw(part, cap=c)
-                if total <= c:
-                    break
-                rest = self.dev.fetch_found(c, total - c)  # (as in cmd_mul)
-                if len(rest) == total - c:
-                    raw = np.concatenate([raw, rest])
-                    break
-                c = total
-            new = []
-            for r in raw:
-                if self.flt.confirm(r["h160"]):
-                    pk = int.from_bytes(kdf_digest(self.kdf or "sha256", part[int(r["key_offset"])]), "big")
-                    new.append(FoundRecord(label_of(r["compressed"]), [int(v) for v in r["h160"]], pk))
-                    self.k_found += 1
-            if self.verify:
-                self._verify(new)
-            self.found.extend(new)
-            self.k_checked += len(part)
+            self._search_lines(lambda c: self.dev.mul_batch_raw(part, cap=c), len(part), cap,
+                               lambda r: int.from_bytes(kdf_digest(self.kdf or "sha256", part[int(r["key_offset"])]), "big"), self.verify)
         return self.found
-
 
     def cmd_seed(self, phrases, paths, count=1, passphrase=b"", cap=4096):
         """`seed`: BIP39 phrases (bytes objects) x BIP32 paths (lists of elements or text), `count` consecutive values of each path's last
@@ -620,28 +555,10 @@ class KeySearch:
         for at in range(0, len(phrases), SEED_BATCH):
             part = phrases[at : at + SEED_BATCH]
             for i, path in enumerate(todo):
-                c = max(cap, 2 * len(part))
-                while True:
-                    raw, total = self.dev.seed_batch(part, path, passphrase=passphrase, reuse=i > 0, cap=c)
-                    if total <= c:
-                        break
-                    rest = self.dev.fetch_found(c, total - c)  # (as in cmd_mul)
-                    if len(rest) == total - c:
-                        raw = np.concatenate([raw, rest])
-                        break
-                    c = total
-                new = []
-                for r in raw:
-                    if self.flt.confirm(r["h160"]):
-                        phrase = part[int(r["key_offset"])]
-                        rec = FoundRecord(label_of(r["compressed"]), [int(v) for v in r["h160"]], bip39_key(phrase, path, passphrase))
-                        rec.path, rec.phrase = format_path(path), phrase
-                        new.append(rec)
-                        self.k_found += 1
-                if self.verify:
-                    self._verify(new)
-                self.found.extend(new)
-                self.k_checked += len(part)
+                def more(rec, r):
+                    rec.path, rec.phrase = format_path(path), part[int(r["key_offset"])]
+                self._search_lines(lambda c: self.dev.seed_batch(part, path, passphrase=passphrase, reuse=i > 0, cap=c), len(part), cap,
+                                   lambda r: bip39_key(part[int(r["key_offset"])], path, passphrase), self.verify, more)
         return self.found
 
 
@@ -1077,11 +994,8 @@ def bsgs_search(pub, range_s, range_e, baby_log2=None, filter_words=None, device
         while done < plan["steps"]:
             n = min(plan["steps"] - done, 1 << 32)
             start = plan["giant_start"] + (done << plan["giant_offs"])
-            raw, total = giant.add_range(start, n, cap=cap, origin=origin)
-            if total > len(raw):
-                raw = np.concatenate([raw, giant.fetch_found(len(raw), total - len(raw))])
-                if len(raw) != total:
-                    raise EclError("bsgs: more records in one call than the device keeps; use a larger filter")
+            raw = collect_records(lambda c: giant.add_range(start, n, cap=c, origin=origin), giant, cap,
+                                  short="bsgs: more records in one call than the device keeps; use a larger filter")
             stats["giant_steps"] += n
             for off in sorted(int(r["key_offset"]) for r in raw):
                 first = range_s + (done + off) * plan["s"]
@@ -1171,11 +1085,8 @@ def kangaroo_search(pub, a, b, herd_log2=None, dp_bits=None, seed=0, max_factor=
     d = Dev(device, a33=False, pub=True, herd=True, ord_offs=plan["dp"])
     try:
         while True:
-            raw, total = d.add_range(None, steps * H, cap=cap, herd=block)
-            if total > len(raw):
-                raw = np.concatenate([raw, d.fetch_found(len(raw), total - len(raw))])
-                if len(raw) != total:
-                    raise EclError("kangaroo: more records in one round than the device keeps; use more dp bits")
+            raw = collect_records(lambda c: d.add_range(None, steps * H, cap=c, herd=block), d, cap,
+                                  short="kangaroo: more records in one round than the device keeps; use more dp bits")
             stats["jumps"] += steps * H
             stats["rounds"] += 1
             for ident, dist, herd in sorted((_dp_identity(r), _dp_distance(r), int(r["endo"])) for r in raw):

@@ -36,8 +36,8 @@ static void *scan_worker(void *arg) {
   scan_worker_t *w = arg;
   scan_t *sn = w->scan;
   run_t *run = sn->run;
-  u32 cap = 4096;
-  ecl_found *buf = malloc(sizeof(ecl_found) * cap);
+  hits_t hits = {NULL, 0}; /* kept, and what it grew to, across the calls */
+  hits_room(&hits, 4096);
   if (!(sn->hashed.w[1] | sn->hashed.w[2] | sn->hashed.w[3])) { /* where the hand-out stops: the library may look ahead over small jobs up to here */
     sc end = scan_scalar(run, &sn->rs, &sn->hashed);
     if (sc_cmp(&end, &sn->rs) > 0) ecl_hip_set_scan_end(run->dev[w->g], end.w);
@@ -73,18 +73,10 @@ static void *scan_worker(void *arg) {
     int rc;
     u64 start[12]; /* -p with -k: the scalar, then the origin - the same origin for every chunk and every shard */
     memcpy(start, s.w, 32), memcpy(start + 4, run->origin, 64);
-    for (;;) {
-      rc = ecl_hip_add_range(run->dev[w->g], start, n, buf, cap, &cnt);
-      if (rc != ECL_E_OVERFLOW) break;
-      /* dense filter: the device kept the records that did not fit (up to max(cap, 2^20) per call) - read them; only a call with
-         more hits than that is run again with a buffer that fits */
-      u32 had = cap, got = 0;
-      cap = cnt, buf = realloc(buf, sizeof(ecl_found) * cap);
-      if (!buf) { fprintf(stderr, "out of memory for %u hit records\n", cap); exit(1); }
-      rc = ecl_hip_fetch_found(run->dev[w->g], had, buf + had, cnt - had, &got);
-      if (rc != ECL_OK || got == cnt - had) break;
-    }
+    do rc = ecl_hip_add_range(run->dev[w->g], start, n, hits.rec, hits.cap, &cnt);
+    while (hits_need_repeat(run->dev[w->g], &rc, &hits, cnt));
     if (rc != ECL_OK) die_ecl(run, w->g, rc, "add_range");
+    ecl_found *buf = hits.rec;
     u32 kept = 0;
     sc *pks = cnt ? malloc(sizeof(sc) * cnt) : NULL;
     for (u32 i = 0; i < cnt; ++i) {
@@ -99,7 +91,7 @@ static void *scan_worker(void *arg) {
     free(pks), free(qx);
     report_progress(&run->rep, st);
   }
-  free(buf);
+  free(hits.rec);
   return NULL;
 }
 

@@ -163,8 +163,8 @@ static int cmd_bsgs(const opts_t *o) {
     fflush(stdout);
   }
 
-  ecl_found *recs = malloc((size_t)BSGS_CAP * sizeof *recs);
-  u32 rcap = BSGS_CAP;
+  hits_t hits = {NULL, 0}; /* kept, and what it grew to, across the calls and the targets */
+  hits_room(&hits, BSGS_CAP);
   for (size_t t = 0; t < ntargets; ++t) {
     const bsgs_target *q = &targets[t];
     u64 start12[12], fp = 0;
@@ -176,16 +176,13 @@ static int cmd_bsgs(const opts_t *o) {
     u64 steps;
     while (!found && (steps = bsgs_giant_call(&plan, &done, &call_start)) != 0) {
       memcpy(start12, call_start.w, 32);
-      rc = ecl_hip_add_range(giant, start12, steps, recs, rcap, &n);
-      if (rc == ECL_E_OVERFLOW) { /* a thin filter: the rest of the call's records are still on the device */
-        if (n > rcap) recs = realloc(recs, (size_t)n * sizeof *recs);
-        u32 got = 0;
-        const u32 have = rcap;
-        if (n > rcap) rcap = n;
-        rc = ecl_hip_fetch_found(giant, have, recs + have, n - have, &got);
-        if (rc == ECL_OK && got != n - have) { fprintf(stderr, "\n[!] bsgs: more records in one call than the device keeps; use a larger filter (-m)\n"); exit(1); }
+      rc = ecl_hip_add_range(giant, start12, steps, hits.rec, hits.cap, &n);
+      if (hits_need_repeat(giant, &rc, &hits, n)) { /* (a thin filter; the walk is not made again) */
+        fprintf(stderr, "\n[!] bsgs: more records in one call than the device keeps; use a larger filter (-m)\n");
+        exit(1);
       }
       if (rc != ECL_OK) bsgs_die(giant, rc, "giant steps");
+      ecl_found *recs = hits.rec;
       qsort(recs, n, sizeof *recs, bsgs_order);
       for (u32 r = 0; r < n && !found; ++r) {
         bsgs_int i = bsgs_u64(recs[r].key_offset), first;
@@ -230,7 +227,7 @@ static int cmd_bsgs(const opts_t *o) {
     bsgs_status(o->quiet, &done, &plan.steps, fp, true);
     if (!found) fprintf(stderr, "%s not found\n", q->hex);
   }
-  free(recs), free(targets);
+  free(hits.rec), free(targets);
   if (outfile) fclose(outfile);
   ecl_hip_close(giant);
   if (scan) ecl_hip_close(scan);

@@ -96,9 +96,9 @@ static int cmd_kangaroo(const opts_t *o) {
            ntargets, ntargets == 1 ? "" : "s", plan.wbits, plan.herd_log2, plan.dp, plan.jb, (unsigned long long)round_jumps);
     fflush(stdout);
   }
-  /* records of a round: twice the expected number and some, the rest of a fuller round comes through ecl_hip_fetch_found */
-  u32 rcap = (round_jumps >> plan.dp) > (1ull << 26) ? 1u << 27 : (u32)(2 * (round_jumps >> plan.dp) + 4096);
-  ecl_found *recs = malloc((size_t)rcap * sizeof *recs);
+  /* records of a round: twice the expected number and some, the rest of a fuller round comes through hits_need_repeat */
+  hits_t hits = {NULL, 0}; /* kept, and what it grew to, across the rounds and the targets */
+  hits_room(&hits, (round_jumps >> plan.dp) > (1ull << 26) ? 1u << 27 : (u32)(2 * (round_jumps >> plan.dp) + 4096));
   for (size_t t = 0; t < ntargets; ++t) {
     const bsgs_target *q = &targets[t];
     u64 blk[16];
@@ -110,15 +110,13 @@ static int cmd_kangaroo(const opts_t *o) {
     bool found = false;
     while (!found) {
       u32 n = 0;
-      rc = ecl_hip_add_range(h, blk, round_jumps, recs, rcap, &n);
-      if (rc == ECL_E_OVERFLOW) {
-        const u32 have = rcap;
-        recs = realloc(recs, (size_t)n * sizeof *recs), rcap = n;
-        u32 got = 0;
-        rc = recs ? ecl_hip_fetch_found(h, have, recs + have, n - have, &got) : ECL_E_HIP;
-        if (rc == ECL_OK && got != n - have) { fprintf(stderr, "\n[!] kangaroo: more records in one round than the device keeps; use more -dp bits\n"); exit(1); }
+      rc = ecl_hip_add_range(h, blk, round_jumps, hits.rec, hits.cap, &n);
+      if (hits_need_repeat(h, &rc, &hits, n)) { /* (too few -dp bits; the round is not made again) */
+        fprintf(stderr, "\n[!] kangaroo: more records in one round than the device keeps; use more -dp bits\n");
+        exit(1);
       }
       if (rc != ECL_OK) bsgs_die(h, rc, "herd");
+      ecl_found *recs = hits.rec;
       jumps += round_jumps;
       qsort(recs, n, sizeof *recs, kg_order);
       for (u32 r = 0; r < n && !found; ++r) {
@@ -155,7 +153,7 @@ static int cmd_kangaroo(const opts_t *o) {
     }
     free(store.slot);
   }
-  free(recs), free(targets);
+  free(hits.rec), free(targets);
   if (outfile) fclose(outfile);
   ecl_hip_close(h);
   return 0;

@@ -104,38 +104,37 @@ static void raw_line_digest(const run_t *run, u32 st[8], const u8 *msg, size_t l
   for (int i = 0; i < 8; ++i) st[i] = (u32)d[4 * i] << 24 | (u32)d[4 * i + 1] << 16 | (u32)d[4 * i + 2] << 8 | d[4 * i + 3];
 }
 
-/* hit records of one device call: the buffer starts with room for MUL_HITS_CAP of them.  A call that reports more (ECL_E_OVERFLOW: a dense
-   filter) has kept up to max(cap, 2^20) of them on the device, and they are fetched here.  A call with more hits than the device keeps -
-   2^19 + 1 scalars of `-a cu` through an all-ones filter are enough, and a batch is up to 2^24 scalars - has to be run again with a
-   buffer that fits (include/ecloop_hip.h, ecl_hip_fetch_found; add_worker in cli_add.h does the same): -> true, *cap is then the call's count */
+/* hit records of one device call of n lines: a buffer per call, with room for min(2 n + 16, MUL_HITS_CAP) of them; a batch of up to 2^24
+   scalars through a dense filter reports more, and they come through hits_need_repeat (cli_report.h) */
 #define MUL_HITS_CAP (1u << 16)
-static bool mul_collect(run_t *run, int g, int rc, ecl_found **buf, u32 *cap, u32 cnt, const char *what) {
-  if (rc == ECL_E_OVERFLOW) {
-    u32 had = *cap, got = 0;
-    *cap = cnt, *buf = realloc(*buf, sizeof(ecl_found) * cnt);
-    if (!*buf) { fprintf(stderr, "out of memory for %u hit records\n", cnt); exit(1); }
-    rc = ecl_hip_fetch_found(run->dev[g], had, *buf + had, cnt - had, &got);
-    if (rc == ECL_OK && got != cnt - had) return true;
-  }
-  if (rc != ECL_OK) die_ecl(run, g, rc, what);
-  return false;
+static hits_t mul_hits(u32 n) {
+  hits_t hits = {NULL, 0};
+  hits_room(&hits, n * 2 + 16 < MUL_HITS_CAP ? n * 2 + 16 : MUL_HITS_CAP);
+  return hits;
+}
+/* one hit of `mul` and its key, to the found sink.  The Bitcoin types keep the reference's behaviour (no verify: main.c:469,474); an eth /
+   p2tr / pub hit has none to keep and is verified like add's, which also gives a p2tr / pub hit the whole key its line prints; always: the
+   caller's own reason to verify every hit (-kdf) */
+static void mul_report(run_t *run, int g, const ecl_found *hit, const sc *pk, bool always) {
+  u32 qx[1][FULL_WORDS];
+  if (run->eth || run->tr || run->pub || always) verify_hits(run, g, pk, hit, 1, qx);
+  report_hit(&run->rep, hit->compressed, run->tr || run->pub ? qx[0] : hit->h160, pk);
 }
 static void mul_flush(run_t *run, int g, u64 (*ks)[4], u32 n) {
   if (!n) return;
-  u32 cap = n * 2 + 16 < MUL_HITS_CAP ? n * 2 + 16 : MUL_HITS_CAP, cnt = 0;
-  ecl_found *buf = malloc(sizeof(ecl_found) * cap);
+  hits_t hits = mul_hits(n);
+  u32 cnt = 0;
   int rc;
-  do rc = ecl_hip_mul_batch(run->dev[g], ks, n, buf, cap, &cnt);
-  while (mul_collect(run, g, rc, &buf, &cap, cnt, "mul_batch"));
+  do rc = ecl_hip_mul_batch(run->dev[g], ks, n, hits.rec, hits.cap, &cnt);
+  while (hits_need_repeat(run->dev[g], &rc, &hits, cnt));
+  if (rc != ECL_OK) die_ecl(run, g, rc, "mul_batch");
   for (u32 i = 0; i < cnt; ++i) {
-    if (!filter_confirms(&run->flt, buf[i].h160)) continue;
+    if (!filter_confirms(&run->flt, hits.rec[i].h160)) continue;
     sc pk;
-    memcpy(pk.w, ks[buf[i].key_offset], 32);
-    u32 qx[1][FULL_WORDS];
-    if (run->eth || run->tr || run->pub) verify_hits(run, g, &pk, &buf[i], 1, qx); /* (an eth / p2tr / pub hit has no reference behaviour to keep: verified like add's) */
-    report_hit(&run->rep, buf[i].compressed, run->tr || run->pub ? qx[0] : buf[i].h160, &pk); /* no verify: main.c:469,474 */
+    memcpy(pk.w, ks[hits.rec[i].key_offset], 32);
+    mul_report(run, g, &hits.rec[i], &pk, false);
   }
-  free(buf);
+  free(hits.rec);
   report_progress(&run->rep, n);
 }
 static bool kdf_test_disagree(void) {
@@ -145,28 +144,26 @@ static bool kdf_test_disagree(void) {
 /* -raw: lines [at, at + n) of a chunk, hashed on the device; a hit's private key is that line's SHA-256 (-kdf: its digest), recomputed here */
 static void mul_flush_raw(run_t *run, int g, const u8 *text, size_t text_len, const u64 *lines, u32 n) {
   if (!n) return;
-  u32 cap = n * 2 + 16 < MUL_HITS_CAP ? n * 2 + 16 : MUL_HITS_CAP, cnt = 0;
-  ecl_found *buf = malloc(sizeof(ecl_found) * cap);
+  hits_t hits = mul_hits(n);
+  u32 cnt = 0;
   int rc;
-  do rc = ecl_hip_mul_batch_raw(run->dev[g], text, (u32)text_len, lines, n, buf, cap, &cnt);
-  while (mul_collect(run, g, rc, &buf, &cap, cnt, "mul_batch_raw"));
+  do rc = ecl_hip_mul_batch_raw(run->dev[g], text, (u32)text_len, lines, n, hits.rec, hits.cap, &cnt);
+  while (hits_need_repeat(run->dev[g], &rc, &hits, cnt));
+  if (rc != ECL_OK) die_ecl(run, g, rc, "mul_batch_raw");
   for (u32 i = 0; i < cnt; ++i) {
-    if (!filter_confirms(&run->flt, buf[i].h160)) continue;
-    const u64 ln = lines[buf[i].key_offset];
+    if (!filter_confirms(&run->flt, hits.rec[i].h160)) continue;
+    const u64 ln = lines[hits.rec[i].key_offset];
     u32 st[8];
     raw_line_digest(run, st, text + (u32)ln, (size_t)(ln >> 32));
     sc pk = {{(u64)st[6] << 32 | st[7], (u64)st[4] << 32 | st[5], (u64)st[2] << 32 | st[3], (u64)st[0] << 32 | st[1]}};
     /* test hook: ECLOOP_HIP_TEST_KDF_DISAGREE=1 flips the lowest bit of the host's -kdf digest of every hit - what a device hash that
        disagrees with the host's looks like from here - so that the verification below has to stop the run (tests/test_gpu_kdf.py) */
     if (run->kdf != KDF_SHA256 && kdf_test_disagree()) pk.w[0] ^= 1;
-    u32 qx[1][FULL_WORDS];
-    /* plain -raw keeps the reference's behaviour for the Bitcoin types (no verify: main.c:469,474); under -kdf every hit of every type is
-       re-derived on the device from the host's digest: the device's hash and the host's are two implementations, and a key is printed
-       only where they agree */
-    if (run->eth || run->tr || run->pub || run->kdf != KDF_SHA256) verify_hits(run, g, &pk, &buf[i], 1, qx);
-    report_hit(&run->rep, buf[i].compressed, run->tr || run->pub ? qx[0] : buf[i].h160, &pk);
+    /* plain -raw keeps the reference's behaviour for the Bitcoin types; under -kdf every hit of every type is re-derived on the device from
+       the host's digest: the device's hash and the host's are two implementations, and a key is printed only where they agree */
+    mul_report(run, g, &hits.rec[i], &pk, run->kdf != KDF_SHA256);
   }
-  free(buf);
+  free(hits.rec);
   report_progress(&run->rep, n);
 }
 /* cmd_mul (main.c:542-576): stdin lines -> scalars (hex, or SHA-256 of the text with -raw) -> device batches.

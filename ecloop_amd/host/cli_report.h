@@ -134,6 +134,27 @@ static void die_ecl(run_t *run, int g, int rc, const char *what) {
   keys_restore();
   _exit(1);
 }
+/* The hit records of a device call, and the caller's half of the overflow protocol (include/ecloop_hip.h).  A search call that reports more
+   hits than its buffer holds (ECL_E_OVERFLOW: a dense filter) has kept up to max(cap, 2^20) of them on the device, and they are read from
+   there.  A call with more hits than the device keeps - 2^19 + 1 keys of `-a cu` through an all-ones filter are enough - has to be made
+   again with a buffer that fits.  Every command that searches goes through here. */
+typedef struct { ecl_found *rec; u32 cap; } hits_t;
+static void hits_room(hits_t *b, u32 cap) { /* room for cap records, what b holds stays; a failed allocation ends the program */
+  if (cap <= b->cap) return;
+  b->rec = realloc(b->rec, sizeof(ecl_found) * cap), b->cap = cap;
+  if (!b->rec) { fprintf(stderr, "out of memory for %u hit records\n", cap); exit(1); }
+}
+/* behind a search call that returned *rc and reported cnt hits into b.  ECL_E_OVERFLOW: b grows to cnt and records [old cap, cnt) are
+   fetched.  -> true: the device kept fewer than the call produced - b now holds room for cnt, the same call made again fits.
+   -> false: *rc is the call's result (ECL_OK: b holds all cnt records). */
+static bool hits_need_repeat(ecl_hip *h, int *rc, hits_t *b, u32 cnt) {
+  if (*rc != ECL_E_OVERFLOW) return false;
+  const u32 had = b->cap;
+  u32 got = 0;
+  hits_room(b, cnt);
+  *rc = ecl_hip_fetch_found(h, had, b->rec + had, cnt - had, &got);
+  return *rc == ECL_OK && got != cnt - had;
+}
 /* pk_verify_hash (main.c:248-263) for all hits of one device call at once: both hash160 values of every reported key are
    derived again on the device by the window-table sum (ecl_hip_verify: not the walk kernel; own inversion per key) and
    compared with what the walk reported; a p2sh hit is compared with the script hash of that addr33 hash (ecl_hip_p2sh_hash);

@@ -189,8 +189,8 @@ static int cmd_seed(run_t *run) {
   if (!o->quiet) printf("seed: %d path%s x %llu ~ filter: %s\n----------------------------------------\n", npaths, npaths == 1 ? "" : "s",
                         (unsigned long long)count, run->flt.list ? "list" : "bloom"), fflush(stdout);
   const bool disagree = seed_test_disagree();
-  u32 cap = MUL_HITS_CAP;
-  ecl_found *hits = seed_alloc(NULL, sizeof(ecl_found) * cap);
+  hits_t found = {NULL, 0}; /* kept, and what it grew to, across the calls */
+  hits_room(&found, MUL_HITS_CAP);
   u64 *table = seed_alloc(NULL, ((size_t)SEED_BATCH + 1) * 8), *lines = NULL;
   u8 *text = NULL;
   size_t lines_cap = 0, text_cap = 0;
@@ -220,8 +220,10 @@ static int cmd_seed(run_t *run) {
           memcpy(rec + 8 + 4 * path.depth, pass, pass_len);
           table[0] = (u64)(8 + 4 * (size_t)path.depth + pass_len) << 32;
           u32 cnt = 0;
-          do rc = ecl_hip_mul_batch_raw(run->dev[0], text, (u32)text_bytes, table, m + 1, hits, cap, &cnt);
-          while (mul_collect(run, 0, rc, &hits, &cap, cnt, "mul_batch_raw (seed)"));
+          do rc = ecl_hip_mul_batch_raw(run->dev[0], text, (u32)text_bytes, table, m + 1, found.rec, found.cap, &cnt);
+          while (hits_need_repeat(run->dev[0], &rc, &found, cnt));
+          if (rc != ECL_OK) die_ecl(run, 0, rc, "mul_batch_raw (seed)");
+          const ecl_found *hits = found.rec;
           for (u32 i = 0; i < cnt; ++i) {
             if (!filter_confirms(&run->flt, hits[i].h160)) continue;
             const u64 ln = lines[at + hits[i].key_offset];
@@ -238,7 +240,7 @@ static int cmd_seed(run_t *run) {
     }
   }
   report_close(&run->rep);
-  free(table), free(hits), free(lines), free(text), free(in.buf);
+  free(table), free(found.rec), free(lines), free(text), free(in.buf);
   ecl_hip_close(run->dev[0]);
   return 0;
 }

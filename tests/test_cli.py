@@ -888,6 +888,41 @@ def test_mul_device_calls_with_more_hits_than_the_device_keeps(cli, tmp_path):
         assert np.array_equal(np.sort(raw.reshape(-1, 113).view("S113").ravel()), expected(b)), name
 
 
+@pytest.mark.gpu
+def test_add_device_call_with_more_hits_than_the_device_keeps(cli, tmp_path):
+    """`add -a cu -r 80000:100800` through an all-ones filter: 2^19 + 2048 keys are one device call with 2^20 + 4096 hits, more than the
+    2^20 records the device keeps of a call (the smallest range of two types that gets there), so fetching the overflow falls short and
+    the launch has to be repeated with a buffer that fits: two launches.  Every key's two found lines must be there, equal to the
+    ORACLE's (orc.mul_hash160_many over the consecutive keys), compared as sorted arrays of the 113-byte found lines."""
+    import orc
+    first, n = 0x80000, (1 << 19) + 2048
+    hexd = np.frombuffer(b"0123456789abcdef", dtype=np.uint8)
+
+    def hex_of(b):  # (n, m) uint8 -> (n, 2m) uint8 hex digits
+        out = np.empty((len(b), 2 * b.shape[1]), np.uint8)
+        out[:, 0::2], out[:, 1::2] = hexd[b >> 4], hexd[b & 15]
+        return out
+
+    keys = np.zeros((n, 32), np.uint8)  # the private keys' big-endian bytes
+    keys[:, 28:] = (first + np.arange(n)).astype(">u4").view(np.uint8).reshape(n, 4)
+    h33, h65, ok = orc.mul_hash160_many(np.ascontiguousarray(keys[:, ::-1]).view("<u8").reshape(n, 4), True, True)
+    assert ok.all()
+    want = np.empty((2 * n, 113), np.uint8)
+    for at, label, hh in ((0, b"addr33", h33), (n, b"addr65", h65)):
+        part = want[at:at + n]
+        part[:, :6], part[:, 6], part[:, 47], part[:, 112] = np.frombuffer(label, np.uint8), 9, 9, 10
+        part[:, 7:47], part[:, 48:112] = hex_of(hh.astype(">u4").view(np.uint8).reshape(n, 20)), hex_of(keys)
+    flt, out = str(tmp_path / "ones.blf"), str(tmp_path / "add.found")
+    write_blf(flt, np.full(64, 0xFFFFFFFFFFFFFFFF, np.uint64))
+    pr = subprocess.run(["timeout", "-k", "10", "300", cli, "add", "-t", "1", "-a", "cu", "-f", flt, "-r", "%x:%x" % (first, first + n), "-q", "-o", out],
+                        stdin=subprocess.DEVNULL, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=dict(os.environ, ECLOOP_HIP_STATS="1"))
+    assert pr.returncode == 0, pr.stderr.decode(errors="replace")[-2000:]
+    assert "gpu 0: 2 launches" in pr.stdout.decode(errors="replace"), pr.stdout.decode(errors="replace")[-2000:]
+    raw = np.fromfile(out, np.uint8)
+    assert len(raw) == 2 * n * 113, len(raw)
+    assert np.array_equal(np.sort(raw.reshape(-1, 113).view("S113").ravel()), np.sort(want.view("S113").ravel()))
+
+
 def test_scan_plan_matches_the_oracles_job_loop(cli):
     """the hidden `plan` command prints what scan_plan() derives from -r / -d: keys hashed and status counter of
     cmd_add (main.c:405-454).  Compared with the oracle, which RUNS the reference's job loop (counter stepping by
