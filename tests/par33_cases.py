@@ -12,8 +12,8 @@ import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "ecloop_amd", "csrc", "tools", "par33_host.cpp")
+from support import host_program
+
 LIMB_PAR33 = 27  # csrc/limb_ops.h: in0 = lam, in1 = b, in2 = Y; flag = parity, out0.n[0] = 1 when the exact product was taken
 G = 256          # EMIT33_YPAR_G
 REC = np.dtype([("lam", "<u4", 9), ("b", "<u4", 9), ("Y", "<u4", 9), ("par", "<u4"), ("path", "<u4"), ("set", "<u4")])
@@ -32,10 +32,7 @@ def _workdir():
 @functools.lru_cache(maxsize=None)
 def program(sanitize=False):
     """path of the compiled program (g++; with sanitize: the address and undefined-behaviour sanitizers, errors fatal)"""
-    exe = os.path.join(_workdir(), "par33_host_san" if sanitize else "par33_host")
-    flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else ["-O2"]
-    subprocess.run(["g++"] + flags + ["-std=c++17", "-o", exe, SRC], check=True)
-    return exe
+    return host_program(_workdir(), "par33_host.cpp", ["-O1", "-g"] if sanitize else ["-O2"], sanitize)
 
 
 @functools.lru_cache(maxsize=None)

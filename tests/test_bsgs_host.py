@@ -7,7 +7,6 @@ import functools
 import os
 import random
 import re
-import shutil
 import subprocess
 import sys
 
@@ -16,28 +15,16 @@ import pytest
 
 import orc
 import pub_ref
+from ecloop_amd.capi import limbs
+from support import ROOT, cli, host_lib, host_program, int_of, kept_assembly, run_program, words8
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-SRC = os.path.join(ROOT, "ecloop_amd", "csrc", "tools", "bsgs_host.cpp")
 P, N = orc.P, orc.N
-
-
-def limbs(v):
-    return np.array([(v >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], np.uint64)
 
 
 def ptr(v):
     """the limbs of v as a pointer argument that keeps its array alive for the call"""
     return limbs(v).ctypes.data_as(C.c_void_p)
-
-
-def int_of(a):
-    return sum(int(v) << (64 * i) for i, v in enumerate(a))
-
-
-def words8(v):
-    return [(v >> (32 * i)) & 0xFFFFFFFF for i in range(8)]
 
 
 def words16(pt):
@@ -51,9 +38,7 @@ def x_of(k):
 
 @pytest.fixture(scope="module")
 def H(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("bsgshost") / "libbsgshost.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, SRC], check=True)
-    lib = C.CDLL(so)
+    lib = host_lib(tmp_path_factory, "bsgs_host.cpp")
     lib.bh_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p]
     lib.bh_default_beta.argtypes = [C.c_void_p, C.c_void_p]
     lib.bh_default_beta.restype = C.c_uint
@@ -246,17 +231,8 @@ def test_header_and_binding_pin_the_two_flags():
 
 def test_the_host_program_runs_clean_under_the_sanitizers(tmp_path):
     """csrc/tools/bsgs_host.cpp has a main of its own: built as a program with the address and undefined-behaviour sanitizers and run"""
-    exe = str(tmp_path / "bsgs_host")
-    subprocess.run(["g++", "-O0", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, SRC], check=True)
-    pr = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    pr = run_program(host_program(tmp_path, "bsgs_host.cpp", ["-O0"]))
     assert pr.returncode == 0 and "bsgs_host: ok" in pr.stdout, (pr.stdout, pr.stderr)
-
-
-@pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
 
 
 def test_cli_names_the_command_and_refuses_before_a_gpu_is_looked_for(cli, tmp_path):
@@ -288,13 +264,8 @@ def test_the_new_kernels_registers_and_loops():
     """static, from the assembly the build keeps (tools/isa_mix.py --bsgs): the insert walk fits 128 VGPRs (four waves per SIMD, as
     k_add_pub), has no scratch instruction below its launch loop, sets its 20 bits in the `which` loop, and its loop nest was seen; the
     origin kernel does not spill.  Figures of this build: 128 VGPRs, 14 spilled (launch loop), per key 1 536 static VALU against 813."""
-    from ecloop_amd.build import ASM, build_library
     import isa_mix
-    if shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc"):
-        build_library()
-    if not os.path.exists(ASM):
-        pytest.skip("no hipcc and no kept assembly: nothing to analyse")
-    now = isa_mix.analyse_bsgs(ASM)
+    now = isa_mix.analyse_bsgs(kept_assembly())
     ins, org = now["bsgs insert"], now["bsgs origin"]
     print(ins["registers"], ins["per_key_valu"], ins["pub_per_key_valu"], org["registers"])
     assert ins["registers"]["vgpr_count"] <= 128 and ins["scratch_below_top"] == 0

@@ -6,11 +6,8 @@ texts, the three transitions of the last call's records, the coverage totals by 
 and undefined-behaviour sanitizers and run.  The text checks below keep the counter words and the last records behind their names."""
 import os
 import re
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ecloop_amd", "csrc")
-SRC = os.path.join(CSRC, "tools", "callstate_host.cpp")
+from support import CSRC, ROOT, host_program, run_program
 
 
 def code_of(path):
@@ -24,9 +21,7 @@ def host_code():
 
 
 def test_the_verdict_table_holds_under_the_sanitizers(tmp_path):
-    exe = str(tmp_path / "callstate_host")
-    subprocess.run(["g++", "-O0", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, SRC], check=True)
-    pr = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    pr = run_program(host_program(tmp_path, "callstate_host.cpp", ["-O0", "-Wall", "-Werror"]))
     assert pr.returncode == 0 and pr.stderr == "", (pr.stdout, pr.stderr)
     m = re.search(r"callstate_host: ok \((\d+) cases\)", pr.stdout)
     assert m and int(m.group(1)) >= 14, pr.stdout

@@ -10,34 +10,10 @@ import subprocess
 import numpy as np
 import pytest
 
+from support import GOLD, cli, counts, run_cli
 from synth import synth_bloom_words, write_blf
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
 G = json.load(open(os.path.join(GOLD, "golden.json")))["cases"]
-
-
-@pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
-
-
-def run(cli, args, stdin_path=None, out=None, env=None):
-    cmd = [cli] + args + (["-q", "-o", out] if out else [])
-    pr = subprocess.run(cmd, stdin=open(stdin_path, "rb") if stdin_path else subprocess.DEVNULL, stdout=subprocess.PIPE,
-                        stderr=subprocess.PIPE, timeout=600, env=env)
-    assert pr.returncode == 0, pr.stderr.decode(errors="replace")[-2000:]
-    status = pr.stderr.decode(errors="replace").replace("\x1b[2K", "\r").split("\r")[-1].strip()
-    lines = sorted(l.rstrip("\n") for l in open(out)) if out and os.path.exists(out) else []
-    return lines, status, pr.stdout.decode(errors="replace")
-
-
-def counts(status):
-    found, checked = status.split("~")[-1].split("/")
-    clean = lambda s: int("".join(c for c in s if c.isdigit()))
-    return clean(found), clean(checked)
 
 
 def digest(lines):
@@ -72,9 +48,9 @@ def test_odd_list_layout_read_like_the_reference_host_side():
 
 @pytest.mark.gpu
 def test_odd_list_layout_found_lines_equal_the_references(cli, tmp_path):
-    lines, status, _ = run(cli, ["add", "-f", os.path.join(GOLD, "odd-list.txt"), "-r", "8000:87ff", "-t", "1"], out=str(tmp_path / "o.txt"))
+    r = run_cli(cli, ["add", "-f", os.path.join(GOLD, "odd-list.txt"), "-r", "8000:87ff", "-t", "1"], out=str(tmp_path / "o.txt"))
     g = G["odd_list_8000_87ff"]
-    assert lines == sorted(g["lines"]) and list(counts(status)) == g["status"]
+    assert r.lines == sorted(g["lines"]) and list(counts(r.status)) == g["status"]
 
 
 def test_usage_and_version(cli):
@@ -90,10 +66,10 @@ def test_add_known_answers(cli, tmp_path):
     puz = os.path.join(GOLD, "btc-puzzles-hash")
     for name, rng, extra in [("cfg1_list_800000_ffffff", "800000:ffffff", []), ("make_add_8000_ffffff", "8000:ffffff", []),
                              ("ci_smoke_8000_ffff", "8000:ffff", []), ("endo_cu_list_8000_fffff", "8000:fffff", ["-a", "cu", "-endo"])]:
-        lines, status, _ = run(cli, ["add", "-f", puz, "-r", rng, "-t", "1"] + extra, out=str(tmp_path / (name + ".txt")))
+        r = run_cli(cli, ["add", "-f", puz, "-r", rng, "-t", "1"] + extra, out=str(tmp_path / (name + ".txt")))
         g = G[name]
-        assert lines == sorted(g["lines"])
-        assert counts(status) == (g["status_found"], g["status_checked"])
+        assert r.lines == sorted(g["lines"])
+        assert counts(r.status) == (g["status_found"], g["status_checked"])
 
 
 @pytest.mark.gpu
@@ -113,7 +89,8 @@ def test_add_sharded_over_device_threads(cli, tmp_path, ngpu, counter):
                                ("endo_cu_list_8000_fffff", ["-f", puz, "-r", "8000:fffff", "-a", "cu", "-endo"], 1015808),
                                ("dump33_overrun_9000_9801", ["-f", ones, "-r", "9000:9801"], 4096),
                                ("dump_cu_endo_8000_87ff", ["-f", ones, "-r", "8000:87ff", "-a", "cu", "-endo"], 2048)]:
-        lines, status, stdout = run(cli, ["add", "-t", str(ngpu)] + args, out=str(tmp_path / (name + ".txt")), env=env)
+        r = run_cli(cli, ["add", "-t", str(ngpu)] + args, out=str(tmp_path / (name + ".txt")), env=env)
+        lines, status, stdout = r.lines, r.status, r.stdout
         g = G[name]
         assert "gpus: %d " % ngpu in stdout
         assert len(lines) == g.get("count", len(g.get("lines", []))) and digest(lines) == g["sha256_sorted"], name
@@ -143,16 +120,16 @@ def test_add_handed_out_in_the_references_job_size(cli, tmp_path, threads):
     cases = [["-f", puz, "-r", "8000:ffffff"], ["-f", flt, "-r", "100000000:11fffffff"], ["-f", flt, "-r", "100000000:101ffffff", "-a", "cu", "-endo"],
              ["-f", flt, "-r", "%x:%x" % (1 << 160, (1 << 160) + (((1 << 26) - 1) << 64)), "-d", "64:32"]]
     for k, args in enumerate(cases):
-        base = run(cli, ["add", "-t", "1"] + args, out=str(tmp_path / ("base%d.txt" % k)))
+        base = run_cli(cli, ["add", "-t", "1"] + args, out=str(tmp_path / ("base%d.txt" % k)))
         outs = []
         for e, extra in enumerate(({}, {"ECL_HIP_LOOKAHEAD_LOG2": "0"})):
             env = dict(os.environ, ECLOOP_HIP_JOB_KEYS=str(1 << 21), ECLOOP_HIP_SHARE_GPU=str(threads), ECLOOP_HIP_STATS="1", **extra)
-            lines, status, stdout = run(cli, ["add", "-t", str(threads)] + args, out=str(tmp_path / ("job%d_%d.txt" % (k, e))), env=env)
-            assert lines == base[0] and counts(status) == counts(base[1]), (k, extra)
-            outs.append(sum(int(m) for m in re.findall(r"^gpu \d+: (\d+) launches", stdout, re.M)))
+            r = run_cli(cli, ["add", "-t", str(threads)] + args, out=str(tmp_path / ("job%d_%d.txt" % (k, e))), env=env)
+            assert r.lines == base.lines and counts(r.status) == counts(base.status), (k, extra)
+            outs.append(sum(int(m) for m in re.findall(r"^gpu \d+: (\d+) launches", r.stdout, re.M)))
         if k == 1:  # 2^29 keys = 256 jobs: a handful of launches with the look-ahead, one per job without
             assert outs[0] <= 8 + 2 * threads and outs[1] == 256, outs
-        assert len(base[0]) > 0
+        assert len(base.lines) > 0
 
 
 @pytest.mark.gpu
@@ -196,8 +173,8 @@ def test_mul_from_a_file_in_batches_equals_the_general_reader_the_pipe_and_the_o
     runs = {"file": (base, src, {"ECLOOP_HIP_MUL_BATCH_LOG2": "19"}), "file-avx2": (base, src, {"ECLOOP_HIP_NO_AVX512": "1"}),
             "chunks": (base, src, {"ECLOOP_HIP_MUL_READ": "chunks"}), "crlf": (base, crlf, {}), "bin": (base + ["-bin"], binf, {})}
     for name, (args, path, extra) in runs.items():
-        lines, status, _ = run(cli, args, stdin_path=path, out=str(tmp_path / (name + ".txt")), env=dict(os.environ, **extra))
-        assert lines == want and counts(status) == (len(want), n), name
+        r = run_cli(cli, args, stdin_path=path, out=str(tmp_path / (name + ".txt")), env=extra)
+        assert r.lines == want and counts(r.status) == (len(want), n), name
     pr = subprocess.Popen(["cat", src], stdout=subprocess.PIPE)
     out = str(tmp_path / "pipe.txt")
     got = subprocess.run([cli] + base + ["-q", "-o", out], stdin=pr.stdout, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
@@ -217,10 +194,10 @@ def test_rnd_windows_handed_out_in_the_references_job_size(cli, tmp_path):
     outs = []
     for k, extra in enumerate(({}, {"ECLOOP_HIP_JOB_KEYS": str(1 << 21)}, {"ECLOOP_HIP_JOB_KEYS": str(1 << 21), "ECL_HIP_LOOKAHEAD_LOG2": "0"})):
         env = dict(os.environ, ECLOOP_HIP_RND_WINDOWS="3", ECLOOP_HIP_STATS="1", **extra)
-        lines, status, stdout = run(cli, args, out=str(tmp_path / ("rnd%d.txt" % k)), env=env)
-        masks = [l for l in stdout.splitlines() if re.fullmatch(r"[0-9a-f ]{67}", l)]
-        launches = sum(int(m) for m in re.findall(r"^gpu \d+: (\d+) launches", stdout, re.M))
-        outs.append((lines, counts(status), masks, launches))
+        r = run_cli(cli, args, out=str(tmp_path / ("rnd%d.txt" % k)), env=env)
+        masks = [l for l in r.stdout.splitlines() if re.fullmatch(r"[0-9a-f ]{67}", l)]
+        launches = sum(int(m) for m in re.findall(r"^gpu \d+: (\d+) launches", r.stdout, re.M))
+        outs.append((r.lines, counts(r.status), masks, launches))
     assert outs[0][:3] == outs[1][:3] == outs[2][:3] and len(outs[0][2]) == 6 and len(outs[0][0]) > 10
     assert outs[0][3] == 3 and outs[1][3] <= 12 and outs[2][3] == 3 * 128, [o[3] for o in outs]
 
@@ -234,10 +211,10 @@ def test_add_dumps_and_stride(cli, tmp_path):
                        ("dump_cu_endo_8000_87ff", ["-r", "8000:87ff", "-a", "cu", "-endo"]),
                        ("dump33_overrun_9000_9801", ["-r", "9000:9801"]),
                        ("dump33_stride128", ["-r", f"{a:x}:{a + 1:x}", "-d", "128:32"])]:
-        lines, status, _ = run(cli, ["add", "-f", ones, "-t", "1"] + args, out=str(tmp_path / (name + ".txt")))
+        r = run_cli(cli, ["add", "-f", ones, "-t", "1"] + args, out=str(tmp_path / (name + ".txt")))
         g = G[name]
-        assert len(lines) == g["count"] and digest(lines) == g["sha256_sorted"], name
-        assert counts(status) == (g["status_found"], g["status_checked"]), name
+        assert len(r.lines) == g["count"] and digest(r.lines) == g["sha256_sorted"], name
+        assert counts(r.status) == (g["status_found"], g["status_checked"]), name
 
 
 @pytest.mark.gpu
@@ -245,8 +222,8 @@ def test_sparse_bloom_two_jobs(cli, tmp_path):
     g = G["sparse_fp33_two_jobs"]
     blf = str(tmp_path / "s.blf")
     write_blf(blf, synth_bloom_words(g["bloom"]["words"], g["bloom"]["seed"], g["bloom"]["mode"]))
-    lines, status, _ = run(cli, ["add", "-f", blf, "-r", "8000:208800"], out=str(tmp_path / "o.txt"))
-    assert digest(lines) == g["sha256_sorted"] and counts(status) == (g["status_found"], g["status_checked"])
+    r = run_cli(cli, ["add", "-f", blf, "-r", "8000:208800"], out=str(tmp_path / "o.txt"))
+    assert digest(r.lines) == g["sha256_sorted"] and counts(r.status) == (g["status_found"], g["status_checked"])
 
 
 @pytest.mark.gpu
@@ -262,26 +239,26 @@ def test_long_hash_list_prepared_on_the_device(cli, tmp_path):
     r.shuffle(entries)
     lst = tmp_path / "big.txt"
     lst.write_text("\n".join(entries) + "\n")
-    a, sa, _ = run(cli, ["add", "-f", str(lst), "-r", "8000:ffff"], out=str(tmp_path / "a.txt"))
-    b, sb, _ = run(cli, ["add", "-f", str(lst), "-r", "8000:ffff"], out=str(tmp_path / "b.txt"), env=dict(os.environ, ECLOOP_HIP_LIST_ON_HOST="1"))
-    assert sorted(a) == sorted(b) and len(a) == 3 and counts(sa) == counts(sb)
-    assert sorted(l.split("\t")[2][-4:] for l in a) == ["8123", "9abc", "fff0"]
+    a = run_cli(cli, ["add", "-f", str(lst), "-r", "8000:ffff"], out=str(tmp_path / "a.txt"))
+    b = run_cli(cli, ["add", "-f", str(lst), "-r", "8000:ffff"], out=str(tmp_path / "b.txt"), env={"ECLOOP_HIP_LIST_ON_HOST": "1"})
+    assert sorted(a.lines) == sorted(b.lines) and len(a.lines) == 3 and counts(a.status) == counts(b.status)
+    assert sorted(l.split("\t")[2][-4:] for l in a.lines) == ["8123", "9abc", "fff0"]
 
 
 @pytest.mark.gpu
 def test_mul_flows(cli, tmp_path):
-    lines, status, _ = run(cli, ["mul", "-f", os.path.join(GOLD, "btc-bw-hash"), "-a", "cu"], stdin_path=os.path.join(GOLD, "btc-bw-priv"),
-                           out=str(tmp_path / "m.txt"))
+    r = run_cli(cli, ["mul", "-f", os.path.join(GOLD, "btc-bw-hash"), "-a", "cu"], stdin_path=os.path.join(GOLD, "btc-bw-priv"),
+                out=str(tmp_path / "m.txt"))
     g = G["make_mul_bw"]
-    assert len(lines) == 1080 and digest(lines) == g["sha256_sorted"] and counts(status) == (1080, 1080)
+    assert len(r.lines) == 1080 and digest(r.lines) == g["sha256_sorted"] and counts(r.status) == (1080, 1080)
     ones = str(tmp_path / "ones.blf")
     write_blf(ones, np.full(64, 0xFFFFFFFFFFFFFFFF, np.uint64))
-    lines, _, _ = run(cli, ["mul", "-f", ones, "-a", "cu"], stdin_path=os.path.join(GOLD, "mul_scalars.txt"), out=str(tmp_path / "d.txt"))
+    lines = run_cli(cli, ["mul", "-f", ones, "-a", "cu"], stdin_path=os.path.join(GOLD, "mul_scalars.txt"), out=str(tmp_path / "d.txt")).lines
     assert digest(lines) == G["mul_dump_cu"]["sha256_sorted"]
     # -raw: scalar = SHA-256(line); "abc" is a public SHA-256 test vector
     raw = tmp_path / "raw.txt"
     raw.write_text("abc\n")
-    lines, _, _ = run(cli, ["mul", "-f", ones, "-raw"], stdin_path=str(raw), out=str(tmp_path / "r.txt"))
+    lines = run_cli(cli, ["mul", "-f", ones, "-raw"], stdin_path=str(raw), out=str(tmp_path / "r.txt")).lines
     assert lines[0].split("\t")[2] == "ba7816bf8f01cfea414140de5dae2223b00361a396177a9cb410ff61f20015ad"
 
 
@@ -302,7 +279,7 @@ def test_rnd_window_is_an_add_over_the_printed_bounds(cli, tmp_path):
     assert int(masks[0], 16) == lo and int(masks[1], 16) == hi
     rnd_lines = sorted(l.rstrip("\n") for l in open(out))
     add_out = str(tmp_path / "add.txt")
-    add_lines, _, _ = run(cli, ["add", "-f", ones, "-r", f"{lo:x}:{hi:x}"], out=add_out)
+    add_lines = run_cli(cli, ["add", "-f", ones, "-r", f"{lo:x}:{hi:x}"], out=add_out).lines
     # rnd scans whole 2^21-key jobs (main.c:624): the add over the same bounds is a subset; same keys inside the window
     inside = [l for l in rnd_lines if lo <= int(l.split("\t")[2], 16) <= hi + 2048]
     assert set(add_lines) <= set(rnd_lines) and len(add_lines) > 100
@@ -602,8 +579,8 @@ def test_mul_long_lines_found_lines_equal_the_references(cli, tmp_path):
     ones = str(tmp_path / "ones.blf")
     write_blf(ones, np.full(64, 0xFFFFFFFFFFFFFFFF, np.uint64))
     for name, flag in (("mul_long_lines_hex", []), ("mul_long_lines_raw", ["-raw"])):
-        lines, status, _ = run(cli, ["mul", "-f", ones] + flag, stdin_path=os.path.join(GOLD, name + ".txt"), out=str(tmp_path / (name + ".txt")))
-        assert lines == sorted(G[name]["lines"]) and list(counts(status)) == G[name]["status"]
+        r = run_cli(cli, ["mul", "-f", ones] + flag, stdin_path=os.path.join(GOLD, name + ".txt"), out=str(tmp_path / (name + ".txt")))
+        assert r.lines == sorted(G[name]["lines"]) and list(counts(r.status)) == G[name]["status"]
 
 
 def test_mul_parser_raw_and_bin_and_chunk_boundaries(cli):
@@ -810,12 +787,12 @@ def test_mul_fans_out_over_device_threads(cli, tmp_path, mode):
         src.write_bytes(b"".join((int(l, 16) % N).to_bytes(32, "little") for l in lines_in))
         extra = ["-bin"]
     env = dict(os.environ, ECLOOP_HIP_SHARE_GPU="4")
-    lines, status, stdout = run(cli, ["mul", "-f", os.path.join(GOLD, "btc-bw-hash"), "-a", "cu", "-t", "4"] + extra, stdin_path=str(src),
-                                out=str(tmp_path / "m.txt"), env=env)
-    assert "gpus: 4 " in stdout
-    c = Counter(lines)
+    r = run_cli(cli, ["mul", "-f", os.path.join(GOLD, "btc-bw-hash"), "-a", "cu", "-t", "4"] + extra, stdin_path=str(src),
+                out=str(tmp_path / "m.txt"), env=env)
+    assert "gpus: 4 " in r.stdout
+    c = Counter(r.lines)
     assert len(c) == 1080 and set(c.values()) == {2} and digest(sorted(c)) == G["make_mul_bw"]["sha256_sorted"]
-    assert counts(status) == (2160, len(lines_in))
+    assert counts(r.status) == (2160, len(lines_in))
 
 
 @pytest.mark.gpu
@@ -836,12 +813,12 @@ def test_mul_raw_fans_out_over_device_threads(cli, tmp_path):
         for block in (fill, targets, [""], fill, targets):
             f.write("\n".join(block) + "\n")
     env = dict(os.environ, ECLOOP_HIP_SHARE_GPU="4")
-    lines, status, stdout = run(cli, ["mul", "-raw", "-f", str(lst), "-t", "4"], stdin_path=str(src), out=str(tmp_path / "r.txt"), env=env)
-    assert "gpus: 4 " in stdout
-    c = Counter(lines)
+    r = run_cli(cli, ["mul", "-raw", "-f", str(lst), "-t", "4"], stdin_path=str(src), out=str(tmp_path / "r.txt"), env=env)
+    assert "gpus: 4 " in r.stdout
+    c = Counter(r.lines)
     want = {"addr33\t%s\t%064x" % ("".join("%08x" % w for w in h), k) for h, k in zip(hs, keys)}
     assert set(c) == want and set(c.values()) == {2}
-    assert counts(status) == (400, 2 * len(fill) + 2 * len(targets))
+    assert counts(r.status) == (400, 2 * len(fill) + 2 * len(targets))
 
 
 @pytest.mark.gpu

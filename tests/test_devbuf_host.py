@@ -6,17 +6,12 @@ whose third allocation fails has the capacity of its smallest member and is comp
 allocations equal frees at exit.  Built as a program of its own with the address and undefined-behaviour sanitizers and run."""
 import os
 import re
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "ecloop_amd", "csrc")
-SRC = os.path.join(CSRC, "tools", "devbuf_host.cpp")
+from support import CSRC, host_program, run_program
 
 
 def test_the_buffer_rules_hold_under_the_sanitizers(tmp_path):
-    exe = str(tmp_path / "devbuf_host")
-    subprocess.run(["g++", "-O0", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, SRC], check=True)
-    pr = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    pr = run_program(host_program(tmp_path, "devbuf_host.cpp", ["-O0", "-Wall", "-Werror"]))
     assert pr.returncode == 0 and pr.stderr == "", (pr.stdout, pr.stderr)
     m = re.search(r"devbuf_host: ok \((\d+) allocations, (\d+) frees\)", pr.stdout)
     assert m and int(m.group(1)) == int(m.group(2)) > 0, pr.stdout

@@ -1,26 +1,20 @@
 """The DEVICE source (ecloop_amd/csrc/*.h) compiled for the host with g++ and checked against the oracle on the CPU:
 covers the kernels' arithmetic / hashing / probe logic without a GPU (the -m gpu tests cover the generated code)."""
 import ctypes as C
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
 import limb_cases
 import orc
+from support import host_lib
 from synth import synth_bloom_words
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def D(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("devhost") / "libdevhost.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so,
-                    os.path.join(ROOT, "ecloop_amd", "csrc", "tools", "devsrc_host.cpp")], check=True)
-    return C.CDLL(so)
+    return host_lib(tmp_path_factory, "devsrc_host.cpp")
 
 
 def test_field(D):

@@ -7,23 +7,18 @@ leaves in [p, 2p) with and without bit 24 in limb 8, the top of y swept over the
 sets of tests/limb_cases.py, which this test writes to a file: x at magnitudes 1 .. 4, y at 1 .. 3, every pattern of `element` at
 the magnitude ceilings, the weak-pass targets and the table of k p +- d included.  What the program returns for those - hash160, parity,
 index - is then compared with the oracle's hash160 of (x mod p, y mod p) and with bloom.h's index formula in Python integers."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import emit33_cases
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "ecloop_amd", "csrc", "tools", "emit33_host.cpp")
+from support import host_program
 
 
 @pytest.fixture(scope="module")
 def prog(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("emit33") / "emit33_host")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-o", exe, SRC], check=True)
-    return exe
+    return host_program(tmp_path_factory.mktemp("emit33"), "emit33_host.cpp", ["-O2"], sanitize=False)
 
 
 def test_builtin_cases_agree_with_the_general_path(prog):

@@ -7,7 +7,6 @@ import hashlib
 import os
 import random
 import re
-import shutil
 import subprocess
 import sys
 
@@ -16,8 +15,8 @@ import pytest
 
 import eth_ref
 import orc
+from support import ROOT, cli, host_lib, kept_assembly, words8
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 # private key -> Ethereum address
@@ -38,16 +37,9 @@ def test_the_yardstick_is_sha3_with_another_pad_byte_and_gives_the_known_address
 
 @pytest.fixture(scope="module")
 def E(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("ethhost") / "libethhost.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so,
-                    os.path.join(ROOT, "ecloop_amd", "csrc", "tools", "eth_host.cpp")], check=True)
-    lib = C.CDLL(so)
+    lib = host_lib(tmp_path_factory, "eth_host.cpp")
     lib.eh_eth_many.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     return lib
-
-
-def words8(v):
-    return [(v >> (32 * i)) & 0xFFFFFFFF for i in range(8)]
 
 
 def device_eth(E, xs, ys):
@@ -80,13 +72,6 @@ def test_header_declares_the_flag_and_the_entry_point():
     assert "eth is searched alone" in header.lower()
     from ecloop_amd import capi
     assert capi.ETH == 64 and "ecl_hip_verify_eth" in capi.EXPORTS and capi.label_of(3) == "eth"
-
-
-@pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
 
 
 def test_cli_help_names_the_eth_letter_and_mixed_type_strings_are_refused(cli):
@@ -134,12 +119,8 @@ def test_eth_kernels_keep_scratch_out_of_their_loops_and_the_which_loop_is_small
     the image loop inside it; k_mul_check_eth: window, sum and walk-back loops).  The `which` loop of k_add_eth<false> - one key: curve
     arithmetic, normalisation, Keccak, probe 0 - is at most 5600 VALU instructions: ~770 for everything but the hash (the `which` loop of
     -a c less its hash160, profiles/r07_static_mix.json), ~35 for y, and a Keccak of at most 4800 (24 rounds x 200)."""
-    from ecloop_amd.build import ASM, build_library
     import isa_mix
-    if shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc"):
-        build_library()
-    if not os.path.exists(ASM):
-        pytest.skip("no hipcc and no kept assembly: nothing to analyse")
+    ASM = kept_assembly()
     now = isa_mix.analyse_eth(ASM)
     assert set(now) == set(isa_mix.ETH_KERNELS) == {"-a e", "-a e -endo", "mul -a e"}
     for label, a in now.items():

@@ -3,17 +3,15 @@ points), geometries and continuation, the insert walk's filter bit for bit again
 engine.bsgs_search and the CLI with keys planted at every edge of the windows, a thin filter whose false positives are the yardstick's,
 and the coverage check on both new contexts.  Every GPU-using subprocess runs under its own time limit."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import orc
 import pub_ref
+from support import rec_set, run_cli
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ONES = np.full(64, 0xFFFFFFFFFFFFFFFF, np.uint64)
 P, N = orc.P, orc.N
 T_KEY = 0xdc2a04  # the origin of most tests: O = T_KEY G
@@ -31,10 +29,6 @@ def insert_device(nwords, offs=1):
     d = Device(0, a33=False, pub=True, insert=True, ord_offs=offs)
     d.set_bloom(np.zeros(nwords, np.uint64))
     return d
-
-
-def rec_set(recs, base=0):
-    return sorted((base + int(r["key_offset"]), int(r["endo"]), int(r["compressed"]), tuple(int(v) for v in r["h160"])) for r in recs)
 
 
 def walk_x(k0, step, count):
@@ -194,11 +188,11 @@ def compressed_of(k):
     return pub_ref.compressed(k)
 
 
-def run_cli(args, timeout=120):
+def run_bsgs(args):
+    """-> the `pub: ` lines in the order they were printed, stderr"""
     from ecloop_amd.build import build_host_cli
-    pr = subprocess.run(["timeout", "-k", "10", str(timeout), build_host_cli(), "bsgs"] + args, stdin=subprocess.DEVNULL, capture_output=True, text=True)
-    assert pr.returncode == 0, (pr.returncode, pr.stderr[-2000:])
-    return [l for l in pr.stdout.splitlines() if l.startswith("pub: ")], pr.stderr
+    r = run_cli(build_host_cli(), ["bsgs"] + args, hard_limit=120)
+    return [l for l in r.stdout.splitlines() if l.startswith("pub: ")], r.stderr
 
 
 def test_end_to_end_keys_at_every_edge(tmp_path):
@@ -234,16 +228,16 @@ def test_end_to_end_keys_at_every_edge(tmp_path):
     listed = tmp_path / "targets.txt"
     listed.write_text("".join(compressed_of(key) + "\n" for key in keys + [b + 1]))
     out = tmp_path / "found.txt"
-    lines, err = run_cli(["-k", str(listed), "-r", "%x:%x" % (a, b), "-b", str(beta), "-o", str(out)])
+    lines, err = run_bsgs(["-k", str(listed), "-r", "%x:%x" % (a, b), "-b", str(beta), "-o", str(out)])
     assert lines == [pub_ref.found_line(key) for key in keys], (lines, err)
     assert err.count("not found") == 1 and compressed_of(b + 1) + " not found" in err
     assert out.read_text().splitlines() == ["pub\t%s\t%064x" % (compressed_of(key), key) for key in keys]
-    lines, err = run_cli(["-k", compressed_of(b2), "-r", "%x:%x" % (a, b2), "-b", str(beta)])
+    lines, err = run_bsgs(["-k", compressed_of(b2), "-r", "%x:%x" % (a, b2), "-b", str(beta)])
     assert lines == [pub_ref.found_line(b2)] and "not found" not in err
-    lines, err = run_cli(["-k", compressed_of(b2 + 1), "-r", "%x:%x" % (a, b2), "-b", str(beta)])
+    lines, err = run_bsgs(["-k", compressed_of(b2 + 1), "-r", "%x:%x" % (a, b2), "-b", str(beta)])
     assert lines == [] and compressed_of(b2 + 1) + " not found" in err and "%d / %d" % (steps, steps) in err.replace(",", "")
     # the default beta and filter
-    lines, err = run_cli(["-k", compressed_of(keys[4]), "-r", "%x:%x" % (a, b)])
+    lines, err = run_bsgs(["-k", compressed_of(keys[4]), "-r", "%x:%x" % (a, b)])
     assert lines == [pub_ref.found_line(keys[4])]
 
 

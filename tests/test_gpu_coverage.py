@@ -7,17 +7,15 @@ import hashlib
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import orc
+from support import GOLD, cli, counts, rec_set, run_cli
 from synth import synth_bloom_words
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
 G = json.load(open(os.path.join(GOLD, "golden.json")))["cases"]
 ONES = np.full(64, 0xFFFFFFFFFFFFFFFF, np.uint64)
 SPARSE = synth_bloom_words(1 << 16, 5, "a|(b&c)")  # 0.625^20: a hit every ~12000 hashes
@@ -189,7 +187,7 @@ def test_drop_round_fails_mul_and_mul_raw():
         now = d.coverage()
         assert now[0] - cov[0] == len(lines) and now[1] == cov[1] and now[2] - cov[2] < len(lines)
         recs, total = d.mul_batch_raw(lines, cap=1 << 16)
-        assert total == ngood and key(recs) == key(good)
+        assert total == ngood and rec_set(recs) == rec_set(good)
         # the raw records against the oracle on the SHA-256 scalars of their lines
         sc = [int.from_bytes(hashlib.sha256(l).digest(), "big") for l in lines]
         rc, out, no = orc.mul_batch(orc.OrcFilter(bloom_words=DENSER), sc, a33=True, a65=True)
@@ -198,10 +196,6 @@ def test_drop_round_fails_mul_and_mul_raw():
             sorted((orc.hex160(out[i].h160), orc.val(out[i].pk)) for i in range(no))
     finally:
         d.close()
-
-
-def key(recs):
-    return sorted((int(r["key_offset"]), int(r["endo"]), int(r["compressed"]), tuple(int(v) for v in r["h160"])) for r in recs)
 
 
 def test_lookahead_never_publishes_a_sweep_that_miscounts():
@@ -215,7 +209,7 @@ def test_lookahead_never_publishes_a_sweep_that_miscounts():
         for j in range(9):  # job 0 launches, job 1 sweeps jobs 1 ... 8 (2^24 keys), 2 ... 8 are served from that sweep
             want, nw = p.add_range(A + j * JOB, JOB)
             got, ng = a.add_range(A + j * JOB, JOB)
-            assert ng == nw and key(got) == key(want), j
+            assert ng == nw and rec_set(got) == rec_set(want), j
         sweeps, swept, served, _ = a.lookahead_stats()
         req, cov, dev = a.coverage()
         assert sweeps == 1 and served == 8 and req == cov == 9 * JOB and dev >= cov
@@ -227,7 +221,7 @@ def test_lookahead_never_publishes_a_sweep_that_miscounts():
         for j in range(9, jobs):  # job 9 again, then the rest: launched, none served
             want, nw = p.add_range(A + j * JOB, JOB)
             got, ng = a.add_range(A + j * JOB, JOB)
-            assert ng == nw and key(got) == key(want), j
+            assert ng == nw and rec_set(got) == rec_set(want), j
         assert a.lookahead_stats()[2] == served
         req2, cov2, dev2 = a.coverage()
         assert req2 - req == (jobs - 8) * JOB and cov2 - cov == (jobs - 9) * JOB and dev2 >= cov2
@@ -235,29 +229,8 @@ def test_lookahead_never_publishes_a_sweep_that_miscounts():
         p.close(), a.close()
 
 
-@pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
-
-
-def run_cli(cli, args, out, stdin_path=None, **env):
-    pr = subprocess.run([cli] + args + ["-q", "-o", out], stdin=open(stdin_path, "rb") if stdin_path else subprocess.DEVNULL,
-                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, env=dict(os.environ, **env))
-    lines = sorted(l.rstrip("\n") for l in open(out)) if os.path.exists(out) else []
-    return pr.returncode, pr.stdout.decode(errors="replace"), pr.stderr.decode(errors="replace"), lines
-
-
 def digest(lines):
     return hashlib.sha256(("\n".join(lines) + "\n").encode()).hexdigest()
-
-
-def counts(stderr):
-    status = stderr.replace("\x1b[2K", "\r").split("\r")[-1].strip()
-    found, checked = status.split("~")[-1].split("/")
-    clean = lambda s: int("".join(c for c in s if c.isdigit()))
-    return clean(found), clean(checked)
 
 
 CASES = {"add": (["add", "-f", os.path.join(GOLD, "btc-puzzles-hash"), "-r", "8000:ffffff"], None, "make_add_8000_ffffff"),
@@ -270,15 +243,16 @@ def test_cli_stops_on_a_miscount_and_reports_coverage(cli, tmp_path, case):
     g = G[gold]
     # the hook (armed on every context: `mul` hands its one batch to either of its two): exit status 1, the library's text on stderr,
     # no found line written
-    rc, _, err, lines = run_cli(cli, args, str(tmp_path / "drop.txt"), stdin_path, ECLOOP_HIP_TEST_DROP_ROUND="1")
-    assert rc == 1 and "[!] " in err and "did not hash every key" in err, err[-500:]
-    assert lines == []
+    r = run_cli(cli, args, out=str(tmp_path / "drop.txt"), stdin_path=stdin_path, env={"ECLOOP_HIP_TEST_DROP_ROUND": "1"}, check=False)
+    assert r.returncode == 1 and "[!] " in r.stderr and "did not hash every key" in r.stderr, r.stderr[-500:]
+    assert r.lines == []
     # without it: the found lines and status counters of the golden run, and no coverage line unless asked for
-    rc, out, err, lines = run_cli(cli, args, str(tmp_path / "plain.txt"), stdin_path)
-    assert rc == 0 and len(lines) == g["count"] and digest(lines) == g["sha256_sorted"] and counts(err) == (g["status_found"], g["status_checked"])
-    assert "coverage" not in out + err
-    rc, out, err, lines = run_cli(cli, args, str(tmp_path / "stats.txt"), stdin_path, ECLOOP_HIP_STATS="1")
-    assert rc == 0 and digest(lines) == g["sha256_sorted"]  # (the stats lines follow the status line on stderr)
+    r = run_cli(cli, args, out=str(tmp_path / "plain.txt"), stdin_path=stdin_path, check=False)
+    assert r.returncode == 0 and len(r.lines) == g["count"] and digest(r.lines) == g["sha256_sorted"] and counts(r.status) == (g["status_found"], g["status_checked"])
+    assert "coverage" not in r.stdout + r.stderr
+    r = run_cli(cli, args, out=str(tmp_path / "stats.txt"), stdin_path=stdin_path, env={"ECLOOP_HIP_STATS": "1"}, check=False)
+    out, err = r.stdout, r.stderr
+    assert r.returncode == 0 and digest(r.lines) == g["sha256_sorted"]  # (the stats lines follow the status line on stderr)
     pat = r"^gpu (\d+) coverage: requested (\d+), covered (\d+), device (\d+)$" if case == "add" else \
         r"^mul context (\d+) coverage: requested (\d+), covered (\d+), device (\d+)$"
     found = re.findall(pat, out if case == "add" else err, re.M)

@@ -13,11 +13,10 @@ import pytest
 
 import eth_ref
 import orc
+from support import GOLD, cli, counts, rec_set, run_cli
 from synth import synth_bloom_words
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
 ONES = np.full(64, 0xFFFFFFFFFFFFFFFF, np.uint64)
 KNOWN = {1: "7e5f4552091a69125d5dfcb7b8c2659029395bdf", 2: "2b5ad5c4795c026514f8317c7a215e218dccd6cf",
          0xdc2a04: "d2c71c0b28f045d0e6facc19a3a6a81a85a17ce4", 0x8000: "8af7c4e8e5f28db7cd19ad12818458d73547d2ec",
@@ -72,10 +71,6 @@ def all_records(endo, start, nkeys, offs, **types):
         d.close()
 
 
-def rec_key(a):
-    return sorted((int(r["key_offset"]), int(r["endo"]), int(r["compressed"]), tuple(int(v) for v in r["h160"])) for r in a)
-
-
 @pytest.mark.parametrize("endo", [False, True], ids=["plain", "endo"])
 @pytest.mark.parametrize("start,nkeys,offs", RANGES, ids=["contiguous", "stride128"])
 def test_every_key_and_image_once_with_the_right_address(endo, start, nkeys, offs):
@@ -95,7 +90,7 @@ def test_every_key_and_image_once_with_the_right_address(endo, start, nkeys, off
     for (off, e), r in zip(got, recs):
         k = calc_priv(start, 1 << offs, off, e)
         assert [int(v) for v in r["h160"]] == eth_ref.eth_words(*orc.point_of(k)), (off, e)
-    assert rec_key(u_before) == rec_key(u_after) and len(u_before) == nkeys * imgs
+    assert rec_set(u_before) == rec_set(u_after) and len(u_before) == nkeys * imgs
     assert all(int(r["compressed"]) == 0 for r in u_after)
 
 
@@ -123,47 +118,22 @@ def test_drop_round_fails_an_eth_call():
         d.close()
 
 
-@pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
-
-
-def run(cli, args, stdin_path=None, env=None):
-    e = dict(os.environ, **(env or {}))
-    pr = subprocess.run([cli] + args, stdin=open(stdin_path, "rb") if stdin_path else subprocess.DEVNULL, stdout=subprocess.PIPE,
-                        stderr=subprocess.PIPE, timeout=600, env=e)
-    assert pr.returncode == 0, pr.stderr.decode(errors="replace")[-2000:]
-    err = pr.stderr.decode(errors="replace")
-    status = err.replace("\x1b[2K", "\r").split("\r")[-1].strip()
-    stdout = pr.stdout.decode(errors="replace")
-    found = sorted(l for l in stdout.splitlines() if ": " in l and " <- " in l)
-    return found, status, stdout, err
-
-
-def counts(status):
-    found, checked = status.split("~")[-1].split("/")
-    clean = lambda s: int("".join(c for c in s if c.isdigit()))
-    return clean(found), clean(checked)
-
-
 def test_cli_add_finds_the_eth_lines_from_a_0x_list_and_a_blf(cli, tmp_path):
     lst = tmp_path / "eth.txt"
     lst.write_text("0x%s\n0x%s\n" % (KNOWN[0xdc2a04], KNOWN[0xffffff]))
     want = sorted("eth: %s <- %064x" % (KNOWN[k], k) for k in (0xdc2a04, 0xffffff))
-    found, status, out, _ = run(cli, ["add", "-f", str(lst), "-a", "e", "-r", "800000:ffffff"])
-    assert found == want and counts(status) == (2, 8388608), (out, status)
-    assert "~ endo: 0 ~ eth: 1 | filter: list (2)" in out
-    found, _, out, err = run(cli, ["add", "-f", str(lst), "-a", "e", "-r", "800000:ffffff"], env={"ECLOOP_HIP_STATS": "1"})
-    assert found == want and "list: 2 entries" in err  # both 0x lines were read
-    assert re.search(r"coverage: requested 8388608, covered 8388608, device \d+", out), out
+    r = run_cli(cli, ["add", "-f", str(lst), "-a", "e", "-r", "800000:ffffff"])
+    assert r.found == want and counts(r.status) == (2, 8388608), (r.stdout, r.status)
+    assert "~ endo: 0 ~ eth: 1 | filter: list (2)" in r.stdout
+    r = run_cli(cli, ["add", "-f", str(lst), "-a", "e", "-r", "800000:ffffff"], env={"ECLOOP_HIP_STATS": "1"})
+    assert r.found == want and "list: 2 entries" in r.stderr  # both 0x lines were read
+    assert re.search(r"coverage: requested 8388608, covered 8388608, device \d+", r.stdout), r.stdout
     blf = str(tmp_path / "eth.blf")
     subprocess.run([cli, "blf-gen", "-a", "e", "-n", "1000", "-o", blf], stdin=open(str(lst), "rb"), stdout=subprocess.PIPE, check=True, timeout=120)
-    found, status, out, _ = run(cli, ["add", "-f", blf, "-a", "e", "-r", "800000:ffffff"])
-    assert "filter: bloom" in out and found == want and counts(status) == (2, 8388608)
-    found, status, out, _ = run(cli, ["add", "-f", str(lst), "-a", "e", "-endo", "-r", "800000:ffffff"])
-    assert found == want and counts(status) == (2, 8388608 * 6) and "~ endo: 1 ~ eth: 1 |" in out
+    r = run_cli(cli, ["add", "-f", blf, "-a", "e", "-r", "800000:ffffff"])
+    assert "filter: bloom" in r.stdout and r.found == want and counts(r.status) == (2, 8388608)
+    r = run_cli(cli, ["add", "-f", str(lst), "-a", "e", "-endo", "-r", "800000:ffffff"])
+    assert r.found == want and counts(r.status) == (2, 8388608 * 6) and "~ endo: 1 ~ eth: 1 |" in r.stdout
     # without -a e the same file holds no entry
     pr = subprocess.run([cli, "add", "-f", str(lst), "-r", "800000:ffffff"], stdin=subprocess.DEVNULL, capture_output=True, text=True, timeout=120)
     assert pr.returncode != 0 and "no hashes in filter file" in pr.stderr
@@ -178,17 +148,17 @@ def test_mul_mul_raw_and_rnd_report_the_planted_addresses(cli, tmp_path):
     planted = ["eth: %s <- %064x" % (eth_of(k), k) for k in [orc.sn_from_hex(l) for l in picked] + [pk_of_phrase(p) for p in phrases]]
     lst = tmp_path / "planted.txt"
     lst.write_text("".join("0x" + l.split()[1] + "\n" for l in planted))
-    found, status, out, _ = run(cli, ["mul", "-f", str(lst), "-a", "e"], stdin_path=os.path.join(GOLD, "mul_scalars.txt"))
-    assert found == sorted(planted[:3]), out
-    assert "~ eth: 1 |" in out
+    r = run_cli(cli, ["mul", "-f", str(lst), "-a", "e"], stdin_path=os.path.join(GOLD, "mul_scalars.txt"))
+    assert r.found == sorted(planted[:3]), r.stdout
+    assert "~ eth: 1 |" in r.stdout
     ph = tmp_path / "phrases.txt"
     ph.write_bytes(b"\n".join(others[:1000] + phrases + others[1000:]) + b"\n")
-    found, status, out, _ = run(cli, ["mul", "-raw", "-f", str(lst), "-a", "e"], stdin_path=str(ph))
-    assert found == sorted(planted[3:]), out
+    r = run_cli(cli, ["mul", "-raw", "-f", str(lst), "-a", "e"], stdin_path=str(ph))
+    assert r.found == sorted(planted[3:]), r.stdout
     one = tmp_path / "dc.txt"
     one.write_text("0x%s\n" % KNOWN[0xdc2a04])
-    found, status, out, _ = run(cli, ["rnd", "-f", str(one), "-a", "e", "-seed", "eth", "-r", "800000:ffffff", "-d", "0:23"])
-    assert found == ["eth: %s <- %064x" % (KNOWN[0xdc2a04], 0xdc2a04)], out
+    r = run_cli(cli, ["rnd", "-f", str(one), "-a", "e", "-seed", "eth", "-r", "800000:ffffff", "-d", "0:23"])
+    assert r.found == ["eth: %s <- %064x" % (KNOWN[0xdc2a04], 0xdc2a04)], r.stdout
 
 
 def test_lookahead_keeps_eth_and_addr65_contexts_apart():

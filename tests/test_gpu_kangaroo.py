@@ -4,18 +4,16 @@ end through engine.kangaroo_search (statistics equal to the yardstick's driver) 
 own time limit."""
 import ctypes as C
 import functools
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import kangaroo_ref as ref
 import orc
+from support import run_cli
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P, N = orc.P, orc.N
 KEY, BASE = 0x123456789, 0x100000000
 
@@ -203,13 +201,6 @@ def test_end_to_end_exact(which):
     assert want_key == key == got_key and got == want
 
 
-def run_cli(args, timeout=120):
-    from ecloop_amd.build import build_host_cli
-    pr = subprocess.run(["timeout", "-k", "10", str(timeout), build_host_cli(), "kangaroo"] + args, stdin=subprocess.DEVNULL, capture_output=True, text=True)
-    assert pr.returncode == 0, (pr.returncode, pr.stdout[-2000:], pr.stderr[-2000:])
-    return pr
-
-
 def jumps_of(stderr):
     return int(re.sub(r"\D", "", re.findall(r"jumps: ([^~]+) ~", stderr)[-1]))
 
@@ -219,19 +210,20 @@ def test_end_to_end_defaults_through_the_cli(tmp_path):
     64 * 2 sqrt(W) = 2^31 jumps (seed 7: see the figure the run prints; the limit is the condition); a target outside the range ends with
     `not found within ... jumps` and status 0 at -max 4"""
     from ecloop_amd import engine
+    from ecloop_amd.build import build_host_cli
     a, b = 0x1000000000000, 0x1000000000000 + (1 << 48) - 1
     key = a + 0x5EED5EED5EED
     plan = engine.kangaroo_plan(a, b)
     assert (plan["herd_log2"], plan["dp"]) == (20, 3)
     out = tmp_path / "found.txt"
-    pr = run_cli(["-k", compressed_of(key), "-r", "%x:%x" % (a, b), "-seed", "7", "-o", str(out)])
+    pr = run_cli(build_host_cli(), ["kangaroo", "-k", compressed_of(key), "-r", "%x:%x" % (a, b), "-seed", "7", "-o", str(out)], hard_limit=120)
     line = "pub: %s <- %064x" % (compressed_of(key), key)
     assert line in pr.stdout.split("\n") and out.read_text() == "pub\t%s\t%064x\n" % (compressed_of(key), key)
     jumps = jumps_of(pr.stderr)
     print("jumps to the key:", jumps)
     assert 0 < jumps < 64 * 2 * (1 << 24)
     outside = b + (1 << 60)
-    pr = run_cli(["-k", compressed_of(outside), "-r", "%x:%x" % (a, b), "-seed", "7", "-max", "4"])
+    pr = run_cli(build_host_cli(), ["kangaroo", "-k", compressed_of(outside), "-r", "%x:%x" % (a, b), "-seed", "7", "-max", "4"], hard_limit=120)
     limit = engine.kangaroo_give_up(plan, 4)
     m = re.search(r"^%s not found within (\d+) jumps$" % compressed_of(outside), pr.stderr, re.M)
     assert m and limit <= int(m.group(1)) < limit + (plan["round_steps"] << plan["herd_log2"]) and "pub:" not in pr.stdout

@@ -14,10 +14,10 @@ import pytest
 import kdf_ref
 import mul_ref
 import orc
+from support import cli
 from walk_ref import canon, difference
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ONES = np.full(64, 0xFFFFFFFFFFFFFFFF, np.uint64)
 LENGTHS = list(range(0, 301)) + [407, 408, 409, 1000, 4000]
 E_ARG, E_SELFTEST = -1, -7
@@ -31,13 +31,6 @@ def limbs_of_digests(digests):
 
 def key(a):
     return sorted(zip(a["key_offset"].tolist(), a["compressed"].tolist(), map(tuple, a["h160"].tolist())))
-
-
-@pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
 
 
 def test_every_valid_combination_opens_and_passes_its_selftest_and_the_five_companions_are_refused():

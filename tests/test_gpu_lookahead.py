@@ -10,14 +10,11 @@ import numpy as np
 import pytest
 
 import orc
+from support import rec_set
 from synth import synth_bloom_words
 
 pytestmark = pytest.mark.gpu
 JOB = 1 << 21  # MAX_JOB_SIZE, main.c:16
-
-
-def key(recs):
-    return sorted((int(r["key_offset"]), int(r["endo"]), int(r["compressed"]), tuple(int(v) for v in r["h160"])) for r in recs)
 
 
 def plain_device(words, **kw):
@@ -52,7 +49,7 @@ def test_contiguous_jobs_get_the_records_of_their_own_launch(hint):
         for j in range(jobs):
             want, nw = p.add_range(A + j * JOB, JOB, cap=4096)
             got, ng = a.add_range(A + j * JOB, JOB, cap=4096)
-            assert ng == nw == len(want) and key(got) == key(want), j
+            assert ng == nw == len(want) and rec_set(got) == rec_set(want), j
         sweeps, swept, served_calls, served_keys = a.lookahead_stats()
         assert sweeps >= 1 and served_keys == served_calls * JOB
         if hint:
@@ -82,7 +79,7 @@ def test_end_of_range_is_never_passed_and_the_stride_is_honoured():
         for j in range(11):
             want, nw = p.add_range(A + ((j * job) << offs), job, cap=1 << 14)
             got, ng = a.add_range(A + ((j * job) << offs), job, cap=1 << 14)
-            assert ng == nw and key(got) == key(want) and nw > 100, j
+            assert ng == nw and rec_set(got) == rec_set(want) and nw > 100, j
         sweeps, swept, served_calls, _ = a.lookahead_stats()
         assert (sweeps, swept, served_calls) == (1, 10 * job, 10)
     finally:
@@ -106,7 +103,7 @@ def test_jobs_that_do_not_continue_fall_back_to_their_own_launch():
         for i, (s, n) in enumerate(calls):
             want, nw = p.add_range(s, n, cap=4096)
             got, ng = a.add_range(s, n, cap=4096)
-            assert ng == nw and key(got) == key(want), (i, hex(s), n)
+            assert ng == nw and rec_set(got) == rec_set(want), (i, hex(s), n)
         sweeps, swept, served_calls, served_keys = a.lookahead_stats()
         assert sweeps == 1 and swept == 43 * JOB and served_calls >= 6
     finally:
@@ -130,7 +127,7 @@ def test_a_call_with_too_small_a_buffer_overflows_and_fetches_from_the_sweep():
             rc = a.lib.ecl_hip_add_range(a.h, s.ctypes.data, JOB, out.ctypes.data, 50, C.byref(n))
             assert rc == capi.E_OVERFLOW and n.value == nw > 50
             rest = a.fetch_found(50, n.value - 50)
-            assert len(rest) == n.value - 50 and key(np.concatenate([out, rest])) == key(want)
+            assert len(rest) == n.value - 50 and rec_set(np.concatenate([out, rest])) == rec_set(want)
             assert len(a.fetch_found(n.value, 10)) == 0
         assert a.lookahead_stats()[2] == 7
     finally:
@@ -148,7 +145,7 @@ def test_a_dense_filter_is_swept_in_small_pieces_or_not_at_all():
             for j in range(40):
                 want, nw = p.add_range(A + j * job, job, cap=1 << 16)
                 got, ng = a.add_range(A + j * job, job, cap=1 << 16)
-                assert ng == nw and key(got) == key(want), j
+                assert ng == nw and rec_set(got) == rec_set(want), j
             sweeps, swept, served_calls, _ = a.lookahead_stats()
             assert (sweeps > 2 and served_calls > 20 and swept / sweeps <= (1 << 25)) if expect_sweeps else (sweeps == 0 and served_calls == 0)
         finally:
@@ -177,7 +174,7 @@ def test_worker_threads_on_several_contexts_share_the_sweeps(contexts):
                     return
                 got, n = d.add_range(A + j * JOB, JOB, cap=4096)
                 assert n == len(got)
-                results[j] = key(got)
+                results[j] = rec_set(got)
         except Exception as e:  # noqa: BLE001
             errors.append(e)
 
@@ -188,7 +185,7 @@ def test_worker_threads_on_several_contexts_share_the_sweeps(contexts):
         assert not errors, errors
         for j in range(jobs):
             want, _ = p.add_range(A + j * JOB, JOB, cap=4096)
-            assert results[j] == key(want), j
+            assert results[j] == rec_set(want), j
         stats = [d.lookahead_stats() for d in devs]
         assert sum(s[1] for s in stats) <= jobs * JOB and sum(s[2] for s in stats) >= jobs // 4  # (typically > 95 %: how the threads interleave decides)
     finally:
@@ -212,7 +209,7 @@ def test_contexts_with_different_filters_do_not_share():
             for p, a in ((p1, a1), (p2, a2), (p3, a3)):
                 want, nw = p.add_range(A + j * JOB, JOB, cap=1 << 14)
                 got, ng = a.add_range(A + j * JOB, JOB, cap=1 << 14)
-                assert ng == nw and key(got) == key(want), j
+                assert ng == nw and rec_set(got) == rec_set(want), j
         # every context swept for itself (a shared group would have answered the later contexts from the first one's sweeps)
         assert all(a.lookahead_stats()[0] >= 1 and a.lookahead_stats()[2] >= 4 for a in (a1, a2, a3))
         # ... while a fourth context with the first one's filter - uploaded from another host copy - does join its group
@@ -222,7 +219,7 @@ def test_contexts_with_different_filters_do_not_share():
             for j in range(12, 40):
                 got, ng = (a1 if j % 2 else a4).add_range(A + j * JOB, JOB, cap=1 << 14)
                 want, nw = p1.add_range(A + j * JOB, JOB, cap=1 << 14)
-                assert ng == nw and key(got) == key(want), j
+                assert ng == nw and rec_set(got) == rec_set(want), j
             assert a4.lookahead_stats()[2] >= 10 and a4.lookahead_stats()[0] + a1.lookahead_stats()[0] <= 4
         finally:
             a4.close()

@@ -3,8 +3,6 @@ addresses (tests/eth_ref.py through test_gpu_prefix.eth_records) and a table bui
 split and strided calls, ecl_hip_diag_bloom against the host build of mask.h, the ABI's refusals, the split-key walk, and the CLI's found
 lines against the text yardstick tests/mask_ref.py.  Every GPU-using subprocess runs under its own time limit."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,10 +10,10 @@ import pytest
 import eth_ref
 import mask_ref as R
 import orc
+from support import cli, host_lib, run_cli
 from test_gpu_prefix import NKEYS, START, eth_records
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TYPES = {"e": dict(endo=False), "e-endo": dict(endo=True)}
 ZERO = [(0, 0)]
 
@@ -139,11 +137,9 @@ def test_split_calls_and_a_strided_call():
         d.close()
 
 
-def test_diag_bloom_runs_the_mask_test(tmp_path):
+def test_diag_bloom_runs_the_mask_test(tmp_path_factory):
     """the synthetic cases of the CPU test (tests/mask_ref.py: mask_filter_cases): the device's answers equal the host build's"""
-    so = str(tmp_path / "libmaskhost.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, os.path.join(ROOT, "ecloop_amd", "csrc", "tools", "mask_host.cpp")], check=True)
-    H = C.CDLL(so)
+    H = host_lib(tmp_path_factory, "mask_host.cpp")
     H.mk_test_many.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
     d = open_mask("e")
     try:
@@ -270,22 +266,6 @@ def test_engine_prefix_search_masked_with_and_without_an_origin():
 
 # ---- the CLI
 
-@pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
-
-
-def run(cli, args, env=None):
-    pr = subprocess.run([cli] + args, stdin=subprocess.DEVNULL, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300, env=dict(os.environ, **(env or {})))
-    err = pr.stderr.decode(errors="replace")
-    assert pr.returncode == 0, err[-2000:]
-    status = err.replace("\x1b[2K", "\r").split("\r")[-1].strip()
-    out = pr.stdout.decode(errors="replace")
-    return sorted(l for l in out.splitlines() if ": " in l and " <- " in l), status, out
-
-
 def patterns_from(values):
     """three patterns cut from real addresses: head 2 + * + tail 3, a ? hole, and a pure suffix of 5"""
     a, b, c = (R.eth(v) for v in values)
@@ -303,9 +283,9 @@ def test_cli_add_prints_the_lines_the_yardstick_expects(cli, tmp_path):
                       for r in recs if R.first_match(patterns, R.value_of(r[1])) is not None)
         assert len(want) >= 3
         outfile = tmp_path / ("found-%s.txt" % name)
-        found, status, out = run(cli, ["add", "-p", str(f), "-a", "e", "-r", "%x:%x" % (START, START + NKEYS - 1), "-o", str(outfile)] + extra)
-        assert found == want, (out, status)
-        assert "~ eth: 1 | filter: prefix (3 patterns, 3 mask entries)" in out and "edge: 0" in status
+        r = run_cli(cli, ["add", "-p", str(f), "-a", "e", "-r", "%x:%x" % (START, START + NKEYS - 1), "-o", str(outfile)] + extra, timeout=300)
+        assert r.found == want, (r.stdout, r.status)
+        assert "~ eth: 1 | filter: prefix (3 patterns, 3 mask entries)" in r.stdout and "edge: 0" in r.status
         assert sorted(outfile.read_text().splitlines()) == sorted(l.replace("eth: ", "eth\t").replace(" <- ", "\t").replace(" 0x", "\t0x") for l in want)
 
 
@@ -320,9 +300,9 @@ def test_cli_add_split_key(cli, tmp_path):
     want = sorted("eth: %040x <- %064x %s split:0" % (v, k, R.eth(v)) for k, v in addr.items() if R.first_match(patterns, v) is not None)
     assert len(want) >= 3
     pub = "%02x%064x" % (2 | Q[1] & 1, Q[0])
-    found, status, out = run(cli, ["add", "-p", str(f), "-k", pub, "-a", "e", "-r", "%x:%x" % (START, START + NKEYS - 1)])
-    assert found == want and "PARTIAL keys for %s" % pub in out and "edge: 0" in status, (out, status)
-    for line in found:  # the partial key, combined with k_Q, is the key of the printed address
+    r = run_cli(cli, ["add", "-p", str(f), "-k", pub, "-a", "e", "-r", "%x:%x" % (START, START + NKEYS - 1)], timeout=300)
+    assert r.found == want and "PARTIAL keys for %s" % pub in r.stdout and "edge: 0" in r.status, (r.stdout, r.status)
+    for line in r.found:  # the partial key, combined with k_Q, is the key of the printed address
         _, h, _, part, a, sp = line.split()
         final = splitkey_combine(KQ, int(part, 16), int(sp.split(":")[1]))
         assert R.eth(R.value_of(eth_ref.eth_words(*orc.point_of(final)))) == a == "0x" + h
@@ -335,12 +315,13 @@ def test_cli_rnd_searches_the_window_it_prints(cli, tmp_path):
     f.write_text("\n".join(patterns) + "\n")
     inside = sorted("eth: %040x <- %064x %s" % (R.value_of(r[1]), START + r[0], R.eth(R.value_of(r[1]))) for r in recs if R.first_match(patterns, R.value_of(r[1])) is not None)
     assert len(inside) >= 3
-    found, status, out = run(cli, ["rnd", "-p", str(f), "-a", "e", "-seed", "mask", "-r", "%x:%x" % (START, START + NKEYS - 1), "-d", "0:20"],
-                             env={"ECLOOP_HIP_RND_WINDOWS": "1"})
+    r = run_cli(cli, ["rnd", "-p", str(f), "-a", "e", "-seed", "mask", "-r", "%x:%x" % (START, START + NKEYS - 1), "-d", "0:20"],
+                env={"ECLOOP_HIP_RND_WINDOWS": "1"}, timeout=300)
+    out = r.stdout
     bounds = [int(l.replace(" ", ""), 16) for l in out.splitlines() if len(l.replace(" ", "")) == 64 and set(l) <= set("0123456789abcdef ")]
     assert bounds[:2] == [START, START + NKEYS - 1], out  # the window it prints: bits 0 ... 19 cleared / set, clamped to the range
-    assert set(inside) <= set(found), (out, status)  # (rnd walks full-size jobs: 2^21 keys from the window's first key)
-    for line in found:  # every line is a key of the walk with its own address, and the address matches a pattern
+    assert set(inside) <= set(r.found), (out, r.status)  # (rnd walks full-size jobs: 2^21 keys from the window's first key)
+    for line in r.found:  # every line is a key of the walk with its own address, and the address matches a pattern
         _, h, _, k, a = line.split()
         assert START <= int(k, 16) < START + (1 << 21)
         assert R.eth(R.value_of(eth_ref.eth_words(*orc.point_of(int(k, 16))))) == a == "0x" + h and R.first_match(patterns, int(h, 16)) is not None

@@ -11,11 +11,10 @@ import pytest
 
 import orc
 import p2sh_ref
+from support import GOLD, cli, counts, rec_set, run_cli
 from synth import synth_bloom_words
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
 ONES = np.full(64, 0xFFFFFFFFFFFFFFFF, np.uint64)
 KEY_DC = 0xDC2A04
 P2SH_DC = "45a41e75045f683ed5f71fec4b4322fcd263891b"
@@ -86,33 +85,7 @@ def test_every_key_type_and_image_once_with_the_right_hash(endo, start, nkeys, o
         # the same call without P2SH: identical addr33 / addr65 records
         if types != "s":
             base = all_records(types.replace("s", ""), endo, start, nkeys, offs)
-            key = lambda a: sorted((int(r["key_offset"]), int(r["endo"]), int(r["compressed"]), tuple(int(v) for v in r["h160"])) for r in a)
-            assert key(base) == key([r for r in recs if int(r["compressed"]) != 2]), types
-
-
-@pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
-
-
-def run(cli, args, stdin_path=None, out=None, env=None):
-    cmd = [cli] + args + (["-q", "-o", out] if out else [])
-    e = dict(os.environ, **(env or {}))
-    pr = subprocess.run(cmd, stdin=open(stdin_path, "rb") if stdin_path else subprocess.DEVNULL, stdout=subprocess.PIPE,
-                        stderr=subprocess.PIPE, timeout=600, env=e)
-    assert pr.returncode == 0, pr.stderr.decode(errors="replace")[-2000:]
-    status = pr.stderr.decode(errors="replace").replace("\x1b[2K", "\r").split("\r")[-1].strip()
-    stdout = pr.stdout.decode(errors="replace")
-    found = sorted(l for l in stdout.splitlines() if ": " in l and " <- " in l)
-    return found, status, stdout
-
-
-def counts(status):
-    found, checked = status.split("~")[-1].split("/")
-    clean = lambda s: int("".join(c for c in s if c.isdigit()))
-    return clean(found), clean(checked)
+            assert rec_set(base) == rec_set([r for r in recs if int(r["compressed"]) != 2]), types
 
 
 @pytest.fixture(scope="module")
@@ -127,18 +100,18 @@ def test_cli_add_finds_the_p2sh_line(cli, hash_list, tmp_path):
     addr33 = "addr33: %s <- %s" % (orc.hex160(h33_of(KEY_DC)), key)
     p2sh = "p2sh: %s <- %s" % (P2SH_DC, key)
     for env in ({}, {"ECLOOP_HIP_SHARE_GPU": "2"}):
-        found, status, out = run(cli, ["add", "-f", hash_list, "-a", "s", "-r", "800000:ffffff"], env=env)
-        assert found == [p2sh] and counts(status) == (1, 8388608), (env, out, status)
-        assert "~ endo: 0 ~ p2sh: 1 | filter: list" in out
-        found, status, out = run(cli, ["add", "-f", hash_list, "-a", "cs", "-r", "800000:ffffff"], env=env)
-        assert found == sorted([addr33, p2sh]) and counts(status) == (2, 8388608), (env, out, status)
+        r = run_cli(cli, ["add", "-f", hash_list, "-a", "s", "-r", "800000:ffffff"], env=env)
+        assert r.found == [p2sh] and counts(r.status) == (1, 8388608), (env, r.stdout, r.status)
+        assert "~ endo: 0 ~ p2sh: 1 | filter: list" in r.stdout
+        r = run_cli(cli, ["add", "-f", hash_list, "-a", "cs", "-r", "800000:ffffff"], env=env)
+        assert r.found == sorted([addr33, p2sh]) and counts(r.status) == (2, 8388608), (env, r.stdout, r.status)
         f = str(tmp_path / ("o%d.txt" % len(env)))
-        _, status, _ = run(cli, ["add", "-f", hash_list, "-a", "cs", "-r", "800000:ffffff"], out=f, env=env)
+        r = run_cli(cli, ["add", "-f", hash_list, "-a", "cs", "-r", "800000:ffffff"], out=f, env=env)
         assert sorted(open(f).read().splitlines()) == sorted([addr33.replace(": ", "\t").replace(" <- ", "\t"), "p2sh\t%s\t%s" % (P2SH_DC, key)])
-        assert counts(status) == (2, 8388608)
+        assert counts(r.status) == (2, 8388608)
     # without `s` the banner is the one it always was
-    found, status, out = run(cli, ["add", "-f", hash_list, "-a", "c", "-r", "800000:ffffff"])
-    assert found == [addr33] and "p2sh" not in out and "~ endo: 0 | filter: list" in out
+    r = run_cli(cli, ["add", "-f", hash_list, "-a", "c", "-r", "800000:ffffff"])
+    assert r.found == [addr33] and "p2sh" not in r.stdout and "~ endo: 0 | filter: list" in r.stdout
 
 
 def test_list_mode_and_blf_give_the_same_p2sh_records(cli, hash_list, tmp_path):
@@ -157,8 +130,8 @@ def test_list_mode_and_blf_give_the_same_p2sh_records(cli, hash_list, tmp_path):
     assert n == 1 and got == ["p2sh: %s <- %064x" % (P2SH_DC, KEY_DC)]
     blf = str(tmp_path / "l.blf")
     subprocess.run([cli, "blf-gen", "-n", "1000000", "-o", blf], stdin=open(hash_list, "rb"), stdout=subprocess.PIPE, check=True)
-    found, status, out = run(cli, ["add", "-f", blf, "-a", "s", "-r", "800000:ffffff"])
-    assert "filter: bloom" in out and found == got and counts(status) == (1, 8388608)
+    r = run_cli(cli, ["add", "-f", blf, "-a", "s", "-r", "800000:ffffff"])
+    assert "filter: bloom" in r.stdout and r.found == got and counts(r.status) == (1, 8388608)
 
 
 def test_mul_and_mul_raw_report_the_planted_script_hashes(cli, tmp_path):
@@ -176,16 +149,16 @@ def test_mul_and_mul_raw_report_the_planted_script_hashes(cli, tmp_path):
         planted["p2sh: %s <- %064x" % (p2sh_ref.p2sh_hex(orc.hex160(h33_of(k))), k)] = None
     lst = tmp_path / "planted.txt"
     lst.write_text("".join(l.split()[1] + "\n" for l in planted))
-    found, status, out = run(cli, ["mul", "-f", str(lst), "-a", "s"], stdin_path=os.path.join(GOLD, "mul_scalars.txt"))
-    assert found == sorted(list(planted)[:3]), out
-    assert "~ p2sh: 1 |" in out
+    r = run_cli(cli, ["mul", "-f", str(lst), "-a", "s"], stdin_path=os.path.join(GOLD, "mul_scalars.txt"))
+    assert r.found == sorted(list(planted)[:3]), r.stdout
+    assert "~ p2sh: 1 |" in r.stdout
     ph = tmp_path / "phrases.txt"
     ph.write_bytes(b"\n".join(others[:250] + phrases + others[250:]) + b"\n")
-    found, status, out = run(cli, ["mul", "-raw", "-f", str(lst), "-a", "s"], stdin_path=str(ph))
-    assert found == sorted(list(planted)[3:]), out
+    r = run_cli(cli, ["mul", "-raw", "-f", str(lst), "-a", "s"], stdin_path=str(ph))
+    assert r.found == sorted(list(planted)[3:]), r.stdout
     # `-a cs`: the addr33 hashes of the same scalars are not in the list, so the same lines come back
-    found, _, _ = run(cli, ["mul", "-f", str(lst), "-a", "cs"], stdin_path=os.path.join(GOLD, "mul_scalars.txt"))
-    assert found == sorted(list(planted)[:3])
+    r = run_cli(cli, ["mul", "-f", str(lst), "-a", "cs"], stdin_path=os.path.join(GOLD, "mul_scalars.txt"))
+    assert r.found == sorted(list(planted)[:3])
 
 
 def test_lookahead_keeps_p2sh_and_addr33_contexts_apart():

@@ -5,9 +5,7 @@ Every GPU-using subprocess runs under its own time limit."""
 import ctypes as C
 import functools
 import hashlib
-import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,9 +14,9 @@ import eth_ref
 import orc
 import prefix_ref as R
 from fake_device import FakeDevice
+from support import cli, host_lib, run_cli
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 START, NKEYS = 0x8000, 4096
 TOP = R.TOP
 ONES = np.full(64, 0xFFFFFFFFFFFFFFFF, np.uint64)
@@ -191,11 +189,9 @@ def test_split_calls_and_a_strided_call():
         d.close()
 
 
-def test_diag_bloom_runs_the_two_stage_prefix_test(tmp_path):
+def test_diag_bloom_runs_the_two_stage_prefix_test(tmp_path_factory):
     """the synthetic boundary values of the CPU test (tests/prefix_ref.py: prefix_filter_cases): the device's answers equal the host build's"""
-    so = str(tmp_path / "libprefixhost.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, os.path.join(ROOT, "ecloop_amd", "csrc", "tools", "prefix_host.cpp")], check=True)
-    H = C.CDLL(so)
+    H = host_lib(tmp_path_factory, "prefix_host.cpp")
     H.px_test_many.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     d = open_prefix("c")
     try:
@@ -287,28 +283,12 @@ LO, HI = 0xD00000, 0xE00000  # -r d00000:dfffff: 2^20 keys
 
 
 @pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
-
-
-@pytest.fixture(scope="module")
 def hashes33():
     """the oracle's addr33 hashes of the 2^20 keys, as (n, 5) uint32 and as bytes"""
     from ecloop_amd import capi
     h33, _, ok = orc.mul_hash160_many(capi.limbs_array(range(LO, HI)), True, False)
     assert ok.all()
     return h33
-
-
-def run(cli, args, env=None):
-    pr = subprocess.run([cli] + args, stdin=subprocess.DEVNULL, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300, env=dict(os.environ, **(env or {})))
-    err = pr.stderr.decode(errors="replace")
-    assert pr.returncode == 0, err[-2000:]
-    status = err.replace("\x1b[2K", "\r").split("\r")[-1].strip()
-    out = pr.stdout.decode(errors="replace")
-    return sorted(l for l in out.splitlines() if ": " in l and " <- " in l), status, out
 
 
 def test_cli_add_prints_the_lines_the_yardstick_expects(cli, hashes33, tmp_path):
@@ -325,22 +305,22 @@ def test_cli_add_prints_the_lines_the_yardstick_expects(cli, hashes33, tmp_path)
     want = ["addr33: %s <- %s %s" % h for h in hits]
     assert "addr33: %040x <- %064x %s" % (known, KNOWN, R.p2pkh(known)) in want
     outfile = tmp_path / "found.txt"
-    found, status, out = run(cli, ["add", "-p", pattern, "-r", "%x:%x" % (LO, HI - 1), "-o", str(outfile)])
-    assert found == sorted(want), (out, status)
-    assert "filter: prefix (1 pattern, " in out and "edge: " in status
+    r = run_cli(cli, ["add", "-p", pattern, "-r", "%x:%x" % (LO, HI - 1), "-o", str(outfile)], timeout=300)
+    assert r.found == sorted(want), (r.stdout, r.status)
+    assert "filter: prefix (1 pattern, " in r.stdout and "edge: " in r.status
     assert sorted(outfile.read_text().splitlines()) == sorted("addr33\t%s\t%s\t%s" % h for h in hits)  # a fourth tab-separated field
     # the bc1q form (-a c): the same keys' P2WPKH addresses, six characters after the q
     bech = R.p2wpkh(known)[:10]
     top = known >> 130
     want = ["addr33: %040x <- %064x %s" % (R.value_of(h), LO + i, R.p2wpkh(R.value_of(h)))
             for i, h in enumerate(hashes33) if int(h[0]) >> 2 == top and R.p2wpkh(R.value_of(h)).startswith(bech)]
-    found, status, out = run(cli, ["add", "-p", bech, "-a", "c", "-r", "%x:%x" % (LO, HI - 1)])
-    assert found == sorted(want) and len(want) >= 1, (out, status)
+    r = run_cli(cli, ["add", "-p", bech, "-a", "c", "-r", "%x:%x" % (LO, HI - 1)], timeout=300)
+    assert r.found == sorted(want) and len(want) >= 1, (r.stdout, r.status)
     # a file of patterns, upper-case bech32 first: the address is written in the form of the first pattern it matches
     f = tmp_path / "patterns.txt"
     f.write_text("%s\n%s\n" % (bech.upper(), pattern))
-    found, status, out = run(cli, ["add", "-p", str(f), "-r", "%x:%x" % (LO, HI - 1)])
-    assert "addr33: %040x <- %064x %s" % (known, KNOWN, R.p2wpkh(known).upper()) in found and "prefix (2 patterns, " in out
+    r = run_cli(cli, ["add", "-p", str(f), "-r", "%x:%x" % (LO, HI - 1)], timeout=300)
+    assert "addr33: %040x <- %064x %s" % (known, KNOWN, R.p2wpkh(known).upper()) in r.found and "prefix (2 patterns, " in r.stdout
 
 
 def test_cli_add_eth_and_rnd(cli, hashes33):
@@ -349,13 +329,13 @@ def test_cli_add_eth_and_rnd(cli, hashes33):
     pattern = R.eth(addr[KNOWN])[:8]  # six digits
     want = sorted("eth: %040x <- %064x %s" % (v, k, R.eth(v)) for k, v in addr.items() if R.eth(v).startswith(pattern))
     assert len(want) >= 1
-    found, status, out = run(cli, ["add", "-p", pattern.upper().replace("0X", "0x"), "-a", "e", "-r", "%x:%x" % (lo, lo + n - 1)])
-    assert found == want and "~ eth: 1 | filter: prefix" in out, (out, status)
+    r = run_cli(cli, ["add", "-p", pattern.upper().replace("0X", "0x"), "-a", "e", "-r", "%x:%x" % (lo, lo + n - 1)], timeout=300)
+    assert r.found == want and "~ eth: 1 | filter: prefix" in r.stdout, (r.stdout, r.status)
     # rnd: one window with a fixed seed; the 2^20 values of the window's offsets cover d00000 ... dfffff, so the known key is in it
     known = R.value_of(hashes33[KNOWN - LO])
     pattern = R.p2pkh(known)[:6]
-    found, status, out = run(cli, ["rnd", "-p", pattern, "-seed", "prefix", "-r", "%x:%x" % (LO, HI - 1), "-d", "0:20"], env={"ECLOOP_HIP_RND_WINDOWS": "1"})
-    assert "addr33: %040x <- %064x %s" % (known, KNOWN, R.p2pkh(known)) in found, (out, status)
-    for line in found:  # every line is a key of the walk with its own hash and an address that starts with the pattern
+    r = run_cli(cli, ["rnd", "-p", pattern, "-seed", "prefix", "-r", "%x:%x" % (LO, HI - 1), "-d", "0:20"], env={"ECLOOP_HIP_RND_WINDOWS": "1"}, timeout=300)
+    assert "addr33: %040x <- %064x %s" % (known, KNOWN, R.p2pkh(known)) in r.found, (r.stdout, r.status)
+    for line in r.found:  # every line is a key of the walk with its own hash and an address that starts with the pattern
         _, h, _, k, a = line.split()
         assert orc.hex160(orc.hash160(*orc.point_of(int(k, 16)))) == h and a == R.p2pkh(int(h, 16)) and a.startswith(pattern)

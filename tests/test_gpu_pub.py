@@ -15,11 +15,10 @@ import pytest
 
 import orc
 import pub_ref
+from support import GOLD, cli, counts, rec_set, run_cli
 from synth import synth_bloom_words
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
 ONES = np.full(64, 0xFFFFFFFFFFFFFFFF, np.uint64)
 RANGES = [(0x3F000, 3000, 0), (0x123456789ABCDEF, 1500, 7)]  # the ranges of tests/test_gpu_tr.py
 h160_of = pub_ref.h160_of
@@ -31,10 +30,6 @@ def pub_device(words=ONES, offs=0, lookahead=0, endo=False):
     d.set_bloom(words)
     d.set_lookahead(lookahead)
     return d
-
-
-def rec_set(recs, base=0):
-    return sorted((base + int(r["key_offset"]), int(r["endo"]), int(r["compressed"]), tuple(int(v) for v in r["h160"])) for r in recs)
 
 
 def test_flags_and_verify_pub():
@@ -301,31 +296,6 @@ def test_a_full_size_call_equals_its_parts():
         assert (endo, typ) == (0, 5) and h == h160_of(A + off), off
 
 
-@pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
-
-
-def run(cli, args, stdin_path=None, env=None):
-    e = dict(os.environ, **(env or {}))
-    pr = subprocess.run([cli] + args, stdin=open(stdin_path, "rb") if stdin_path else subprocess.DEVNULL, stdout=subprocess.PIPE,
-                        stderr=subprocess.PIPE, timeout=600, env=e)
-    assert pr.returncode == 0, pr.stderr.decode(errors="replace")[-2000:]
-    err = pr.stderr.decode(errors="replace")
-    status = err.replace("\x1b[2K", "\r").split("\r")[-1].strip()
-    stdout = pr.stdout.decode(errors="replace")
-    found = sorted(l for l in stdout.splitlines() if ": " in l and " <- " in l)
-    return found, status, stdout, err
-
-
-def counts(status):
-    found, checked = status.split("~")[-1].split("/")
-    clean = lambda s: int("".join(c for c in s if c.isdigit()))
-    return clean(found), clean(checked)
-
-
 def test_cli_add_and_rnd_print_the_compressed_key_that_was_walked(cli, tmp_path):
     keys = (0xdc2a04, 0xffffff, 0x900001, 0x900002, 0x812345)
     assert {pub_ref.compressed(k)[:2] for k in keys} == {"02", "03"}  # both parities
@@ -335,26 +305,26 @@ def test_cli_add_and_rnd_print_the_compressed_key_that_was_walked(cli, tmp_path)
     # the three forms; 0x900002 is listed as its NEGATIVE's compressed key (the other prefix byte): the key printed is the one walked
     lst.write_text("\n".join([pub_ref.compressed(keys[0]), x(keys[1]), unc(keys[2]), pub_ref.compressed(orc.N - keys[3]), pub_ref.compressed(keys[4])]) + "\n")
     want = sorted(pub_ref.found_line(k) for k in keys)
-    found, status, out, _ = run(cli, ["add", "-f", str(lst), "-a", "x", "-r", "800000:ffffff"])
-    assert found == want and counts(status) == (5, 8388608), (out, status)
-    assert "~ endo: 0 ~ pub: 1 | filter: list (5)" in out
+    r = run_cli(cli, ["add", "-f", str(lst), "-a", "x", "-r", "800000:ffffff"])
+    assert r.found == want and counts(r.status) == (5, 8388608), (r.stdout, r.status)
+    assert "~ endo: 0 ~ pub: 1 | filter: list (5)" in r.stdout
     blf = str(tmp_path / "pub.blf")
     subprocess.run([cli, "blf-gen", "-a", "x", "-n", "1000", "-o", blf], stdin=open(str(lst), "rb"), stdout=subprocess.PIPE, check=True, timeout=120)
-    found, status, out, _ = run(cli, ["add", "-f", blf, "-a", "x", "-r", "800000:ffffff"])
-    assert "filter: bloom" in out and found == want and counts(status) == (5, 8388608)
+    r = run_cli(cli, ["add", "-f", blf, "-a", "x", "-r", "800000:ffffff"])
+    assert "filter: bloom" in r.stdout and r.found == want and counts(r.status) == (5, 8388608)
     # -endo: the list holds keys OUTSIDE the range whose images are inside: lambda k, -lambda^2 k; the key printed is the image's
     inside = (0x8abcde, 0xc00001, 0xfedcba)
     listed = [pub_ref.calc_priv(inside[0], 2), pub_ref.calc_priv(inside[1], 5), inside[2]]
     el = tmp_path / "endo.txt"
     el.write_text("".join(pub_ref.compressed(k) + "\n" for k in listed))
-    found, status, out, _ = run(cli, ["add", "-f", str(el), "-a", "x", "-endo", "-r", "800000:ffffff"])
+    r = run_cli(cli, ["add", "-f", str(el), "-a", "x", "-endo", "-r", "800000:ffffff"])
     # image 5 shares its x with image 4: the walked image is 4, whose key is the negative of the listed one
-    assert found == sorted(pub_ref.found_line(k) for k in (listed[0], orc.N - listed[1], listed[2])), out
-    assert counts(status) == (3, 6 * 8388608) and "~ endo: 1 ~ pub: 1 |" in out
+    assert r.found == sorted(pub_ref.found_line(k) for k in (listed[0], orc.N - listed[1], listed[2])), r.stdout
+    assert counts(r.status) == (3, 6 * 8388608) and "~ endo: 1 ~ pub: 1 |" in r.stdout
     one = tmp_path / "dc.txt"
     one.write_text(pub_ref.compressed(0xdc2a04) + "\n")
-    found, status, out, _ = run(cli, ["rnd", "-f", str(one), "-a", "x", "-seed", "pubkey", "-r", "800000:ffffff", "-d", "0:23"])
-    assert found == [pub_ref.found_line(0xdc2a04)], out
+    r = run_cli(cli, ["rnd", "-f", str(one), "-a", "x", "-seed", "pubkey", "-r", "800000:ffffff", "-d", "0:23"])
+    assert r.found == [pub_ref.found_line(0xdc2a04)], r.stdout
 
 
 def test_cli_mul_and_mul_raw_report_the_planted_keys(cli, tmp_path):
@@ -365,10 +335,10 @@ def test_cli_mul_and_mul_raw_report_the_planted_keys(cli, tmp_path):
     pks = [int.from_bytes(hashlib.sha256(p).digest(), "big") for p in phrases]
     lst = tmp_path / "planted.txt"
     lst.write_text("".join(pub_ref.compressed(k) + "\n" for k in picked + pks))
-    found, status, out, _ = run(cli, ["mul", "-f", str(lst), "-a", "x"], stdin_path=os.path.join(GOLD, "mul_scalars.txt"))
-    assert found == sorted(pub_ref.found_line(k) for k in picked), out
-    assert "~ pub: 1 |" in out
+    r = run_cli(cli, ["mul", "-f", str(lst), "-a", "x"], stdin_path=os.path.join(GOLD, "mul_scalars.txt"))
+    assert r.found == sorted(pub_ref.found_line(k) for k in picked), r.stdout
+    assert "~ pub: 1 |" in r.stdout
     ph = tmp_path / "phrases.txt"
     ph.write_bytes(b"\n".join(others[:1000] + phrases + others[1000:]) + b"\n")
-    found, status, out, _ = run(cli, ["mul", "-raw", "-f", str(lst), "-a", "x"], stdin_path=str(ph))
-    assert found == sorted(pub_ref.found_line(k) for k in pks), out
+    r = run_cli(cli, ["mul", "-raw", "-f", str(lst), "-a", "x"], stdin_path=str(ph))
+    assert r.found == sorted(pub_ref.found_line(k) for k in pks), r.stdout

@@ -13,11 +13,10 @@ import subprocess
 import numpy as np
 import pytest
 
+from support import GOLD, ROOT, counts, last_status
 from synth import synth_bloom_words, write_blf
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
 G = json.load(open(os.path.join(GOLD, "golden.json")))["cases"]
 BIN = os.path.join(ROOT, "oracle", "_ref", "ecloop_gpu")
 
@@ -36,15 +35,9 @@ def run(binary, args, tmp_path, name, stdin_path=None, quiet=True, env=None):
     pr = subprocess.run(cmd, stdin=open(stdin_path, "rb") if stdin_path else subprocess.DEVNULL, stdout=subprocess.PIPE,
                         stderr=subprocess.PIPE, timeout=900, env=dict(os.environ, **env) if env else None)
     assert pr.returncode == 0, pr.stderr.decode(errors="replace")[-2000:]
-    status = pr.stderr.decode(errors="replace").replace("\x1b[2K", "\r").split("\r")[-1].strip()
+    status = last_status(pr.stderr.decode(errors="replace"))
     lines = sorted(l.rstrip("\n") for l in open(out)) if os.path.exists(out) else []
     return lines, status, pr.stdout.decode(errors="replace")
-
-
-def counts(status):
-    found, checked = status.split("~")[-1].split("/")
-    clean = lambda s: int("".join(c for c in s if c.isdigit()))
-    return clean(found), clean(checked)
 
 
 def digest(lines):

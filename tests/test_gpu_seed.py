@@ -14,9 +14,9 @@ import pytest
 
 import bip39_ref as R
 import orc
+from support import cli
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ONES = np.full(64, 0xFFFFFFFFFFFFFFFF, np.uint64)
 E_ARG, E_OVERFLOW = -1, -4
 H = R.HARD
@@ -326,13 +326,6 @@ def test_keysearch_cmd_seed_finds_and_verifies_the_planted_keys(phrases64, tmp_p
     with pytest.raises(ValueError):
         KeySearch(load_filter(str(lst)), device=0, bip39=True, kdf="keccak")
     KeySearch(load_filter(str(lst)), device=0, bip39=True, kdf="sha256").close()  # "sha256" is no kdf, here as everywhere
-
-
-@pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
 
 
 def seed_case(tmp_path, phrases64):

@@ -12,7 +12,6 @@ sample of the others are recomputed with eth_ref.eth_words and compared.
 Every GPU-using subprocess runs under its own time limit."""
 import ctypes as C
 import functools
-import os
 import random
 import subprocess
 
@@ -23,10 +22,10 @@ import eth_ref
 import orc
 import prefix_ref as R
 from eth_ref import keccak_many
+from support import cli, run_cli
 from test_gpu_prefix import keys_of, table_around, table_of
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P, N = orc.P, orc.N
 KQ = 0x3B6F1D9A2C4E8071_95D3A7F20B1C6E48_D27A90C3F15B8E64_0A7C3E912D5F8B46  # the requester's key; Q = KQ G is all the searcher sees
 A = 0x9000000001  # the searcher's start scalar
@@ -490,13 +489,6 @@ def test_engine_prefix_search_with_an_origin():
 LO, HI = 0xD00000, 0xE00000  # -r d00000:dfffff: 2^20 keys
 
 
-@pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
-
-
 def pub_hex(pt):
     return "%02x%064x" % (2 | (pt[1] & 1), pt[0])
 
@@ -541,16 +533,6 @@ def p2pkh_candidates(h, pattern):
     return np.nonzero(np.abs(head - want) <= 1)[0]
 
 
-def run_cli(cli, args, env=None, stdin=None):
-    feed = {"input": stdin.encode()} if stdin is not None else {"stdin": subprocess.DEVNULL}
-    pr = subprocess.run([cli] + args, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300, env=dict(os.environ, **(env or {})), **feed)
-    err = pr.stderr.decode(errors="replace")
-    assert pr.returncode == 0, err[-2000:]
-    status = err.replace("\x1b[2K", "\r").split("\r")[-1].strip()
-    out = pr.stdout.decode(errors="replace")
-    return sorted(l for l in out.splitlines() if ": " in l and " <- " in l), status, out
-
-
 def test_cli_add_split_key_lines_combine_and_rnd(cli, image_hashes, tmp_path):
     """fails on the parent commit: there `add` ignores -k and prints whole keys for the points k G"""
     from ecloop_amd.engine import prefix_ranges, splitkey_combine
@@ -585,10 +567,10 @@ def test_cli_add_split_key_lines_combine_and_rnd(cli, image_hashes, tmp_path):
     f.write_text("%s\n%s\n" % (p58, bech))
     outfile = tmp_path / "found.txt"
     args = ["-p", str(f), "-k", pub_hex(Q()), "-a", "c", "-endo", "-r", "%x:%x" % (LO, HI - 1)]
-    found, status, out = run_cli(cli, ["add"] + args + ["-o", str(outfile)])
-    assert found == want, (out, status)
-    assert "edge: %d" % edge in status and "filter: prefix (2 patterns, " in out
-    assert "PARTIAL keys for %s" % pub_hex(Q()) in out
+    r = run_cli(cli, ["add"] + args + ["-o", str(outfile)], timeout=300)
+    assert r.found == want, (r.stdout, r.status)
+    assert "edge: %d" % edge in r.status and "filter: prefix (2 patterns, " in r.stdout
+    assert "PARTIAL keys for %s" % pub_hex(Q()) in r.stdout
     assert sorted(outfile.read_text().splitlines()) == sorted("addr33\t%040x\t%064x\t%s\tsplit:%d" % h for h in hits)  # a fifth tab-separated field
     # the requester's side: every partial key combined with k_Q is the key of the printed address (combine prints it, and its addresses)
     for v, part, address, e in hits:
@@ -601,9 +583,9 @@ def test_cli_add_split_key_lines_combine_and_rnd(cli, image_hashes, tmp_path):
         assert lines[1].startswith("addr33: %040x " % v) and address in lines[1].split()[2:]
     # rnd: one window with a fixed seed; it walks the 2^21 keys from d00000 (full-size jobs), so the lines of `add` are among its lines,
     # and every line's partial key, combined, gives its address
-    found, status, out = run_cli(cli, ["rnd"] + args[:-2] + ["-seed", "splitkey", "-r", "%x:%x" % (LO, HI - 1), "-d", "0:20"], env={"ECLOOP_HIP_RND_WINDOWS": "1"})
-    assert set(want) <= set(found), (out, status)
-    for line in found:
+    r = run_cli(cli, ["rnd"] + args[:-2] + ["-seed", "splitkey", "-r", "%x:%x" % (LO, HI - 1), "-d", "0:20"], env={"ECLOOP_HIP_RND_WINDOWS": "1"}, timeout=300)
+    assert set(want) <= set(r.found), (r.stdout, r.status)
+    for line in r.found:
         _, h, _, k, a, sp = line.split()
         final = splitkey_combine(KQ, int(k, 16), int(sp.split(":")[1]))
         v = R.value_of(orc.hash160(*orc.point_of(final)))

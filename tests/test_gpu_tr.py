@@ -14,11 +14,10 @@ import pytest
 
 import orc
 import tr_ref
+from support import GOLD, ROOT, cli, counts, rec_set, run_cli
 from synth import synth_bloom_words
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
 ONES = np.full(64, 0xFFFFFFFFFFFFFFFF, np.uint64)
 V1_X = 0xd6889cb081036e0faefa3a35157ad71086b123b2b144b649798b494c300a961d
 V1_T = 0xb86e7be8f39bab32a6f2c0443abbc210f0edac0e2c53d501b36b64437d9c6c70
@@ -43,10 +42,6 @@ def tr_device(words=ONES, offs=0, lookahead=0):
     d.set_bloom(words)
     d.set_lookahead(lookahead)
     return d
-
-
-def rec_set(recs, base=0):
-    return sorted((base + int(r["key_offset"]), int(r["endo"]), int(r["compressed"]), tuple(int(v) for v in r["h160"])) for r in recs)
 
 
 def test_abi_known_answers_and_flags():
@@ -303,31 +298,6 @@ def test_lookahead_serves_taproot_jobs_and_keeps_other_types_apart():
         on.close(), off.close(), c.close(), cplain.close()
 
 
-@pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
-
-
-def run(cli, args, stdin_path=None, env=None):
-    e = dict(os.environ, **(env or {}))
-    pr = subprocess.run([cli] + args, stdin=open(stdin_path, "rb") if stdin_path else subprocess.DEVNULL, stdout=subprocess.PIPE,
-                        stderr=subprocess.PIPE, timeout=600, env=e)
-    assert pr.returncode == 0, pr.stderr.decode(errors="replace")[-2000:]
-    err = pr.stderr.decode(errors="replace")
-    status = err.replace("\x1b[2K", "\r").split("\r")[-1].strip()
-    stdout = pr.stdout.decode(errors="replace")
-    found = sorted(l for l in stdout.splitlines() if ": " in l and " <- " in l)
-    return found, status, stdout, err
-
-
-def counts(status):
-    found, checked = status.split("~")[-1].split("/")
-    clean = lambda s: int("".join(c for c in s if c.isdigit()))
-    return clean(found), clean(checked)
-
-
 def line_of(k):
     return "p2tr: %064x <- %064x" % (tr_ref.output_key(k), k)
 
@@ -337,19 +307,19 @@ def test_cli_add_and_rnd_print_the_whole_output_key(cli, tmp_path):
     lst = tmp_path / "tr.txt"
     lst.write_text("".join("%064x\n" % tr_ref.output_key(k) for k in keys))
     want = sorted(line_of(k) for k in keys)
-    found, status, out, _ = run(cli, ["add", "-f", str(lst), "-a", "t", "-r", "800000:ffffff"])
-    assert found == want and counts(status) == (3, 8388608), (out, status)
-    assert "~ endo: 0 ~ p2tr: 1 | filter: list (3)" in out
-    cfound, cstatus, _, _ = run(cli, ["add", "-f", os.path.join(GOLD, "btc-puzzles-hash"), "-a", "c", "-r", "800000:ffffff"])
-    assert counts(cstatus)[1] == counts(status)[1]  # status-line totals as for -a c on the same range
+    r = run_cli(cli, ["add", "-f", str(lst), "-a", "t", "-r", "800000:ffffff"])
+    assert r.found == want and counts(r.status) == (3, 8388608), (r.stdout, r.status)
+    assert "~ endo: 0 ~ p2tr: 1 | filter: list (3)" in r.stdout
+    c = run_cli(cli, ["add", "-f", os.path.join(GOLD, "btc-puzzles-hash"), "-a", "c", "-r", "800000:ffffff"])
+    assert counts(c.status)[1] == counts(r.status)[1]  # status-line totals as for -a c on the same range
     blf = str(tmp_path / "tr.blf")
     subprocess.run([cli, "blf-gen", "-a", "t", "-n", "1000", "-o", blf], stdin=open(str(lst), "rb"), stdout=subprocess.PIPE, check=True, timeout=120)
-    found, status, out, _ = run(cli, ["add", "-f", blf, "-a", "t", "-r", "800000:ffffff"], env={"ECL_HIP_TR_SLAB_LOG2": "20"})
-    assert "filter: bloom" in out and found == want and counts(status) == (3, 8388608)
+    r = run_cli(cli, ["add", "-f", blf, "-a", "t", "-r", "800000:ffffff"], env={"ECL_HIP_TR_SLAB_LOG2": "20"})
+    assert "filter: bloom" in r.stdout and r.found == want and counts(r.status) == (3, 8388608)
     one = tmp_path / "dc.txt"
     one.write_text("%064x\n" % tr_ref.output_key(0xdc2a04))
-    found, status, out, _ = run(cli, ["rnd", "-f", str(one), "-a", "t", "-seed", "taproot", "-r", "800000:ffffff", "-d", "0:23"])
-    assert found == [line_of(0xdc2a04)], out
+    r = run_cli(cli, ["rnd", "-f", str(one), "-a", "t", "-seed", "taproot", "-r", "800000:ffffff", "-d", "0:23"])
+    assert r.found == [line_of(0xdc2a04)], r.stdout
 
 
 def test_cli_mul_and_mul_raw_report_the_planted_keys(cli, tmp_path):
@@ -360,10 +330,10 @@ def test_cli_mul_and_mul_raw_report_the_planted_keys(cli, tmp_path):
     pks = [int.from_bytes(hashlib.sha256(p).digest(), "big") for p in phrases]
     lst = tmp_path / "planted.txt"
     lst.write_text("".join("%064x\n" % tr_ref.output_key(k % orc.N) for k in picked + pks))
-    found, status, out, _ = run(cli, ["mul", "-f", str(lst), "-a", "t"], stdin_path=os.path.join(GOLD, "mul_scalars.txt"))
-    assert found == sorted(line_of(k) for k in picked), out
-    assert "~ p2tr: 1 |" in out
+    r = run_cli(cli, ["mul", "-f", str(lst), "-a", "t"], stdin_path=os.path.join(GOLD, "mul_scalars.txt"))
+    assert r.found == sorted(line_of(k) for k in picked), r.stdout
+    assert "~ p2tr: 1 |" in r.stdout
     ph = tmp_path / "phrases.txt"
     ph.write_bytes(b"\n".join(others[:1000] + phrases + others[1000:]) + b"\n")
-    found, status, out, _ = run(cli, ["mul", "-raw", "-f", str(lst), "-a", "t"], stdin_path=str(ph))
-    assert found == sorted("p2tr: %064x <- %064x" % (tr_ref.output_key(k % orc.N), k) for k in pks), out
+    r = run_cli(cli, ["mul", "-raw", "-f", str(lst), "-a", "t"], stdin_path=str(ph))
+    assert r.found == sorted("p2tr: %064x <- %064x" % (tr_ref.output_key(k % orc.N), k) for k in pks), r.stdout

@@ -12,9 +12,8 @@ import pytest
 
 import kangaroo_ref as ref
 import orc
+from support import ROOT, cli, host_lib, host_program, int_of, run_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "ecloop_amd", "csrc", "tools", "kangaroo_host.cpp")
 P, N = orc.P, orc.N
 M64 = (1 << 64) - 1
 
@@ -27,19 +26,13 @@ def arr(v, n=4):
     return np.array(limbs(v, n), np.uint64)
 
 
-def int_of(a):
-    return sum(int(v) << (64 * i) for i, v in enumerate(a))
-
-
 def words8(v):
     return np.array([(v >> (32 * i)) & 0xFFFFFFFF for i in range(8)], np.uint32)
 
 
 @pytest.fixture(scope="module")
 def K(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("kghost") / "libkghost.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, SRC], check=True)
-    lib = C.CDLL(so)
+    lib = host_lib(tmp_path_factory, "kangaroo_host.cpp")
     V = C.c_void_p
     lib.kh_table.argtypes = [C.c_uint64, C.c_uint, V]
     lib.kh_table.restype = None
@@ -306,17 +299,8 @@ def test_header_and_binding_pin_the_flag():
 
 def test_the_host_program_runs_clean_under_the_sanitizers(tmp_path):
     """csrc/tools/kangaroo_host.cpp has a main of its own: built as a program with the address and undefined-behaviour sanitizers and run"""
-    exe = str(tmp_path / "kangaroo_host")
-    subprocess.run(["g++", "-O0", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, SRC], check=True)
-    pr = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    pr = run_program(host_program(tmp_path, "kangaroo_host.cpp", ["-O0"]))
     assert pr.returncode == 0 and "kangaroo_host: ok" in pr.stdout, (pr.stdout, pr.stderr)
-
-
-@pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
 
 
 def test_cli_names_the_command_and_refuses_before_a_gpu_is_looked_for(cli, tmp_path):

@@ -16,8 +16,8 @@ import pytest
 import kdf_ref
 import orc
 from fake_device import FakeDevice
+from support import ROOT, cli, host_lib, host_program, run_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LENGTHS = list(range(0, 301)) + [407, 408, 409, 1000, 4000]
 KDF_ID = {"keccak": 1, "sha3": 2, "camp2": 3}
 
@@ -35,10 +35,7 @@ def test_the_reference_is_sha3_with_another_pad_byte_and_gives_the_known_answers
 
 @pytest.fixture(scope="module")
 def K(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("kdfhost") / "libkdfhost.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so,
-                    os.path.join(ROOT, "ecloop_amd", "csrc", "tools", "kdf_host.cpp")], check=True)
-    lib = C.CDLL(so)
+    lib = host_lib(tmp_path_factory, "kdf_host.cpp")
     lib.kh_lines.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
     return lib
 
@@ -103,10 +100,7 @@ def test_kdf_h_as_a_program_under_the_sanitizers(tmp_path):
     """kdf_host.cpp's own main, built with ASan + UBSan and run directly: the known answers at the four alignments; every length 0..300, 407,
     408, 409, 1000, 4000 as the last line of a heap block that ends with the two spare words (a gather that read behind them is a heap
     overflow; a shift by 32 in the masks is undefined behaviour); both flags"""
-    exe = str(tmp_path / "kdf_host_san")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
-                    os.path.join(ROOT, "ecloop_amd", "csrc", "tools", "kdf_host.cpp")], check=True)
-    pr = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    pr = run_program(host_program(tmp_path, "kdf_host.cpp", ["-O1", "-g"]), timeout=300)
     assert pr.returncode == 0 and pr.stdout.strip() == "ok", (pr.stdout, pr.stderr[-2000:])
 
 
@@ -122,13 +116,6 @@ def test_kdf_h_flags_a_line_outside_the_text_and_a_line_that_is_not_there_yet(K,
 
 
 # ---------------------------------------------------------------------------------------------------------------- the host program
-@pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
-
-
 def parse(cli, data, *flags):
     pr = subprocess.run([cli, "parse", "-raw"] + list(flags), input=data, capture_output=True, timeout=300)
     assert pr.returncode == 0, pr.stderr

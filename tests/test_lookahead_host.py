@@ -4,15 +4,14 @@ CPU: the header is compiled verbatim around a stand-in search kernel whose hits 
 (tests/test_gpu_lookahead.py) cannot reach is here: several "devices", sweeps that overflow the record store, sweeps that fail, long random
 call sequences, worker threads racing for jobs."""
 import ctypes as C
-import os
 import random
-import subprocess
 import threading
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import host_lib
+
 FOUND = np.dtype([("key_offset", "<u8"), ("h160", "<u4", (5,)), ("endo", "u1"), ("compressed", "u1"), ("pad", "u1", (2,))])
 E_OVERFLOW, E_RANGE = -4, -6
 M64 = (1 << 64) - 1
@@ -20,10 +19,7 @@ M64 = (1 << 64) - 1
 
 @pytest.fixture(scope="module")
 def L(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("lahost") / "liblahost.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-o", so,
-                    os.path.join(ROOT, "ecloop_amd", "csrc", "tools", "lookahead_host.cpp")], check=True)
-    lib = C.CDLL(so)
+    lib = host_lib(tmp_path_factory, "lookahead_host.cpp", extra=["-pthread"])
     lib.lh_open.restype = C.c_void_p
     lib.lh_open.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64]
     lib.lh_close.argtypes = [C.c_void_p]

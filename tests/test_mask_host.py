@@ -12,9 +12,8 @@ import pytest
 
 import mask_ref as R
 from ecloop_amd import capi, engine
+from support import ROOT, cli, host_lib, host_program, run_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "ecloop_amd", "csrc", "tools", "mask_host.cpp")
 E_CHAR, E_NONE, E_TYPE, E_WIDE, E_MANY = -1, -2, -3, -5, -6
 D40 = "0123456789abcdef0123456789abcdef01234567"
 
@@ -40,9 +39,7 @@ BAD = [("0xde*ad*", True, E_CHAR, "more than one *"), ("0x**", True, E_CHAR, "mo
 
 @pytest.fixture(scope="module")
 def H(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("maskhost") / "libmaskhost.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, SRC], check=True)
-    lib = C.CDLL(so)
+    lib = host_lib(tmp_path_factory, "mask_host.cpp")
     lib.mk_test_many.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
     lib.mk_table_ok.argtypes = [C.c_void_p, C.c_ulonglong]
     lib.mk_pattern_entry.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint32), C.c_char_p]
@@ -375,13 +372,6 @@ def test_binding():
 
 # ---- the CLI (no GPU is reached: everything here is decided before a device is opened)
 
-@pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
-
-
 def refused(cli, args):
     pr = subprocess.run([cli] + args, stdin=subprocess.DEVNULL, capture_output=True, text=True, timeout=120)
     assert pr.returncode == 1, (args, pr.stdout, pr.stderr)
@@ -421,7 +411,5 @@ def test_cli_refusals_and_help(cli, tmp_path):
 # ---- the host program under the sanitizers: built with its own main and run directly
 
 def test_host_program_under_asan_and_ubsan(tmp_path):
-    exe = str(tmp_path / "mask_host_san")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, SRC], check=True)
-    pr = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    pr = run_program(host_program(tmp_path, "mask_host.cpp", ["-O1", "-g"]))
     assert pr.returncode == 0 and pr.stdout.strip() == "ok", (pr.stdout, pr.stderr[-2000:])

@@ -12,11 +12,10 @@ import numpy as np
 import pytest
 
 import orc
+from support import GOLD, ROOT, last_status
 from synth import synth_bloom_words, write_blf
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.path.join(ROOT, "oracle", "_ref", "ecloop_sane")
-GOLD = os.path.join(ROOT, "tests", "golden")
 pytestmark = pytest.mark.skipif(not os.path.exists(REF), reason="oracle/_ref/ecloop_sane not built (needs /root/reference)")
 
 
@@ -26,8 +25,7 @@ def run_ref(args, out):
     pr = subprocess.run([REF] + args + ["-t", "1", "-q", "-o", out], stdin=subprocess.DEVNULL, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     if pr.returncode != 0:
         pytest.skip("the reference binary does not run on this host (%d): %s" % (pr.returncode, pr.stderr.decode(errors="replace")[-200:]))
-    status = pr.stderr.decode(errors="replace").replace("\x1b[2K", "\r").split("\r")[-1]
-    m = re.search(r"~ ([\d,.\s]+) / ([\d,.\s]+)", status)
+    m = re.search(r"~ ([\d,.\s]+) / ([\d,.\s]+)", last_status(pr.stderr.decode(errors="replace")))
     clean = lambda s: int("".join(c for c in s if c.isdigit()))
     lines = sorted(l.rstrip("\n") for l in open(out)) if os.path.exists(out) else []
     return lines, clean(m.group(1)), clean(m.group(2))

@@ -10,8 +10,7 @@ import pytest
 
 import orc
 import p2sh_ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import ROOT, host_lib
 
 # private key -> (hash160 of the compressed key, its P2SH-P2WPKH hash); key 1 is the address 3JvL6Ymt8MVWiCNHC7oWU6nLeHNJKLZGLN
 KNOWN = {1: ("751e76e8199196d454941c45d1b3a323f1433bd6", "bcfeb728b584253d5f3f70bcb780e9ef218a68f4"),
@@ -21,10 +20,7 @@ KNOWN = {1: ("751e76e8199196d454941c45d1b3a323f1433bd6", "bcfeb728b584253d5f3f70
 
 @pytest.fixture(scope="module")
 def P(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("p2shhost") / "libp2shhost.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so,
-                    os.path.join(ROOT, "ecloop_amd", "csrc", "tools", "p2sh_host.cpp")], check=True)
-    lib = C.CDLL(so)
+    lib = host_lib(tmp_path_factory, "p2sh_host.cpp")
     lib.ph_p2sh_many.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     return lib
 

@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 
 import prefix_ref as R
+from support import ROOT, cli, host_lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOP = R.TOP
 H1 = R.value_of([0x751E76E8, 0x199196D4, 0x54941C45, 0xD1B3A323, 0xF1433BD6])  # hash160 of the compressed key of 1
 A1 = "1BgGZ9tcN4rm9KBzDn7KprQz87SZ26SAMH"
@@ -27,10 +27,7 @@ PATTERNS = [(p, True, False, False) for p in B58_PATTERNS] + [("1Lov", False, Tr
 
 @pytest.fixture(scope="module")
 def H(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("prefixhost") / "libprefixhost.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so,
-                    os.path.join(ROOT, "ecloop_amd", "csrc", "tools", "prefix_host.cpp")], check=True)
-    lib = C.CDLL(so)
+    lib = host_lib(tmp_path_factory, "prefix_host.cpp")
     lib.px_test_many.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     lib.px_table_ok.argtypes = [C.c_void_p, C.c_uint64]
     lib.px_bitmap_popcount.argtypes = [C.c_void_p, C.c_uint32]
@@ -274,13 +271,6 @@ def test_table_check(H):
 
 
 # ---- the CLI (no GPU is reached: everything here is decided before a device is opened)
-
-@pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
-
 
 def refused(cli, args):
     pr = subprocess.run([cli] + args, stdin=subprocess.DEVNULL, capture_output=True, text=True, timeout=120)

@@ -11,13 +11,13 @@ the per-key loops.  Needs hipcc (or the assembly a previous build kept); skipped
 import glob
 import json
 import os
-import shutil
 import sys
 import warnings
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import ROOT, kept_assembly
+
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
@@ -28,13 +28,8 @@ def newest_profile():
 
 
 def test_static_mix_of_the_built_kernel_matches_the_profile():
-    from ecloop_amd.build import ASM, build_library
     import isa_mix
-    if shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc"):
-        build_library()  # no-op when current; always leaves the assembly of the shipped code object beside the library
-    if not os.path.exists(ASM):
-        pytest.skip("no hipcc and no kept assembly: nothing to analyse")
-    a = isa_mix.analyse(ASM)
+    a = isa_mix.analyse(kept_assembly())
     prof, name = newest_profile()
     fp, want = a["fingerprint"], prof["fingerprint"]
     stale = [f"{k}: built {fp.get(k)} vs {v}" for k, v in want.items() if k in fp and abs(fp[k] - v) > max(0.01 * v, 1)]
@@ -73,12 +68,8 @@ def test_static_mix_of_the_mul_kernel_matches_its_profile():
     it): the kernel's fingerprint (tools/isa_mix.py: analyse_mul) against the one stored with the counters; structural: the window loop is
     free of scratch traffic and holds the 918 multiply-adds of one XYZZ addition (8 M + 2 S), and the static per-scalar estimate agrees with
     the PMC count of the profiled build"""
-    from ecloop_amd.build import ASM, build_library
     import isa_mix
-    if shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc"):
-        build_library()
-    if not os.path.exists(ASM):
-        pytest.skip("no hipcc and no kept assembly: nothing to analyse")
+    ASM = kept_assembly()
     files = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_roofline_mul.json")))
     assert files, "no profiles/rNN_roofline_mul.json: run tools/collect_profiles.sh on the GPU box"
     prof, name = json.load(open(files[-1])), os.path.basename(files[-1])
@@ -105,13 +96,8 @@ def test_every_instantiation_is_fingerprinted_and_keeps_scratch_out_of_its_loops
     what remains sits in the once-per-group launch loop, or passes arguments to the rarely taken complete sum; (2) the tracked
     profiles/rNN_static_mix.json (tools/isa_mix.py --all: fingerprints, registers, spills) describes the library that is being built -
     a drift warns, and fails under ECL_REQUIRE_FRESH_PROFILES=1, like the PMC profiles above"""
-    from ecloop_amd.build import ASM, build_library
     import isa_mix
-    if shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc"):
-        build_library()
-    if not os.path.exists(ASM):
-        pytest.skip("no hipcc and no kept assembly: nothing to analyse")
-    now = isa_mix.analyse_all(ASM)
+    now = isa_mix.analyse_all(kept_assembly())
     assert set(now) == set(isa_mix.ADD_KERNELS) | set(isa_mix.MUL_KERNELS)
     for label, a in now.items():
         loops = a["scratch_in_loops"]

@@ -6,7 +6,6 @@ import ctypes as C
 import os
 import random
 import re
-import shutil
 import subprocess
 import sys
 
@@ -15,18 +14,10 @@ import pytest
 
 import orc
 import pub_ref
+from support import ROOT, cli, host_lib, int_of_words, kept_assembly, words8
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 P, N = orc.P, orc.N
-
-
-def words8(v):
-    return [(v >> (32 * i)) & 0xFFFFFFFF for i in range(8)]
-
-
-def int_of(w):
-    return sum(int(v) << (32 * i) for i, v in enumerate(w))
 
 
 def y_of(x):
@@ -59,10 +50,7 @@ def test_the_yardstick_against_the_oracle():
 
 @pytest.fixture(scope="module")
 def H(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("pubhost") / "libpubhost.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so,
-                    os.path.join(ROOT, "ecloop_amd", "csrc", "tools", "pub_host.cpp")], check=True)
-    lib = C.CDLL(so)
+    lib = host_lib(tmp_path_factory, "pub_host.cpp")
     lib.ph_pair_many.argtypes = [C.c_void_p] * 6 + [C.c_uint32]
     lib.ph_probe_many.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
     return lib
@@ -72,7 +60,7 @@ def pairs_on_device_header(H, cs, gs):
     arr = [np.array([words8(v) for v in col], np.uint32) for col in ([c[0] for c in cs], [c[1] for c in cs], [g[0] for g in gs], [g[1] for g in gs])]
     xp, xm = np.zeros_like(arr[0]), np.zeros_like(arr[0])
     H.ph_pair_many(*[a.ctypes.data for a in arr], xp.ctypes.data, xm.ctypes.data, len(cs))
-    return [int_of(w) for w in xp], [int_of(w) for w in xm]
+    return [int_of_words(w) for w in xp], [int_of_words(w) for w in xm]
 
 
 def test_the_x_only_pair_step_of_the_device_header(H):
@@ -169,13 +157,6 @@ def test_header_and_binding_declare_pub():
             capi.Device(0, a33=False, pub=True, **kw)
 
 
-@pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
-
-
 def test_cli_help_names_the_letter_and_mixed_type_strings_are_refused(cli):
     out = subprocess.run([cli], capture_output=True, text=True, timeout=60).stdout
     line = [l for l in out.splitlines() if l.strip().startswith("-a ")]
@@ -249,13 +230,8 @@ def test_the_new_kernels_fit_168_registers_keep_scratch_out_of_their_loops_and_d
     per-key VALU count of k_add_pub<false> (the `which` loop body + half the table loop's own body + half the prefix loop, the figure
     tools/isa_mix.py gives every walk kernel) is below that of k_add for -a c from the same assembly less the 2 248 VALU lane-ops of one
     hash160: the hash is gone.  Figures of this build: 813 against 3 272 - 2 248 = 1 024."""
-    from ecloop_amd.build import ASM, build_library
     import isa_mix
-    if shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc"):
-        build_library()
-    if not os.path.exists(ASM):
-        pytest.skip("no hipcc and no kept assembly: nothing to analyse")
-    now = isa_mix.analyse_pub(ASM)
+    now = isa_mix.analyse_pub(kept_assembly())
     assert set(now) == set(isa_mix.PUB_KERNELS) and len(now) == 3
     for label, a in now.items():
         print(label, a["registers"], {k: v for k, v in a.items() if k.startswith(("scratch", "window", "walk", "which", "per_key", "addr33", "table", "prefix", "image"))})

@@ -15,8 +15,8 @@ import numpy as np
 import pytest
 
 import bip39_ref as R
+from support import ROOT, cli, host_lib, host_program, run_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H = R.HARD
 A = R.PHRASE_A
 TABLE = {"m": "1837c1be8e2995ec11cda2b066151be2cfb48adf9e47b151d46adab3a21cdf67",
@@ -41,9 +41,7 @@ def test_the_yardstick_gives_the_published_answers():
 
 @pytest.fixture(scope="module")
 def K(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("bip39host") / "libbip39host.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, os.path.join(ROOT, "ecloop_amd", "csrc", "tools", "bip39_host.cpp")], check=True)
-    lib = C.CDLL(so)
+    lib = host_lib(tmp_path_factory, "bip39_host.cpp")
     V = C.c_void_p
     lib.bh_sha512.argtypes = [V, V, C.c_uint32, V]
     lib.bh_hmac.argtypes = [V, C.c_uint64, C.c_char_p, C.c_uint32, V]
@@ -189,18 +187,8 @@ def test_the_harness_as_a_program_under_the_sanitizers(tmp_path):
     """bip39_host.cpp's own main, built with ASan + UBSan and run directly: the known answers; every length 0 ... 300 as the last line of a
     heap block that ends with the text's two spare words, at the four alignments (a gather that read behind them is a heap overflow; a
     shift by 32 in the masks is undefined behaviour); the validity rules"""
-    exe = str(tmp_path / "bip39_host_san")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe,
-                    os.path.join(ROOT, "ecloop_amd", "csrc", "tools", "bip39_host.cpp")], check=True)
-    pr = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    pr = run_program(host_program(tmp_path, "bip39_host.cpp", ["-O1"]), timeout=300)
     assert pr.returncode == 0 and pr.stdout.strip() == "ok", (pr.stdout, pr.stderr[-2000:])
-
-
-@pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
 
 
 def test_seed_keys_is_the_yardstick_on_40_phrases_and_hardened_paths_of_every_depth(cli):

@@ -11,27 +11,16 @@ import numpy as np
 import pytest
 
 import orc
+from ecloop_amd.capi import limbs
+from support import ROOT, cli, host_lib, host_program, int_of, run_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "ecloop_amd", "csrc", "tools", "splitkey_host.cpp")
 P, N = orc.P, orc.N
-M64 = (1 << 64) - 1
 G1 = "0279be667ef9dcbbac55a06295ce870b07029bfcdb2dce28d959f2815b16f81798"
-
-
-def arr(v):
-    return np.array([(v >> (64 * i)) & M64 for i in range(4)], np.uint64)
-
-
-def int_of(a):
-    return sum(int(v) << (64 * i) for i, v in enumerate(a))
 
 
 @pytest.fixture(scope="module")
 def H(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("skhost") / "libskhost.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so, SRC], check=True)
-    lib = C.CDLL(so)
+    lib = host_lib(tmp_path_factory, "splitkey_host.cpp")
     V = C.c_void_p
     lib.sk_host_image_origin.argtypes = [V, V, C.c_uint]
     lib.sk_host_image_origin.restype = None
@@ -43,19 +32,19 @@ def H(tmp_path_factory):
 
 
 def image_origin(H, pt, e):
-    x, y = arr(pt[0]), arr(pt[1])
+    x, y = limbs(pt[0]), limbs(pt[1])
     H.sk_host_image_origin(x.ctypes.data, y.ctypes.data, e)
     return int_of(x), int_of(y)
 
 
 def combine(H, kq, part, e):
-    a, b, out = arr(kq), arr(part), np.zeros(4, np.uint64)  # (named: the arrays live until the call returns)
+    a, b, out = limbs(kq), limbs(part), np.zeros(4, np.uint64)  # (named: the arrays live until the call returns)
     H.sk_host_combine(a.ctypes.data, b.ctypes.data, e, out.ctypes.data)
     return int_of(out)
 
 
 def endo_scalar(H, k, e):
-    a, out = arr(k), np.zeros(4, np.uint64)
+    a, out = limbs(k), np.zeros(4, np.uint64)
     H.sk_host_endo_scalar(a.ctypes.data, e, out.ctypes.data)
     return int_of(out)
 
@@ -138,17 +127,8 @@ def test_binding_accepts_the_split_key_device_and_keeps_the_other_refusals(monke
 
 def test_the_host_program_runs_clean_under_the_sanitizers(tmp_path):
     """csrc/tools/splitkey_host.cpp has a main of its own: built as a program with the address and undefined-behaviour sanitizers and run"""
-    exe = str(tmp_path / "splitkey_host")
-    subprocess.run(["g++", "-O0", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, SRC], check=True)
-    pr = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    pr = run_program(host_program(tmp_path, "splitkey_host.cpp", ["-O0"]))
     assert pr.returncode == 0 and "splitkey_host: ok" in pr.stdout, (pr.stdout, pr.stderr)
-
-
-@pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
 
 
 def refused(cli, args, stdin=None):

@@ -6,7 +6,6 @@ import ctypes as C
 import os
 import random
 import re
-import shutil
 import subprocess
 import sys
 
@@ -15,8 +14,8 @@ import pytest
 
 import orc
 import tr_ref
+from support import ROOT, cli, host_lib, int_of_words, kept_assembly, words8
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 TAG = "e80fe1639c9ca050e3af1b39c143c63e429cbceb15d940fbb5c5a1f4af57c5e9"
@@ -72,24 +71,13 @@ def test_p2tr_keys_decodes_the_addresses_and_refuses_everything_else():
 
 @pytest.fixture(scope="module")
 def T(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("trhost") / "libtrhost.so")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-o", so,
-                    os.path.join(ROOT, "ecloop_amd", "csrc", "tools", "tr_host.cpp")], check=True)
-    lib = C.CDLL(so)
+    lib = host_lib(tmp_path_factory, "tr_host.cpp")
     lib.th_tweak_many.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
     lib.th_ge_n_many.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     lib.th_lift_many.argtypes = [C.c_void_p, C.c_uint32]
     lib.th_add_x.argtypes = [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 3
     lib.th_add_x.restype = C.c_int
     return lib
-
-
-def words8(v):
-    return [(v >> (32 * i)) & 0xFFFFFFFF for i in range(8)]
-
-
-def int_of(w):
-    return sum(int(v) << (32 * i) for i, v in enumerate(w))
 
 
 def test_taptweak_of_the_device_header_equals_the_yardstick(T):
@@ -99,10 +87,10 @@ def test_taptweak_of_the_device_header_equals_the_yardstick(T):
     tw = np.zeros_like(X)
     ge = np.zeros(len(X), np.uint8)
     T.th_tweak_many(X.ctypes.data, tw.ctypes.data, ge.ctypes.data, len(X))
-    assert int_of(tw[0]) == V1_T
+    assert int_of_words(tw[0]) == V1_T
     for i, x in enumerate(xs):
         t = tr_ref.tweak(x)
-        assert int_of(tw[i]) == t and bool(ge[i]) == (t >= orc.N), i
+        assert int_of_words(tw[i]) == t and bool(ge[i]) == (t >= orc.N), i
 
 
 def test_the_tweak_range_test_and_the_even_y_lift(T):
@@ -116,7 +104,7 @@ def test_the_tweak_range_test_and_the_even_y_lift(T):
     Y = np.array([words8(y) for y in ys], np.uint32)
     T.th_lift_many(Y.ctypes.data, len(Y))
     for i, y in enumerate(ys):
-        assert int_of(Y[i]) == (y if y % 2 == 0 else orc.P - y), i
+        assert int_of_words(Y[i]) == (y if y % 2 == 0 else orc.P - y), i
 
 
 def add_x(T, t, p):
@@ -124,7 +112,7 @@ def add_x(T, t, p):
     a = [np.array(words8(v), np.uint32) for v in (tx, ty, p[0], p[1])]
     out = np.zeros(8, np.uint32)
     how = T.th_add_x(a[0].ctypes.data, a[1].ctypes.data, int(t is None), a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
-    return how, int_of(out)
+    return how, int_of_words(out)
 
 
 def test_the_addition_of_stage_b_and_its_exceptional_cases(T):
@@ -158,13 +146,6 @@ def test_header_and_binding_declare_taproot():
     assert "ecl_hip_verify_tr" in capi.EXPORTS and "ecl_hip_diag_tr" in capi.EXPORTS
     exports = open(os.path.join(ROOT, "ecloop_amd", "csrc", "exports.map")).read()
     assert "ecl_hip_*" in exports
-
-
-@pytest.fixture(scope="module")
-def cli():
-    from ecloop_amd.build import build_host_cli, build_library
-    build_library()
-    return build_host_cli()
 
 
 def test_cli_help_names_the_letter_and_mixed_type_strings_are_refused(cli):
@@ -213,13 +194,8 @@ def test_the_new_kernels_fit_168_registers_and_keep_scratch_out_of_their_loops()
     """static, from the assembly the build keeps (tools/isa_mix.py: analyse_tr): each Taproot kernel has at most 168 VGPRs and no scratch
     instruction in any loop below its launch loop (k_add_tr) / its round loops (the others) - and none in the round loops either, the
     arguments of the out-of-line complete sum aside; the window loop holds the 918 multiply-adds of one XYZZ addition"""
-    from ecloop_amd.build import ASM, build_library
     import isa_mix
-    if shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc"):
-        build_library()
-    if not os.path.exists(ASM):
-        pytest.skip("no hipcc and no kept assembly: nothing to analyse")
-    now = isa_mix.analyse_tr(ASM)
+    now = isa_mix.analyse_tr(kept_assembly())
     assert set(now) == set(isa_mix.TR_KERNELS) and len(now) == 4
     for label, a in now.items():
         print(label, a["registers"], {k: v for k, v in a.items() if k.startswith(("scratch", "window", "walk", "tagged"))})
