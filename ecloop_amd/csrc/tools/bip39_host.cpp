@@ -88,11 +88,12 @@ int main() {
         if (strcmp(hex, k.hex)) return fail("SHA-512 known answer");
       }
   }
-  // every length 0..300 as the last line of the block at the four alignments: the same digest, the same 3-round seed, nothing read outside
-  static char msg[300];
+  // every length 0..1100 (9 blocks), then 2000 and 4000, as the last line of the block at the four alignments: the same digest, the same
+  // 3-round seed, nothing read outside
+  static char msg[4000];
   u32 z = 0x9E3779B9u;
   for (size_t i = 0; i < sizeof msg; ++i) z ^= z << 13, z ^= z >> 17, z ^= z << 5, msg[i] = (char)z;
-  for (u32 len = 0; len <= 300; ++len) {
+  for (u32 len = 0; len <= 4000; len = len < 1100 ? len + 1 : len < 2000 ? 2000 : len + 2000) {
     u64 first[16];
     for (u32 lead = 0; lead < 4; ++lead) {
       u32* text = text_of(msg, len, lead);

@@ -1,5 +1,5 @@
 """What the test files share: paths, host builds of csrc/tools/*_host.cpp (as a shared object for ctypes, or as a stand-alone program
-under the sanitizers), the `cli` fixture, one runner for the host program with its status line and found lines picked out, and the
+under the sanitizers), the long phrase lengths of the seed tests, the `cli` fixture, one runner for the host program with its status line and found lines picked out, and the
 record-to-tuples helper.  A plain module: pytest does not rewrite its asserts, so each one carries its message."""
 import ctypes
 import os
@@ -14,6 +14,10 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 CSRC = os.path.join(ROOT, "ecloop_amd", "csrc")
 TOOLS_SRC = os.path.join(CSRC, "tools")
 SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+# phrase lengths behind the 300 bytes the seed tests began with: the empty phrase; 4 to 9 SHA-512 blocks in steps of 7; around every block
+# end up to 8 blocks - 111 / 112 mod 128 is where the padding spills into a block of its own; the host program's piece of 1024; 16 and 32 blocks
+SEED_LONG_LENS = list(dict.fromkeys([0] + list(range(261, 1101, 7)) + [128 * b + d for b in range(2, 9) for d in (-17, -16, -1, 0, 1)] + [1023, 1024, 1025, 2000, 4000]))
+assert len(SEED_LONG_LENS) == 154
 
 
 def host_lib(tmp_path_factory, source, extra=()):

@@ -1,5 +1,5 @@
 """`seed` without a GPU: the yardstick (tests/bip39_ref.py) pinned to the published BIP39 / BIP32 answers; the device headers sha512.h /
-bip39.h compiled for the host (csrc/tools/bip39_host.cpp) against it - SHA-512 at every length, HMAC key lengths, PBKDF2 iterations and
+bip39.h compiled for the host (csrc/tools/bip39_host.cpp) against it - SHA-512 at every length to 300 bytes and at support.SEED_LONG_LENS (4 to 32 blocks), HMAC keys of the same lengths, PBKDF2 iterations and
 passphrases, the gather at every alignment, CKDpriv, the node validity rules - and as a program under the sanitizers; the host program's
 own derivation through `seed -keys`, and every refusal of the command; the binding's constant, the header, the record seed_batch builds;
 engine.bip39_key and parse_path; the static figures of the two kernels."""
@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 
 import bip39_ref as R
-from support import ROOT, cli, host_lib, host_program, run_program
+from support import ROOT, SEED_LONG_LENS, cli, host_lib, host_program, run_program
 
 H = R.HARD
 A = R.PHRASE_A
@@ -76,9 +76,11 @@ def k_int(words):
 
 
 def test_sha512_at_every_length_and_alignment(K):
+    """every length 0 ... 300, then support.SEED_LONG_LENS: 4 to 32 blocks - sha512_text's block loop past its third pass and the gather of
+    sha512_text_word at positions past 384, which nothing read before - with the 111 / 112 mod 128 padding spill at every block up to the 8th"""
     rnd = random.Random(512)
-    lens = list(range(0, 301))
-    assert {111, 112, 127, 128, 129, 239, 240} <= set(lens)
+    lens = list(range(0, 301)) + SEED_LONG_LENS
+    assert {111, 112, 127, 128, 129, 239, 240, 495, 496, 1007, 1008, 1024, 4000} <= set(lens)
     lines = [bytes(rnd.randrange(256) for _ in range(n)) for n in lens]
     want = [hashlib.sha512(l).digest() for l in lines]
     seen = set()
@@ -92,8 +94,9 @@ def test_sha512_at_every_length_and_alignment(K):
 
 
 def test_hmac_with_keys_around_the_block_size(K):
+    """... and keys of support.SEED_LONG_LENS bytes: bip39_key_block's hashed branch over 4 to 32 blocks"""
     rnd = random.Random(128)
-    for klen in (0, 1, 127, 128, 129, 215, 300):
+    for klen in [0, 1, 127, 128, 129, 215, 300] + SEED_LONG_LENS:
         key = bytes(rnd.randrange(256) for _ in range(klen))
         for lead in range(4):
             text, table, _ = packed([key], lead)
@@ -184,7 +187,7 @@ def test_the_node_validity_rules_on_planted_values(K):
 
 
 def test_the_harness_as_a_program_under_the_sanitizers(tmp_path):
-    """bip39_host.cpp's own main, built with ASan + UBSan and run directly: the known answers; every length 0 ... 300 as the last line of a
+    """bip39_host.cpp's own main, built with ASan + UBSan and run directly: the known answers; every length 0 ... 1100, then 2000 and 4000, as the last line of a
     heap block that ends with the text's two spare words, at the four alignments (a gather that read behind them is a heap overflow; a
     shift by 32 in the masks is undefined behaviour); the validity rules"""
     pr = run_program(host_program(tmp_path, "bip39_host.cpp", ["-O1"]), timeout=300)
