@@ -15,11 +15,11 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libecloop_hip.so")
 ASM = os.path.join(PKG, "libecloop_hip.gfx950.s")  # assembly of the library's code object (kept by the build)
-SOURCES = ["ecloop_hip.hip", "exports.map", "setup_kernels.h", "mul_kernels.h", "tr_kernels.h", "aux_kernels.h", "abi_mul.h", "abi_seed.h", "abi_tr.h", "abi_diag.h", "abi_lookahead.h", "abi_lookahead_ctx.h", "abi_herd.h", "devbuf.h", "callstate.h", "herd_kernel.h", "../host/kangaroo_plan.h", "../host/bsgs_plan.h", "add_kernel.h", "add_walk.inc", "mul_check.inc", "hash160.h", "emit33.h", "keccak.h", "kdf.h", "sha512.h", "bip39.h", "pub_emit.h", "prefix.h", "mask.h", "limb_ops.h", "fe256.h", "ec.h",
+SOURCES = ["ecloop_hip.hip", "exports.map", "setup_kernels.h", "mul_kernels.h", "tr_kernels.h", "aux_kernels.h", "abi_mul.h", "abi_seed.h", "abi_gen.h", "abi_tr.h", "abi_diag.h", "abi_lookahead.h", "abi_lookahead_ctx.h", "abi_herd.h", "devbuf.h", "callstate.h", "herd_kernel.h", "../host/kangaroo_plan.h", "../host/bsgs_plan.h", "add_kernel.h", "add_walk.inc", "mul_check.inc", "hash160.h", "emit33.h", "keccak.h", "kdf.h", "sha512.h", "bip39.h", "gen.h", "../host/gen_plan.h", "pub_emit.h", "prefix.h", "mask.h", "limb_ops.h", "fe256.h", "ec.h",
            "bloom.h", "scalar_host.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden"]
 HOST_SOURCES = ["ecloop_hip_cli.c"]  # the translation unit; its parts (hashed for the stamp like it):
-HOST_PARTS = ["cli_base.h", "cli_filter.h", "cli_report.h", "cli_add.h", "cli_mul.h", "cli_rnd_blf.h", "cli_keys.h", "cli_bsgs.h", "bsgs_plan.h", "cli_kangaroo.h", "kangaroo_plan.h", "cli_prefix.h", "prefix_plan.h", "mask_plan.h", "cli_splitkey.h", "splitkey.h", "keccak_host.h", "cli_seed.h", "bip39_host.h"]
+HOST_PARTS = ["cli_base.h", "cli_filter.h", "cli_report.h", "cli_add.h", "cli_mul.h", "cli_rnd_blf.h", "cli_keys.h", "cli_bsgs.h", "bsgs_plan.h", "cli_kangaroo.h", "kangaroo_plan.h", "cli_prefix.h", "prefix_plan.h", "mask_plan.h", "cli_splitkey.h", "splitkey.h", "keccak_host.h", "cli_seed.h", "bip39_host.h", "cli_brain.h", "gen_plan.h"]
 HOST_FLAGS = ["-O2", "-std=gnu11", "-Wall"]
 
 

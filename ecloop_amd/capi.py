@@ -17,6 +17,7 @@ MASK = 8192  # the mask filter in place of the bloom: beside ETH alone, with or 
 # the key derivation function of mul_batch_raw, a two-bit field (include/ecloop_hip.h): none = SHA-256; valid beside every context that has a `mul`
 KDF_KECCAK, KDF_SHA3, KDF_CAMP2 = 0x4000, 0x8000, 0xC000
 BIP39 = 0x10000  # the lines of mul_batch_raw are BIP39 phrases, lines[0] the derivation record (include/ecloop_hip.h: ECL_KDF_BIP39); not beside a KDF_* bit
+GEN = 0x20000  # the lines of mul_batch_raw are generated on the device from a template (include/ecloop_hip.h: ECL_GEN); beside a KDF_* bit or none, not beside BIP39
 KDF_FLAGS = {None: 0, "sha256": 0, "keccak": KDF_KECCAK, "sha3": KDF_SHA3, "camp2": KDF_CAMP2}
 E_ARG = -1
 E_NOBLOOM = -5
@@ -142,9 +143,12 @@ class Device:
     """One GPU context (ecl_hip handle)."""
 
     def __init__(self, device=0, a33=True, a65=False, endo=False, ord_offs=0, p2sh=False, eth=False, tr=False, pub=False, origin=False,
-                 insert=False, herd=False, prefix=False, mask=False, kdf=None, bip39=False):
+                 insert=False, herd=False, prefix=False, mask=False, kdf=None, bip39=False, gen=False):
         if kdf not in KDF_FLAGS:
             raise ValueError("kdf is None (SHA-256), 'keccak', 'sha3' or 'camp2'")
+        if gen and (bip39 or origin or insert or herd or prefix or mask):
+            raise ValueError("gen goes with the contexts that have a `mul`, with or without a kdf: not with bip39, origin, insert, herd, prefix or mask")
+        self.gen = bool(gen)
         if bip39 and (KDF_FLAGS[kdf] or origin or insert or herd or prefix or mask):
             raise ValueError("bip39 goes with the contexts that have a `mul`, and not with a kdf: not with origin, insert, herd, prefix or mask")
         self.bip39 = bool(bip39)
@@ -173,7 +177,7 @@ class Device:
         if tr and (a33 or a65 or p2sh or eth or endo):
             raise ValueError("Taproot is searched alone and without the endomorphism: Device(a33=False, tr=True)")
         flags = (ADDR33 if a33 else 0) | (ADDR65 if a65 else 0) | (P2SH if p2sh else 0) | (ETH if eth else 0) | (TR if tr else 0) | (PUB if pub else 0) | (ENDO if endo else 0) | \
-                (ORIGIN if origin else 0) | (INSERT if insert else 0) | (HERD if herd else 0) | (PREFIX if prefix else 0) | (MASK if mask else 0) | KDF_FLAGS[kdf] | (BIP39 if bip39 else 0)
+                (ORIGIN if origin else 0) | (INSERT if insert else 0) | (HERD if herd else 0) | (PREFIX if prefix else 0) | (MASK if mask else 0) | KDF_FLAGS[kdf] | (BIP39 if bip39 else 0) | (GEN if gen else 0)
         rc = self.lib.ecl_hip_open(C.byref(self.h), device, flags, ord_offs)
         if rc != 0:
             msg = self.lib.ecl_hip_last_error(self.h).decode() if self.h else ""
@@ -336,6 +340,23 @@ class Device:
         if len(path) > 255 or len(passphrase) > 255:
             raise ValueError("a path of more than 255 elements or a passphrase of more than 255 bytes does not fit the record")
         return self.mul_batch_raw([self.seed_record(path, passphrase, reuse)] + list(phrases), cap=cap)
+
+    def brain_batch(self, template, first, n, cap=4096):
+        """the candidates first ... first + n - 1 of a template, generated and hashed on the device -> (records, total); key_offset of a
+        record is its index - first.  template: positions (a list of lists of bytes objects: engine.parse_mask makes one from a mask) or
+        the packed blob of engine.brain_table (include/ecloop_hip.h: ECL_GEN)"""
+        if not self.gen:
+            raise ValueError("brain_batch goes with Device(gen=True)")
+        if not isinstance(template, (bytes, bytearray)):
+            from .engine import brain_table
+            template = brain_table(template)
+        buf = np.frombuffer(bytes(template), dtype=np.uint8) if template else np.zeros(1, dtype=np.uint8)
+        start = np.array([first], dtype=np.uint64)
+        out = np.zeros(cap, dtype=FOUND_DTYPE)
+        got = C.c_uint32()
+        rc = self.lib.ecl_hip_mul_batch_raw(self.h, buf.ctypes.data, len(template), start.ctypes.data, n, out.ctypes.data, cap, C.byref(got))
+        self._chk(rc, allow=(E_OVERFLOW,))
+        return out[: min(got.value, cap)], got.value
 
     def set_mul_window(self, bits):
         """window width of this context's `mul` table (8..29 bits; 0 = automatic: 22, then 26 after 2^30 scalars)"""

@@ -414,6 +414,7 @@ static int raw_buffers(ecl_hip* h, u32 text_bytes, u32 n) {
 }
 
 static int seed_batch(ecl_hip* h, const uint8_t* text, uint32_t text_bytes, const uint64_t* lines, uint32_t n, ecl_found* out, uint32_t cap, uint32_t* nout);
+static int gen_batch(ecl_hip* h, const uint8_t* blob, uint32_t blob_bytes, const uint64_t* lines, uint32_t n, ecl_found* out, uint32_t cap, uint32_t* nout);
 // `mul -raw`: lines of text in, SHA-256 (or the context's ECL_KDF_* hash) on the device, then the `mul` body on the digests (n <= 2^26 lines a call): the pieces of
 // ecl_hip_mul_batch, with 8 bytes of table + the line instead of 32 bytes of scalar on the copy stream, and every piece's lines hashed
 // into its staging buffer ahead of its window sums (details at the two lambdas below).  Until round 6 a call was ONE piece of at most
@@ -429,6 +430,7 @@ extern "C" int ecl_hip_mul_batch_raw(ecl_hip* h, const uint8_t* text, uint32_t t
   if (n == 0) return ECL_OK;
   HIPCHK(h, hipSetDevice(h->dev));
   if (h->bip39) return seed_batch(h, text, text_bytes, lines, n, out, cap, nout);  // lines[0] is the derivation record (abi_seed.h)
+  if (h->gen) return gen_batch(h, text, text_bytes, lines, n, out, cap, nout);      // text is the template, lines[0] the first index (abi_gen.h)
   call_frame f = {h, "mul_batch_raw", (h->flags & ECL_TR) ? "mul_batch_raw" : nullptr, n, out, cap, nout, true, false};
   int rc;
   if ((rc = f.begin()) != ECL_OK) return rc;

@@ -29,6 +29,8 @@
 #include "aux_kernels.h"
 #include "herd_kernel.h"
 #include "bip39.h"
+#include "gen.h"
+#include "../host/gen_plan.h"
 #include "devbuf.h"
 #include "callstate.h"
 
@@ -92,6 +94,10 @@ struct ecl_hip {
   // before this one returned ECL_OK or ECL_E_OVERFLOW - what a reuse = 1 call is checked against
   devbuf<u32> d_nodes; u32 seed_n = 0, seed_pass_len = 0; uint8_t seed_pass[BIP39_PASS_MAX] = {};
   bool seed_have = false, seed_last_ok = false;
+  // ECL_GEN (not part of `flags` either): ecl_hip_mul_batch_raw takes a template and generates the lines (abi_gen.h).  The template the device
+  // holds in d_gen, as the caller gave it (gen_blob: what the next call's is compared with) and as it was sent (gen_img: lives until the copy is done)
+  bool gen = false;
+  devbuf<u32> d_gen; std::vector<uint8_t> gen_blob; std::vector<u32> gen_img;
   hipStream_t copy_stream = nullptr, stream2 = nullptr;  // `mul`: the copy engine's stream; the second compute stream (pieces alternate)
   hipEvent_t ev_copied[MUL_NBUF] = {}, ev_free[MUL_NBUF] = {}, ev_fork = nullptr, ev_join = nullptr;
   hipStream_t prep_stream = nullptr; hipEvent_t ev_hashed[MUL_NBUF] = {};  // `mul -raw`: the lines are hashed on a stream of their own, ahead of the pieces
@@ -179,6 +185,10 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   const u32 bip39 = flags & ECL_KDF_BIP39;
   if (bip39 && (kdf || (flags & (ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX | ECL_MASK)))) return ECL_E_ARG;
   flags &= ~ECL_KDF_BIP39;
+  // lines generated on the device from a template (ECL_GEN): beside the same contexts, with or without an ECL_KDF_* bit, not beside ECL_KDF_BIP39
+  const u32 gen = flags & ECL_GEN;
+  if (gen && (bip39 || (flags & (ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX | ECL_MASK)))) return ECL_E_ARG;
+  flags &= ~ECL_GEN;
   if (!out || ord_offs > 255 || !(flags & (types | ECL_ETH | ECL_TR | ECL_PUB)) ||
       (flags & ~(types | ECL_ETH | ECL_TR | ECL_PUB | ECL_ENDO | ECL_ORIGIN | ECL_INSERT | ECL_HERD | ECL_PREFIX | ECL_MASK)))
     return ECL_E_ARG;
@@ -199,7 +209,7 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   int n = ecl_hip_device_count();
   if (device < 0 || device >= n) return ECL_E_NODEV;
   ecl_hip* h = new ecl_hip();
-  h->dev = device, h->flags = flags, h->kdf = kdf, h->bip39 = bip39 != 0, h->offs = ord_offs, h->la_max = la_default_max();
+  h->dev = device, h->flags = flags, h->kdf = kdf, h->bip39 = bip39 != 0, h->gen = gen != 0, h->offs = ord_offs, h->la_max = la_default_max();
   *out = h;
   HIPCHK(h, hipSetDevice(device));
   HIPCHK(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
@@ -217,7 +227,7 @@ int ecl_hip_open(ecl_hip** out, int device, uint32_t flags, uint32_t ord_offs) {
   static std::mutex mu;
   static std::set<u64> passed;
   const char* skip = getenv("ECL_HIP_SKIP_SELFTEST");
-  const u64 key = (u64)device << 32 | (flags | kdf | bip39);
+  const u64 key = (u64)device << 32 | (flags | kdf | bip39 | gen);  // (every bit of ecl_hip_open's flags: no two kernel selections share a record)
   {
     std::lock_guard<std::mutex> lk(mu);
     if ((skip && skip[0] == '1') || passed.count(key)) return ECL_OK;
@@ -1028,5 +1038,6 @@ extern "C" int ecl_hip_add_range(ecl_hip* h, const uint64_t start[4], uint64_t n
 
 #include "abi_mul.h"
 #include "abi_seed.h"
+#include "abi_gen.h"
 #include "abi_tr.h"
 #include "abi_diag.h"

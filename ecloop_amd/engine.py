@@ -353,6 +353,151 @@ def bip39_key(phrase, path, passphrase=b""):
     return k
 
 
+# ----------------------------------------------------------------------------------------------- generated pass phrases (brain)
+# The mirror of ecloop_amd/host/gen_plan.h (the template is defined there).  A template is `positions`: a list of positions, each a list
+# of alternatives (bytes objects).  Candidate i takes alternative d_p of position p, i = sum d_p * prod_{q > p} c_q: the last position
+# runs fastest.
+GEN_POS_MAX, GEN_ALT_LEN_MAX, GEN_L_MAX, GEN_NALT_MAX, GEN_POOL_MAX = 16, 255, 256, 1 << 22, 1 << 28
+BRAIN_CALL = 1 << 24
+_GEN_SPECIALS = b" !\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~"
+_GEN_LOWER, _GEN_UPPER, _GEN_DIGITS = bytes(range(97, 123)), bytes(range(65, 91)), b"0123456789"
+GEN_CLASSES = {"l": _GEN_LOWER, "u": _GEN_UPPER, "d": _GEN_DIGITS, "h": b"0123456789abcdef", "s": _GEN_SPECIALS,
+               "a": _GEN_LOWER + _GEN_UPPER + _GEN_DIGITS + _GEN_SPECIALS}
+
+
+def brain_words(text):
+    """the words of a word list (bytes): cut at newlines as `mul -raw` cuts lines - one '\\r' before the newline dropped, empty lines
+    skipped, duplicates kept"""
+    words = [w[:-1] if w.endswith(b"\r") else w for w in bytes(text).split(b"\n")]
+    words = [w for w in words if w]
+    if any(len(w) > GEN_ALT_LEN_MAX for w in words):
+        raise ValueError("a word is longer than 255 bytes")
+    return words
+
+
+def _brain_set(spec, name):
+    """-1 ... -4: @file (its words), or literal bytes and classes -> one-byte alternatives in the order given, none twice"""
+    spec = spec.encode("latin-1") if isinstance(spec, str) else bytes(spec)
+    if spec[:1] == b"@":
+        words = brain_words(open(spec[1:].decode("latin-1"), "rb").read())
+        if not words:
+            raise ValueError("-%s: the word list holds no word" % name)
+        return words
+    out, i = [], 0
+    while i < len(spec):
+        c = spec[i:i + 1]
+        if c == b"?":
+            i += 1
+            x = spec[i:i + 1].decode("latin-1")
+            if x != "?" and x not in GEN_CLASSES:
+                raise ValueError("-%s: unknown class ?%s" % (name, x))
+            c = b"?" if x == "?" else GEN_CLASSES[x]
+        for b in c:
+            if bytes([b]) in out:
+                raise ValueError("-%s: the byte %r is in the set twice" % (name, chr(b)))
+            out.append(bytes([b]))
+        i += 1
+    if not out:
+        raise ValueError("-%s: the set is empty" % name)
+    return out
+
+
+def parse_mask(mask, custom=None):
+    """the command line's -mask (and custom = {1: set, ...}: a set's text as -1 ... -4 takes it, or a list of bytes objects) -> positions"""
+    mask = mask.encode("latin-1") if isinstance(mask, str) else bytes(mask)
+    sets = {int(k): (list(v) if isinstance(v, (list, tuple)) else _brain_set(v, k)) for k, v in (custom or {}).items()}
+    positions, run, i = [], b"", 0
+
+    def flush():
+        nonlocal run
+        if run:
+            positions.append([run])
+            run = b""
+
+    while i < len(mask):
+        c = mask[i:i + 1]
+        if c != b"?" or mask[i + 1:i + 2] == b"?":
+            if c == b"?":
+                i += 1
+            if len(run) == GEN_ALT_LEN_MAX:
+                flush()
+            run += mask[i:i + 1]
+            i += 1
+            continue
+        x = mask[i + 1:i + 2].decode("latin-1")
+        flush()
+        if x in ("1", "2", "3", "4"):
+            if int(x) not in sets:
+                raise ValueError("invalid -mask: ?%s needs -%s <set>" % (x, x))
+            positions.append(list(sets[int(x)]))
+        elif x in GEN_CLASSES:
+            positions.append([bytes([b]) for b in GEN_CLASSES[x]])
+        else:
+            raise ValueError("invalid -mask: unknown class ?%s" % x)
+        i += 2
+    flush()
+    if not positions:
+        raise ValueError("invalid -mask: the template is empty")
+    brain_count(positions)
+    return positions
+
+
+def brain_count(positions):
+    """T, the number of candidates; ValueError for a template outside the format's limits"""
+    if not 1 <= len(positions) <= GEN_POS_MAX:
+        raise ValueError("invalid -mask: more than 16 positions" if positions else "a template has 1 ... 16 positions")
+    if any(not p for p in positions) or any(len(a) > GEN_ALT_LEN_MAX for p in positions for a in p):
+        raise ValueError("a position has at least one alternative, an alternative at most 255 bytes")
+    if sum(max(len(a) for a in p) for p in positions) > GEN_L_MAX:
+        raise ValueError("the template's candidates are longer than 256 bytes")
+    if sum(len(p) for p in positions) > GEN_NALT_MAX or sum(len(a) for p in positions for a in p) > GEN_POOL_MAX:
+        raise ValueError("a template has at most 2^22 alternatives and 2^28 bytes of them")
+    T = 1
+    for p in positions:
+        T *= len(p)
+    if T >= 1 << 64:
+        raise ValueError("the template has 2^64 candidates or more")
+    return T
+
+
+def brain_table(positions):
+    """positions -> the packed blob of include/ecloop_hip.h (ECL_GEN): header, pos[], alt[], pool"""
+    brain_count(positions)
+    pos, alt, pool, first = b"", b"", b"", 0
+    for p in positions:
+        pos += len(p).to_bytes(4, "little") + first.to_bytes(4, "little")
+        first += len(p)
+        for a in p:
+            alt += len(pool).to_bytes(4, "little") + len(a).to_bytes(4, "little")
+            pool += bytes(a)
+    return b"GEN\0" + bytes([len(positions), 0, 0, 0]) + first.to_bytes(4, "little") + len(pool).to_bytes(4, "little") + pos + alt + pool
+
+
+def brain_positions(blob):
+    """the packed blob -> positions (what brain_table packed)"""
+    blob = bytes(blob)
+    if blob[:4] != b"GEN\0" or len(blob) < 16:
+        raise ValueError("not a template")
+    npos, nalt, pool_bytes = blob[4], int.from_bytes(blob[8:12], "little"), int.from_bytes(blob[12:16], "little")
+    u32 = lambda at: int.from_bytes(blob[at:at + 4], "little")
+    alt_at, pool_at = 16 + 8 * npos, 16 + 8 * npos + 8 * nalt
+    if len(blob) != pool_at + pool_bytes:
+        raise ValueError("not a template")
+    return [[blob[pool_at + u32(alt_at + 8 * a): pool_at + u32(alt_at + 8 * a) + u32(alt_at + 8 * a + 4)] for a in range(u32(16 + 8 * p + 4), u32(16 + 8 * p + 4) + u32(16 + 8 * p))]
+            for p in range(npos)]
+
+
+def brain_candidate(positions, i):
+    """candidate i (bytes) of the template"""
+    digits = []
+    for p in reversed(positions):
+        i, d = divmod(i, len(p))
+        digits.append(d)
+    if i:
+        raise ValueError("the index is outside the template")
+    return b"".join(p[d] for p, d in zip(positions, reversed(digits)))
+
+
 class FoundRecord:
     __slots__ = ("label", "h160", "pk", "prefix", "address", "split", "path", "phrase")
 
@@ -395,7 +540,7 @@ class KeySearch:
     """ctx_t + cmd_add / cmd_mul for one GPU."""
 
     def __init__(self, flt, device=0, a33=True, a65=False, endo=False, ord_offs=0, verify=True, launch_keys=1 << 32,
-                 half_group=0, max_lanes=0, device_cls=None, p2sh=False, eth=False, tr=False, pub=False, prefix=False, origin=None, mask=False, kdf=None, bip39=False):
+                 half_group=0, max_lanes=0, device_cls=None, p2sh=False, eth=False, tr=False, pub=False, prefix=False, origin=None, mask=False, kdf=None, bip39=False, gen=False):
         if pub:
             a33 = False  # public keys are searched alone (with or without the endomorphism)
         elif tr:
@@ -416,6 +561,9 @@ class KeySearch:
         self.bip39 = bool(bip39)  # the context of cmd_seed: the lines of mul_batch_raw are BIP39 phrases
         if bip39 and self.kdf:  # ("sha256" is no kdf: None by now)
             raise ValueError("bip39 does not go with a kdf")
+        self.gen = bool(gen)  # the context of cmd_brain: the lines of mul_batch_raw are generated on the device from a template
+        if gen and (bip39 or prefix or mask):
+            raise ValueError("gen does not go with bip39, prefix or mask")
         if origin is not None and not (prefix or mask):
             raise ValueError("an origin goes with the prefix search only (prefix_search(origin=(x, y)))")
         # split-key search (prefix_search(origin=)): the walk is O + k G, the records' keys are partial keys
@@ -424,7 +572,7 @@ class KeySearch:
         # the types it is not asked for: a flag is passed only when set.  prefix / mask: flt is a PrefixFilter / MaskFilter, whose table
         # stands where the bloom words stand (prefix_search)
         kw = {name: value for name, value in dict(p2sh=bool(p2sh), eth=bool(eth), tr=bool(tr), pub=bool(pub), prefix=bool(prefix), mask=bool(mask),
-                                                  kdf=self.kdf, bip39=self.bip39, origin=origin is not None).items() if value}
+                                                  kdf=self.kdf, bip39=self.bip39, gen=self.gen, origin=origin is not None).items() if value}
         self.dev = (device_cls or Device)(device, a33=a33, a65=a65, endo=endo, ord_offs=ord_offs, **kw)
         if half_group or max_lanes:
             self.dev.set_geometry(half_group, max_lanes)
@@ -559,6 +707,31 @@ class KeySearch:
                     rec.path, rec.phrase = format_path(path), part[int(r["key_offset"])]
                 self._search_lines(lambda c: self.dev.seed_batch(part, path, passphrase=passphrase, reuse=i > 0, cap=c), len(part), cap,
                                    lambda r: bip39_key(part[int(r["key_offset"])], path, passphrase), self.verify, more)
+        return self.found
+
+    def cmd_brain(self, mask, custom=None, first=0, last=None, cap=4096):
+        """`brain`: the candidates first ... last (both included; default: all) of the template `mask` (text for parse_mask with `custom`,
+        or positions) - on a KeySearch(gen=True), in calls of 2^24.  The phrase of a found line is brain_candidate's and its key that
+        phrase's kdf_digest, both computed here, and every hit is re-derived from that key through the device: a generator that
+        disagrees raises the hash mismatch error.  Records carry .path (the index in hex) and .phrase."""
+        if not self.gen:
+            raise ValueError("cmd_brain goes with KeySearch(gen=True)")
+        positions = parse_mask(mask, custom) if isinstance(mask, (str, bytes)) else [list(p) for p in mask]
+        T = brain_count(positions)
+        last = T - 1 if last is None else last
+        if not 0 <= first <= last < T:
+            raise ValueError("first ... last lies in 0 ... T - 1 = %x" % (T - 1))
+        blob = brain_table(positions)
+        at = first
+        while at <= last:
+            n = min(BRAIN_CALL, last - at + 1)
+
+            def more(rec, r):
+                rec.path, rec.phrase = "%x" % (at + int(r["key_offset"])), brain_candidate(positions, at + int(r["key_offset"]))
+            raw = collect_records(lambda c: self.dev.brain_batch(blob, at, n, cap=c), self.dev, cap)
+            self._collect(raw, lambda r: int.from_bytes(kdf_digest(self.kdf or "sha256", brain_candidate(positions, at + int(r["key_offset"]))), "big"), self.verify, more)
+            self.k_checked += n
+            at += n
         return self.found
 
 

@@ -193,7 +193,8 @@ typedef struct {
   const char *paths[9]; int npaths;  /* seed: every -path in order (a ninth is kept so that cli_seed.h can refuse it by name); path_missing: a last -path without a value */
   bool path_missing;
   bool quiet, endo, raw, bin, version, host_only, rnd_jobs, as_mul;
-  bool keys;                         /* seed -keys (hidden): the host's own derivation alone, no GPU */
+  bool keys;                         /* seed -keys, brain -keys (hidden): the host's own derivation alone, no GPU */
+  const char *mask, *set[4];         /* brain: -mask, -1 ... -4 (gen_plan.h) */
 } opts_t;
 typedef struct { const char *flag; size_t at; bool takes_value; } optdef_t;
 static const optdef_t OPTDEFS[] = {
@@ -207,7 +208,9 @@ static const optdef_t OPTDEFS[] = {
     {"-p", offsetof(opts_t, prefix), true},      {"-part", offsetof(opts_t, part), true},  {"-split", offsetof(opts_t, split), true},
     {"-herd", offsetof(opts_t, herd), true},      {"-dp", offsetof(opts_t, dp), true},      {"-max", offsetof(opts_t, maxf), true},
     {"-kdf", offsetof(opts_t, kdf), true},        {"-pass", offsetof(opts_t, pass), true},
-    {"-keys", offsetof(opts_t, keys), false},
+    {"-keys", offsetof(opts_t, keys), false},     {"-mask", offsetof(opts_t, mask), true},
+    {"-1", offsetof(opts_t, set[0]), true},       {"-2", offsetof(opts_t, set[1]), true},   {"-3", offsetof(opts_t, set[2]), true},
+    {"-4", offsetof(opts_t, set[3]), true},
 };
 static void opts_parse(opts_t *o, int argc, const char **argv) {
   memset(o, 0, sizeof *o);

@@ -12,6 +12,8 @@ typedef struct {
   u64 found, checked;
   bool prefix;     /* -p: the status line shows `edge` as well */
   u64 edge;        /* -p: records dropped because their address text matched no pattern (a range's end values) */
+  bool brain;      /* brain: the status line shows the candidate index reached and the template's count as well (a run resumes with -r) */
+  u64 brain_at, brain_T;
   u64 t_start, t_progress, t_shown; /* ms: clock start, last progress report, last status print */
   u64 paused_ms, paused_since;
   volatile bool paused; /* read by the device threads without the mutex, like the reference's flag (main.c:153) */
@@ -39,8 +41,9 @@ static void status_show_locked(report_t *r) {
   double secs = (run_ms < 1 ? 1 : run_ms) / 1000.0;
   const char *hint = r->closed ? "" : r->paused ? " ('r' \xe2\x80\x93 resume)" : " ('p' \xe2\x80\x93 pause)";
   erase_status_line();
-  char edge[48] = "";
+  char edge[64] = "";
   if (r->prefix) snprintf(edge, sizeof edge, " ~ edge: %llu", (unsigned long long)r->edge);
+  if (r->brain) snprintf(edge, sizeof edge, " ~ index: %llx / %llx", (unsigned long long)r->brain_at, (unsigned long long)r->brain_T);
   fprintf(stderr, "%.2fs ~ %.2f Mkeys/s ~ %'llu / %'llu%s%s%c", secs, r->checked / secs / 1000000, (unsigned long long)r->found,
           (unsigned long long)r->checked, edge, hint, r->closed ? '\n' : '\r');
   fflush(stderr);

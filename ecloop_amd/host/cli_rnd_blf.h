@@ -246,6 +246,7 @@ static void usage(const char *prog) { /* the reference's help text (main.c:750-7
       "  bsgs            - find the private key of a known public key in given range (baby-step giant-step, one GPU)\n",
       "  kangaroo        - the same for ranges too wide for bsgs (Pollard's lambda method, one GPU)\n",
       "  seed            - search the BIP32 keys of BIP39 phrases (from stdin, one per line; derived on the GPU, one GPU)\n",
+      "  brain           - search the keys of pass phrases generated on the GPU from a template (masks, word lists; one GPU)\n",
       "\nCompute options:\n",
       "  -f <file>       - filter file to search (list of hashes or bloom fitler)\n",
       "  -p <pattern>    - add, rnd: search addresses that START with the pattern, or with any pattern of a file (one per line), in\n",
@@ -279,6 +280,14 @@ static void usage(const char *prog) { /* the reference's help text (main.c:750-7
       "                    m/44'/0'/0'/0/0; s m/49'/0'/0'/0/0; t m/86'/0'/0'/0/0; e m/44'/60'/0'/0/0)\n",
       "  -n <count>      - also search the next count - 1 values of each path's last element (1 ... 1024, default: 1)\n",
       "  -pass <text>    - the BIP39 passphrase (at most 99 bytes, default: none)\n",
+      "\nbrain options:\n",
+      "  -f, -a, -o, -q  - as above; -kdf as for mul -raw.  A found line ends with the candidate's index (hex) and the phrase\n",
+      "  -mask <templ>   - the template: ?l a-z, ?u A-Z, ?d 0-9, ?h 0-9a-f, ?s the 33 printable specials, ?a all 95 (?l?u?d?s), ?1 ... ?4 the\n",
+      "                    sets below, ?? a '?', anything else literal: 'pass?d?d?d?d', '?1 ?2' - in quotes.  The last position runs fastest;\n",
+      "                    at most 16 positions (a run of literals is one), candidates of at most 256 bytes, fewer than 2^64 of them\n",
+      "  -1 ... -4 <set> - the bytes of ?1 ... ?4 (literals and the classes above, none twice), or @file: every line of the file is a word\n",
+      "                    (duplicate words are kept and give duplicate candidates)\n",
+      "  -r <a:b>        - candidate indices in hex, both ends included (default: all); the status line shows the index reached\n",
       "\nbsgs options:\n",
       "  -k <pubkey>     - the public key (66 hex digits 02.. / 03.., or 130 digits 04..), or a file of them, one per line\n",
       "  -r <range>      - the range a:b that holds the key, in hex, both ends included (example: 8000:ffffff)\n",

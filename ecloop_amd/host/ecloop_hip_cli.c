@@ -68,6 +68,8 @@ typedef struct { u64 w[4]; } sc; /* 256-bit scalar, little-endian limbs (the ref
 #include "cli_splitkey.h"
 #include "bip39_host.h"
 #include "cli_seed.h"
+#include "gen_plan.h"
+#include "cli_brain.h"
 
 /* ------------------------------------------------------------------------------------------- device bring-up */
 /* Device contexts of a run: context g works on GPU (g mod shown) mod real, where `shown` is the -t count clamped to
@@ -198,6 +200,8 @@ int main(int argc, const char **argv) {
   /* -k with add / rnd / mul (no reference counterpart): the split-key form of -p, nowhere else (cli_splitkey.h) */
   /* seed (no reference counterpart): BIP39 phrases -> BIP32 keys on the device; its own option checks and context (cli_seed.h) */
   if (!strcmp(verb, "seed")) return cmd_seed(&run);
+  /* brain (no reference counterpart): pass phrases generated on the device from a template; its own option checks, -kdf and context (cli_brain.h) */
+  if (!strcmp(verb, "brain")) return cmd_brain(&run);
   /* -kdf (no reference counterpart): the hash that turns a line of `mul -raw` into a key - sha256 (the default: -raw as it always was), or
      what Ethereum brain wallets use: keccak, sha3, camp2 (keccak_host.h).  Checked before anything is opened */
   if (o->kdf) {

@@ -186,7 +186,26 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
    HMACs per phrase, not 4096 compressions.  reuse = 1 is ECL_E_ARG when no nodes are kept, when n or pass differs from the kept nodes',
    or when the previous ecl_hip_mul_batch_raw call on the context returned neither ECL_OK nor ECL_E_OVERFLOW (calls of other functions in
    between are not looked at: none of them touches the kept nodes).  ecl_hip_selftest of such a context also runs
-   both derivation kernels on BIP39's test phrase (ECL_E_SELFTEST). */
+   both derivation kernels on BIP39's test phrase (ECL_E_SELFTEST).
+   ECL_GEN (no reference counterpart): the lines of ecl_hip_mul_batch_raw are not sent but generated on the device, from a template - masks,
+   dictionaries, their combinations (the `brain` command).  Valid beside the contexts the ECL_KDF_* field is valid beside, with or
+   without ECL_KDF_KECCAK / ECL_KDF_SHA3 / ECL_KDF_CAMP2; ECL_E_ARG beside ECL_KDF_BIP39, ECL_ORIGIN, ECL_INSERT, ECL_HERD, ECL_PREFIX or
+   ECL_MASK, alone, or beside a type set that is itself refused.  ONLY ecl_hip_mul_batch_raw changes: `text` / `text_bytes` are the
+   template, `lines` points to ONE u64, the index of the call's first candidate, n (<= 2^26) is the number of candidates, and key_offset
+   of a record is index - first.  The template (host/gen_plan.h is its definition): P positions, 1 <= P <= 16; position p has c_p >= 1
+   alternatives of 0 ... 255 bytes each; L = the sum over the positions of the longest alternative, at most 256; at most 2^22
+   alternatives and 2^28 bytes of them in all; T = the product of the c_p, below 2^64.  Candidate i, 0 <= i < T, has the digits d_p with
+   i = sum d_p * prod_{q > p} c_q (the last position runs fastest) and is alt[0][d_0] || ... || alt[P - 1][d_{P - 1}].  Packed, little-endian:
+       u8 magic[4] = "GEN\0";  u8 npos;  u8 zero[3];  u32 nalt;  u32 pool_bytes;
+       { u32 count; u32 first; } pos[npos]    first = index of the position's first alternative: positions in order, contiguous
+       { u32 off;  u32 len;   } alt[nalt]     off into the pool
+       u8 pool[pool_bytes]
+   A malformed template (wrong magic, a zero byte that is not zero, counts that do not add up to nalt, an alternative outside the pool,
+   a length that is not 16 + 8 npos + 8 nalt + pool_bytes, a limit above exceeded), T >= 2^64 and first + n > T are ECL_E_ARG with a
+   message in ecl_hip_last_error, and nothing is launched.  The template goes to the device when it differs from the one the context
+   holds (the context keeps a copy and compares); a call with the same template sends its first index alone.  Everything around the
+   text - pieces, coverage, overflow, ecl_hip_fetch_found, the list confirm - is as on the context without the flag, and so is every
+   other call.  ecl_hip_selftest of such a context also expands a built-in template against literal strings (ECL_E_SELFTEST). */
 #define ECL_ADDR33 1u
 #define ECL_ADDR65 2u
 #define ECL_ENDO 4u
@@ -203,6 +222,7 @@ typedef struct ecl_hip ecl_hip; /* opaque per-device context */
 #define ECL_KDF_SHA3 0x8000u   /* 32768 */
 #define ECL_KDF_CAMP2 0xC000u  /* both: the two bits are one field */
 #define ECL_KDF_BIP39 0x10000u /* 65536 */
+#define ECL_GEN 0x20000u       /* 131072 */
 
 /* return codes */
 #define ECL_OK 0
